@@ -13,10 +13,14 @@ so every timed step accumulates non-zero sums; after the timed region the fused 
 the oracle's esr_sums on the same rows (rel 1e-9), the last output with the first pass bit for bit (full-size determinism),
 and stream 0 carries the input of golden G6 so the result is also checked against the REFERENCE's own output on 65 536 samples.
 
-    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong]
-Rank 0 prints ONE compact JSON line (< 4 KB: headline, roofline, cpu_baseline, checks, one entry per side workload) as the
-LAST line on stdout and writes the full record to --detail-file (default bench_detail.json beside this file; also on stderr
-behind `bench_detail: `).
+    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the result line.  --full adds everything
+else this file measures and checks: the checks above, the step without the warm-start cache, the opt-in kernel engines, the
+loss-dict passes, live PMC traffic, the CPU baseline with the oracle checks and `other_workloads`.  --dump-outputs DIR writes
+what the last timed step returned (dump_outputs below), so that two builds can be compared output for output.
+Rank 0 prints ONE compact JSON line (< 4 KB: headline, roofline and, with --full, cpu_baseline, checks, one entry per side
+workload) as the LAST line on stdout and writes the full record to --detail-file (default bench_detail.json beside this file;
+also on stderr behind `bench_detail: `).
 
 N > 1 runs one process per GPU over RCCL.  Either the caller provides the ranks (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or --
@@ -45,6 +49,7 @@ FLOP_PER_SAMPLE = 25088          # 12 544 FMA: W_hh GEMV 12 288 + W_ih 192 + hea
 BYTES_PER_SAMPLE = 8             # 4 B x in + 4 B y out
 PEAK_FP32_TFLOPS = 157.3         # MI355X fp32 matrix == vector peak (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
+DUMP_Y_BYTES = 48 << 20          # --dump-outputs: the output sample; with the per-stream sums beside it, under 64 MB in all
 
 
 def synth_input(B, T, device, seed):
@@ -144,14 +149,14 @@ def profile_traffic(pattern, key):
                         "command, gfx950 correction applied; not re-measured in this run)")
 
 
-def measure_workload(workload, B, T, steps, warmup, check, dev, threads=1, delay_mode="auto", live=False):
+def measure_workload(workload, B, T, steps, warmup, check, dev, threads=1, delay_mode="auto", live=False, full=True):
     """One single-GPU workload beside the headline, `steps` timed passes over a resident batch of B distinct streams:
       "diffdel"  BASELINE configs[2]: DiffDelGRU-HS[64] (CHOWTAPE_WOWFLUTTER weights, D = 1847) predict
       "tcn"      BASELINE configs[3]: the TCN contrast point
       "gru"      the headline's model at another batch size -- the per-GPU shapes of configs[4]'s strong-scaling legs
     -> dict with the whole-pass rate, the dominant kernel's event-timed launch duration and roofline, determinism of the
     output and -- when `check` (the CPU leg; the oracle is the checker, never the thing measured) -- scattered streams
-    against the C oracle over the whole sequence."""
+    against the C oracle over the whole sequence.  `full`: also time the two-pass form of the fused DiffDelGRU step."""
     import ntm_amd
     from ntm_amd import weights
     x = synth_input(B, T, dev, seed=1234)
@@ -277,21 +282,22 @@ def measure_workload(workload, B, T, steps, warmup, check, dev, threads=1, delay
                     roof["traffic_source"] = ("profiles/" + os.path.basename(files[-1]) + " (rocprofv3 --pmc passes of `bench.py "
                                               "--workload diffdel`; not re-measured in this run" + (f"; live passes: {why}" if why else "") + ")")
                 roof["algorithmic_bytes"] = 16.0 * B * T
-            model.delay_mode = "two_pass"
-            t1, g1, d1 = [], [], []
-            for i in range(1 + steps):
-                ev0.record(); y2 = run(); ev1.record(); torch.cuda.synchronize()
-                if i:
-                    t1.append(ev0.elapsed_time(ev1)); g1.append(kev[0].elapsed_time(kev[1])); d1.append(kev[1].elapsed_time(kev[2]))
-            dsec = float(np.mean(d1)) * 1e-3
-            alg = 12.0 * B * T + 8.0 * B * model.diffdel.max_delay
-            roof["two_pass"] = {"device_ms_per_step": float(np.mean(t1)), "gru_kernel_ms": float(np.mean(g1)),
-                                "delay_pass_ms": 1e3 * dsec, "delay_pass_kernel": "delay_apply_kernel + delay_update_kernel",
-                                "delay_pass_hbm": {"achieved": alg / dsec / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                                   "frac": alg / dsec / 1e9 / PEAK_HBM_GBS, "bytes_per_sample": 12},
-                                "identical_output": bool(torch.equal(y2, y))}
-            model.delay_mode = delay_mode
-            del y2
+            if full:
+                model.delay_mode = "two_pass"
+                t1, g1, d1 = [], [], []
+                for i in range(1 + steps):
+                    ev0.record(); y2 = run(); ev1.record(); torch.cuda.synchronize()
+                    if i:
+                        t1.append(ev0.elapsed_time(ev1)); g1.append(kev[0].elapsed_time(kev[1])); d1.append(kev[1].elapsed_time(kev[2]))
+                dsec = float(np.mean(d1)) * 1e-3
+                alg = 12.0 * B * T + 8.0 * B * model.diffdel.max_delay
+                roof["two_pass"] = {"device_ms_per_step": float(np.mean(t1)), "gru_kernel_ms": float(np.mean(g1)),
+                                    "delay_pass_ms": 1e3 * dsec, "delay_pass_kernel": "delay_apply_kernel + delay_update_kernel",
+                                    "delay_pass_hbm": {"achieved": alg / dsec / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                                       "frac": alg / dsec / 1e9 / PEAK_HBM_GBS, "bytes_per_sample": 12},
+                                    "identical_output": bool(torch.equal(y2, y))}
+                model.delay_mode = delay_mode
+                del y2
         else:
             # K2 as a separate streaming pass: pre_d and d read once, y written once = 12 algorithmic bytes per sample
             # (the two gathered taps come from pre_d, i.e. from the same bytes); the carried buffer adds 8 D bytes per stream
@@ -514,7 +520,8 @@ def compact_line(out, detail_file):
           "esr_sums_max_rel": _sig((k.get("esr_sums_vs_oracle") or {}).get("max_rel"), 3), "tolerance": 1e-5}
     if "vs_oracle_max_abs" in k:                  # a --workload line: measure_workload's own checks
         ck = {"deterministic": k.get("deterministic"), "streams_vs_oracle_max_abs": _sig(k.get("vs_oracle_max_abs"), 3), "tolerance": 1e-5}
-    c["checks"] = {n: v for n, v in ck.items() if v is not None}
+    if k:                                         # a plain run has no checks: they run under --full
+        c["checks"] = {n: v for n, v in ck.items() if v is not None}
     ok = out.get("other_kernels") or {}
     eng = {n: {"kernel_ms": _sig(ok[n]["kernel_ms"], 5), "vs_exact_fp32_max_abs": _sig(ok[n]["max_abs_diff_vs_exact_fp32_whole_batch"], 3)}
            for n in ("f16x3", "bf16x3") if n in ok}
@@ -569,13 +576,31 @@ def emit(out, detail_path):
     sys.stdout.flush()
 
 
+def dump_outputs(d, y, sums, res):
+    """--dump-outputs: what a caller of the timed step received in the LAST timed step (rank 0's part), one .npy per array:
+      y.npy         float32 (n, T): the output of n streams -- the whole batch when it fits DUMP_Y_BYTES, else a fixed sample
+                    of streams (default_rng(0), sorted), each over the first DUMP_Y_BYTES / 4 samples at most
+      esr_sums.npy  float64 (B, 2): every stream's [sum (t-y)^2, sum t^2] of the loss leg
+      loss.npy      float64 (4,): the job-wide loss scalars [mean segment loss, segments, sum err^2, sum tgt^2]
+    The inputs are a function of the arguments, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(d, exist_ok=True)
+    B, T = y.shape[0], y.shape[-1]
+    n = max(1, min(B, DUMP_Y_BYTES // (4 * T)))
+    rows = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    ys = y[torch.from_numpy(rows).to(y.device), 0, :DUMP_Y_BYTES // 4]
+    np.save(os.path.join(d, "y.npy"), ys.float().cpu().numpy())
+    np.save(os.path.join(d, "esr_sums.npy"), sums.double().cpu().numpy())
+    np.save(os.path.join(d, "loss.npy"), np.array([res["mean_segment_loss"], res["segments"], res["sum_err2"], res["sum_tgt2"]],
+                                                  np.float64))
+
+
 def side_workload(a):
     """`--workload diffdel | tcn`: BASELINE configs[2] / configs[3] at the headline's batch as a line of their own
     (single GPU, not the headline metric).  Like the headline line, the JSON carries the roofline of the dominant kernel
     with its event-timed launch duration; for the DiffDelGRU step the HBM roofline of the delay-line pass sits beside it."""
     assert torch.cuda.is_available()
-    r = measure_workload(a.workload, a.batch, a.samples, a.steps, a.warmup, not a.no_cpu_baseline, torch.device("cuda", 0),
-                         threads=_host_threads(), delay_mode=a.delay_mode)
+    r = measure_workload(a.workload, a.batch, a.samples, a.steps, a.warmup, a.full and not a.no_cpu_baseline, torch.device("cuda", 0),
+                         threads=_host_threads(), delay_mode=a.delay_mode, full=a.full)
     emit({
         "metric": f"audio samples/sec (44.1 kHz) {a.workload}, batch={a.batch}x{a.samples}", "value": r["value"],
         "unit": "samples/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": r["ms_per_step"],
@@ -646,7 +671,7 @@ def live_traffic(kernel_regex, extra_args=(), per_forward=None):
             for c in ("FETCH_SIZE", "WRITE_SIZE"):
                 d = os.path.join(tmp, c)
                 cmd = [prof, "--kernel-trace", "--pmc", c, "--output-format", "csv", "-d", d, "-o", "pmc", "--", sys.executable,
-                       os.path.abspath(__file__), "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--other", "off",
+                       os.path.abspath(__file__), "--full", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--other", "off",
                        "--traffic", "off", "--detail-file", os.path.join(tmp, c + "_detail.json")] + list(extra_args)
                 env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK",
                                                                       "ROLE_RANK", "MASTER_ADDR", "MASTER_PORT", "NTM_DIST_FORCE_INIT")
@@ -821,15 +846,15 @@ def main():
                     help="cpu_baseline: full = 16 x 8192 best of 3 + 64 x 8192 (about 10 s); small = 16 x 8192 once (tests)")
     ap.add_argument("--no-extra", action="store_true", help="skip the opt-in f16x3 kernel leg")
     ap.add_argument("--other", default="auto", choices=["auto", "on", "off"],
-                    help="attach `other_workloads` (configs[2], [3] and the per-GPU shapes of configs[4]) to the line: "
+                    help="attach `other_workloads` (configs[2], [3] and the per-GPU shapes of configs[4]) to the --full line: "
                          "auto = only for the default single-GPU workload (4096 x 65536)")
     ap.add_argument("--esr", default="fused", choices=["fused", "pass"],
                     help="the loss leg of a step: fused = the ESR sums are accumulated inside the recurrent launch "
                          "(RNN.forward_esr / ntm_gru_forward_esr); pass = forward launch, then the streaming ESR pass on a side "
                          "stream under the next step's launch (rounds 1-2)")
     ap.add_argument("--traffic", default="auto", choices=["auto", "live", "file", "off"],
-                    help="roofline.traffic of the headline kernel: live = two rocprofv3 --pmc child passes in this run (auto: when "
-                         "rocprofv3 is available), file = the newest profiles/*pmc_traffic_mfma2*.json, off = null")
+                    help="roofline.traffic of the headline kernel: live = two rocprofv3 --pmc child passes in this run (auto: with "
+                         "--full, when rocprofv3 is available; off otherwise), file = the newest profiles/*pmc_traffic_mfma2*.json, off = null")
     ap.add_argument("--delay-mode", default="auto", choices=["auto", "two_pass", "fused"],
                     help="--workload diffdel: the fused DiffDelRNN step (auto: where the matrix-pipe kernel runs) or GRU launch + delay pass")
     ap.add_argument("--other-steps", type=int, default=3)
@@ -844,10 +869,19 @@ def main():
                     help="gru = BASELINE configs[1] (the headline metric); diffdel = configs[2]; tcn = configs[3]")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where rank 0 writes the full record; stdout's last line is the compact record (< 4 KB) that names it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: checks, the no-warm-cache step, the opt-in engines, the loss passes, live "
+                         "PMC traffic, the CPU baseline, other_workloads (each still subject to its own option above)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to DIR/*.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--fail-early", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.workload != "gru":
+        ap.error("--dump-outputs: the headline workload (--workload gru) only")
 
     # N > 1 and nobody gave us a rank: this process becomes the launcher (before anything touches the GPU)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -979,10 +1013,15 @@ def main():
     D.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
     res = results[-1] if results else None
-    # every timed step must produce the SAME loss scalars: compared per rank, bit for bit, on the local vectors (the job-wide
-    # values go through an all-reduce whose ring / tree adds different elements of the buffer in different rank orders, so
-    # two rows that are equal on every rank may differ in the last bit after it), then combined over the ranks
-    steps_identical = D.max_over_ranks(0.0 if all(torch.equal(p, pends[0]) for p in pends) else 1.0, dev) == 0.0
+    sums_last = last["sums"].clone() if "sums" in last else None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, y, sums_last, res)
+    if a.full:
+        # every timed step must produce the SAME loss scalars: compared per rank, bit for bit, on the local vectors (the job-wide
+        # values go through an all-reduce whose ring / tree adds different elements of the buffer in different rank orders, so
+        # two rows that are equal on every rank may differ in the last bit after it), then combined over the ranks
+        steps_identical = D.max_over_ranks(0.0 if all(torch.equal(p, pends[0]) for p in pends) else 1.0, dev) == 0.0
+        deterministic = bool(torch.equal(y, y_first))
     kern_ms = [e0.elapsed_time(e1) for e0, e1 in step_evs]
     # the per-GPU roofline is the SLOWEST rank's mean launch duration; the other ranks' means ride along for the record
     kern_ms_rank = float(np.mean(kern_ms))
@@ -993,30 +1032,29 @@ def main():
     else:
         kall = [kmine]
     kern_by_rank = [{"rank": r, "segments": int(v[1]), "kernel_ms": float(v[0])} for r, v in enumerate(kall)]
-    sums_last = last["sums"].clone() if "sums" in last else None
-    deterministic = bool(torch.equal(y, y_first))
 
     # ---- the same step WITHOUT the warm-start cache (what predict() does on every call in the reference, code/model.py:230:
     #      1024 zero samples, B = 1, recomputed by a launch of its own): 3 steps, same brackets, reported beside ms_per_step
-    model.warm_cache = False
-    one_pass(target)
-    D.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    pends_nc = [one_pass(target)[1] for _ in range(3)]
-    torch.cuda.current_stream().wait_stream(side)
-    res_nc = D.reduce_many(pends_nc)
-    torch.cuda.synchronize()
-    D.barrier()
-    ms_no_cache = 1e3 * D.max_over_ranks(time.perf_counter() - t1, dev) / 3
-    model.warm_cache = True
-    no_cache_same = (D.max_over_ranks(0.0 if all(torch.equal(p, pends[0]) for p in pends_nc) else 1.0, dev) == 0.0) if pends else None
-    del res_nc
+    if a.full:
+        model.warm_cache = False
+        one_pass(target)
+        D.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        pends_nc = [one_pass(target)[1] for _ in range(3)]
+        torch.cuda.current_stream().wait_stream(side)
+        res_nc = D.reduce_many(pends_nc)
+        torch.cuda.synchronize()
+        D.barrier()
+        ms_no_cache = 1e3 * D.max_over_ranks(time.perf_counter() - t1, dev) / 3
+        model.warm_cache = True
+        no_cache_same = (D.max_over_ranks(0.0 if all(torch.equal(p, pends[0]) for p in pends_nc) else 1.0, dev) == 0.0) if pends else None
+        del res_nc
 
     # ---- opt-in kernel variant, reported beside the headline (never part of `value`): the f16x3 GEMV
     #      engine, checked over the whole batch against the exact-fp32 pass
     extra = {}
-    if a.variant in ("auto", "mfma2") and not a.no_extra and world == 1:
+    if a.full and a.variant in ("auto", "mfma2") and not a.no_extra and world == 1:
         model.kernel_variant = "f16x3"
         ms2 = []
         for i in range(2 + 5):
@@ -1127,11 +1165,13 @@ def main():
             "dcpre_sums_max_rel_diff": float(((d_l - d_p).abs() / d_p.abs().clamp_min(1e-300)).max())}
     # achievable HBM rate on this box (state it beside the 8 TB/s vendor peak): device copy of the
     # input batch, read + write bytes over the event time
-    cp = torch.empty_like(x)
-    for _ in range(3):
-        ev0.record(); cp.copy_(x); ev1.record(); torch.cuda.synchronize()
-    hbm_copy_gbs = 2.0 * x.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
-    del cp
+    hbm_copy_gbs = None
+    if a.full:
+        cp = torch.empty_like(x)
+        for _ in range(3):
+            ev0.record(); cp.copy_(x); ev1.record(); torch.cuda.synchronize()
+        hbm_copy_gbs = 2.0 * x.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
+        del cp
     if grouped:
         D.barrier()
         torch.distributed.destroy_process_group()
@@ -1152,17 +1192,19 @@ def main():
     # algorithmic bytes of the dominant launch: x in + y out, + the target it reads when the loss leg rides in it
     bytes_per_sample = BYTES_PER_SAMPLE + (4 if fused_esr else 0)
     hbm_gbs = bytes_per_sample * B * T / kern_s / 1e9
-    checks = {"target": "0.9 * first-pass output + 0.02 * x (not the output: the sums are non-zero)",
-              "job_esr": res["mean_segment_loss"] if res else None, "job_sum_err2": res["sum_err2"] if res else None,
-              "job_sum_tgt2": res["sum_tgt2"] if res else None, "segments": res["segments"] if res else None,
-              "every_timed_step_same_loss": steps_identical, "no_warm_cache_steps_same_loss": no_cache_same,
-              "last_output_equals_first_pass_bitwise": deterministic}
-    if gold is not None:
-        yg = y[0, 0].cpu().numpy()
-        e = gold["y"][0, 0] - yg
-        checks["stream0_vs_reference_max_abs"] = float(np.abs(e).max())
-        checks["stream0_vs_reference_esr"] = float((e[INIT_LEN:] ** 2).mean() /
-                                                   ((gold["y"][0, 0][INIT_LEN:] ** 2).mean() + ESR_EPS))
+    checks = None
+    if a.full:
+        checks = {"target": "0.9 * first-pass output + 0.02 * x (not the output: the sums are non-zero)",
+                  "job_esr": res["mean_segment_loss"] if res else None, "job_sum_err2": res["sum_err2"] if res else None,
+                  "job_sum_tgt2": res["sum_tgt2"] if res else None, "segments": res["segments"] if res else None,
+                  "every_timed_step_same_loss": steps_identical, "no_warm_cache_steps_same_loss": no_cache_same,
+                  "last_output_equals_first_pass_bitwise": deterministic}
+        if gold is not None:
+            yg = y[0, 0].cpu().numpy()
+            e = gold["y"][0, 0] - yg
+            checks["stream0_vs_reference_max_abs"] = float(np.abs(e).max())
+            checks["stream0_vs_reference_esr"] = float((e[INIT_LEN:] ** 2).mean() /
+                                                       ((gold["y"][0, 0][INIT_LEN:] ** 2).mean() + ESR_EPS))
     # HBM bytes per launch from the PMC counters, collected as MI355X_MICROARCH.md prescribes (separate rocprofv3 --pmc
     # passes, gfx950 FETCH_SIZE correction), for the launch THIS rank timed (B streams x T samples).  `--traffic live` (what
     # `auto` does when rocprofv3 is on the PATH): the two passes run NOW, as single-GPU child processes of this line's own
@@ -1171,10 +1213,11 @@ def main():
     # newest profiles/*pmc_traffic* file of the same kernel and shape.
     traffic, traffic_source = None, None
     many = (B + 15) // 16 > torch.cuda.get_device_properties(local).multi_processor_count      # launch_gru_mfma2: YPN 4 / 16
-    if T == 65536 and B > 1024 and a.variant in ("auto", "mfma2") and a.traffic != "off":
+    traffic_mode = a.traffic if a.full or a.traffic != "auto" else "off"
+    if T == 65536 and B > 1024 and a.variant in ("auto", "mfma2") and traffic_mode != "off":
         profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
         rx = r"gru_mfma2_kernel<true, false, 0, 0, " + ("4" if many else "16") + ", false, " + ("true, false>" if fused_esr else "false, false>")
-        if a.traffic == "live" or (a.traffic == "auto" and not profiled):     # never a profiler inside a profiler
+        if traffic_mode == "live" or (traffic_mode == "auto" and not profiled):     # never a profiler inside a profiler
             traffic, traffic_source = live_traffic(rx, ["--esr", a.esr, "--variant", a.variant, "--batch", str(B),
                                                         "--samples", str(a.samples)])
         if traffic is None:
@@ -1215,8 +1258,10 @@ def main():
         "metric": f"audio samples/sec (44.1 kHz) GRU-HS[64], batch={a.batch if a.scaling == 'weak' else B}x{T}"
                   + (f", {world} GPU" if world == 1 and a.scaling == "weak" else f" per GPU, {world} GPU ({a.scaling} scaling, {total_segments} segments)"),
         "value": total_samples / elapsed, "unit": "samples/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "ms_per_step_no_warm_cache": ms_no_cache,
-        "value_no_warm_cache": float(total_segments) * T / (ms_no_cache * 1e-3), "higher_is_better": True,
+        "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
+        **({"ms_per_step_no_warm_cache": ms_no_cache, "value_no_warm_cache": float(total_segments) * T / (ms_no_cache * 1e-3)}
+           if a.full else {}),
+        "higher_is_better": True,
         "scaling": a.scaling, "vs_baseline": None, "dtype": dtype, "data": "synthetic",
         # (the driver keeps 120 characters of this string)
         "config": {"workload": f"GRU-HS[64] {total_segments}x{T} f32 on {world} GPU ({per_gpu}), predict+ESR "
@@ -1233,7 +1278,7 @@ def main():
         "rccl_ranks": world if (backend == "nccl" and grouped) else 0, "ranks": world, "rank_devices": rank_devices,
         "realtime_factor": total_samples / elapsed / FS,
         "roofline": roofline,
-        "checks": checks,
+        **({"checks": checks} if checks else {}),
     }
     info = os.path.join(ROOT, "neural-tape-modeling_amd", "build_info.json")      # written by __graft_entry__.build()
     bi = None
@@ -1258,7 +1303,7 @@ def main():
                                     if want in kk["kernel"] or "gru_lat_kernel" in kk["kernel"]]}
     if extra:
         out["other_kernels"] = extra
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # N > 1: rank 0 alone, after the process group is gone (the other ranks have left; nothing of this is timed)
         out["cpu_baseline"] = cpu_baseline(weights.W_GRU, small=a.cpu_sample == "small")
         out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
@@ -1301,7 +1346,7 @@ def main():
                                                    "esr_max_rel_diff": float(np.abs(esr_dev / esr_or - 1).max())}
     # ---- the BASELINE configs no other driver-run line covers (configs[2], [3], the per-GPU shapes of configs[4]); after
     #      the headline's timed region and CPU leg, which they leave untouched; never part of `value`
-    if world == 1 and (a.other == "on" or (a.other == "auto" and (B, T) == (4096, 65536) and a.variant in ("auto", "mfma2"))):
+    if a.full and world == 1 and (a.other == "on" or (a.other == "auto" and (B, T) == (4096, 65536) and a.variant in ("auto", "mfma2"))):
         del x, y, target, y_first
         torch.cuda.empty_cache()
         out["other_workloads"] = other_workloads(a, dev, check=not a.no_cpu_baseline)

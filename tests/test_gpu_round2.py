@@ -324,7 +324,7 @@ def test_bench_spawns_its_own_ranks_on_one_gpu_over_gloo():
     env["NTM_DIST_BACKEND"] = "gloo"
     for extra, total in ((["--batch", "512"], 1024), (["--scaling", "strong", "--total-batch", "768"], 768)):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                            "--samples", "4096", "--no-cpu-baseline", "--no-extra"] + extra,
+                            "--samples", "4096", "--full", "--no-cpu-baseline", "--no-extra"] + extra,
                            env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         line, out = bench_record(r.stdout)                  # one compact line (< 4 KB) + the detail file it names
@@ -349,7 +349,7 @@ def test_bench_one_rank_process_group_runs_the_rccl_calls():
     env = {k: v for k, v in os.environ.items() if k != "NTM_DIST_BACKEND"}
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NTM_DIST_FORCE_INIT="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--batch", "512", "--samples", "4096", "--no-cpu-baseline", "--no-extra"],
+                        "--batch", "512", "--samples", "4096", "--full", "--no-cpu-baseline", "--no-extra"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line, out = bench_record(r.stdout)

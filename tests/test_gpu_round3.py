@@ -335,7 +335,7 @@ def test_bench_eight_ranks_share_the_gpu_over_gloo():
     and a rank that dies after warm-up brings the whole job down, non-zero, well inside the timeout.
     Reference counterpart: none (scripts/sbatch-train-exp1a.sh:7 runs replicas only)."""
     import time
-    common = ["--gpus", "8", "--steps", "2", "--warmup", "1", "--samples", "4096", "--no-cpu-baseline", "--no-extra"]
+    common = ["--gpus", "8", "--steps", "2", "--warmup", "1", "--samples", "4096", "--full", "--no-cpu-baseline", "--no-extra"]
     env = _clean_env(NTM_DIST_BACKEND="gloo")
     for extra, total in ((["--batch", "64"], 512), (["--scaling", "strong", "--total-batch", "500"], 500)):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra, env=env, capture_output=True,
@@ -366,7 +366,7 @@ def test_bench_line_carries_the_other_workloads():
     as `other_workloads` (here at small shapes, `--other on`): each with kernel, kernel_ms, roofline.frac, determinism
     and scattered streams against the oracle; the headline fields are those of a run without them."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "1040",
-                        "--samples", "4096", "--no-extra", "--other", "on", "--other-steps", "2", "--other-gru-batches", "2048,4112", "--other-tcn-batches", "2048", "--other-diffdel-batches", "",
+                        "--samples", "4096", "--full", "--no-extra", "--other", "on", "--other-steps", "2", "--other-gru-batches", "2048,4112", "--other-tcn-batches", "2048", "--other-diffdel-batches", "",
                         "--cli-segments", "0"],              # (other_workloads.cli: tests/test_gpu_round5.py)
                        env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -388,6 +388,33 @@ def test_bench_line_carries_the_other_workloads():
     e = out["checks"]["esr_sums_vs_oracle"]
     assert out["checks"]["job_esr"] > 1e-4 and e["max_rel"] < 1e-9 and e["esr_max_rel_diff"] < 1e-3 and min(e["esr_device"]) > 0
     assert out["ms_per_step_no_warm_cache"] > 0 and ow["tcn"]["roofline"]["bytes_per_sample_if_fused"] == 8
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline fields and nothing that takes runs or checks of its own;
+    --dump-outputs writes what the last timed step returned -- a seeded sample of streams of the output (the whole batch
+    would exceed the budget here), every stream's ESR sums, the job's loss scalars -- and a second run with the same
+    arguments writes the same files."""
+    args = ["--steps", "3", "--warmup", "1", "--batch", "1040", "--samples", "16384", "--detail-file", str(tmp_path / "detail.json")]
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d)], env=_clean_env(),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line, out = bench_record(r.stdout)
+        assert line["steps"] == 3 and line["unit"] == "samples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert abs(line["value"] - 1040 * 16384 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        assert not {"checks", "cpu_baseline", "opt_in_engines", "legs", "value_no_warm_cache"} & set(line)
+        assert not {"checks", "cpu_baseline", "other_kernels", "other_workloads", "ms_per_step_no_warm_cache"} & set(out)
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert set(files) == {"y.npy", "esr_sums.npy", "loss.npy"} and sum(f.stat().st_size for f in d.iterdir()) < 64 << 20
+        y, s, loss = files["y.npy"], files["esr_sums.npy"], files["loss.npy"]
+        assert y.dtype == np.float32 and y.shape == (768, 16384) and np.isfinite(y).all() and np.abs(y).max() > 0
+        assert s.dtype == np.float64 and s.shape == (1040, 2) and loss.dtype == np.float64 and loss[1] == 1040
+        assert abs(loss[2] / s[:, 0].sum() - 1) < 1e-12 and abs(loss[3] / s[:, 1].sum() - 1) < 1e-12 and loss[0] > 0
+        dumps.append(files)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
 
 
 # ----------------------------------------------------------------------------- the fused DiffDelRNN step

@@ -354,7 +354,7 @@ def test_full_size_eight_rank_dry_run_on_one_gpu():
     arithmetic, non-zero job ESR identical in every timed step, bitwise determinism of the output; rank 0 of the weak job holds
     the one-rank job's data (stream 0 = golden g6 against the REFERENCE's output, same number in both).
     Reference counterpart: none (scripts/sbatch-train-exp1a.sh:7 runs replicas only)."""
-    common = ["--steps", "2", "--warmup", "1", "--no-extra", "--other", "off"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-extra", "--other", "off"]
     common = common + ["--cpu-sample", "small"]      # (the CPU leg's 64 x 8192 shape and second repetitions: the default line has them)
     weak = _bench(["--gpus", "8"] + common, NTM_DIST_BACKEND="gloo")
     assert weak["n_gpus"] == 8 and weak["ranks"] == 8 and weak["backend"] == "gloo" and weak["rccl_ranks"] == 0

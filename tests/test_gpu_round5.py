@@ -442,7 +442,7 @@ def test_bench_under_torch_distributed_run_two_ranks():
     env["NTM_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--batch", "1040", "--cpu-sample", "small", "--no-extra"], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "1040", "--full", "--cpu-sample", "small", "--no-extra"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line, d = bench_record(r.stdout)            # the N-rank compact line: < 4 KB, parseable, roofline + cpu_baseline on it
     assert line["n_gpus"] == 2 and line["cpu_baseline"]["value"] > 0 and line["roofline"]["aggregate"]["n_gpus"] == 2
