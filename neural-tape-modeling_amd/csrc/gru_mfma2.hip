@@ -1364,10 +1364,12 @@ __global__ __launch_bounds__(256, 1) void gru_mfma2_kernel(GruArgs a)
     }
 }
 
+static unsigned m2_grid(const GruArgs &a) { return (unsigned)((a.B + m2::SG - 1) / m2::SG); }
+
 // The dynamic-LDS attribute is per (kernel, device): set once for each and remembered (one process may drive several
 // devices; concurrent first calls at worst set it twice).  Real-time style callers issue thousands of short launches.
 template <typename K, K kernel>
-static hipError_t launch_m2(size_t smem_bytes, unsigned grid, const GruArgs &a, hipStream_t stream)
+static hipError_t launch_m2(size_t smem_bytes, const GruArgs &a, hipStream_t stream)
 {
     static std::atomic<uint64_t> configured{0};
     int dev = 0;
@@ -1379,23 +1381,36 @@ static hipError_t launch_m2(size_t smem_bytes, unsigned grid, const GruArgs &a, 
         if (e != hipSuccess) return e;
         configured.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), smem_bytes, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(m2_grid(a)), dim3(256), smem_bytes, stream, a);
     return hipGetLastError();
 }
-#define NTM2_LAUNCH(KERNEL, SMEM) launch_m2<decltype(&KERNEL), &KERNEL>(SMEM, grid, a, stream)
+#define NTM2_LAUNCH(KERNEL, SMEM) launch_m2<decltype(&KERNEL), &KERNEL>(SMEM, a, stream)
 
+// One product configuration.  More stream groups than CUs: the small-LDS build (YPN 4, 53 376 B for ENGINE 0) lets two or
+// three groups share a CU instead of running a second round of workgroups (B = 6144: 7.1 ms instead of 7.7 per 4096 steps;
+// B >= 8192: 0.76-0.80 of peak); otherwise YPN 16 (151 680 B: one workgroup per CU).  ENGINE 2 takes 2 KB more exchange buffer.
+template <int ENGINE, bool FUSE, bool ESR, bool DCP>
+static hipError_t launch_cfg(const GruArgs &a, hipStream_t stream)
+{
+    static_assert(m2::smem_floats(16, ENGINE) * sizeof(float) <= 160 * 1024, "LDS carve-up");
+    if (m2_grid(a) > (unsigned)device_cus())
+        return NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, ENGINE, 4, FUSE, ESR, DCP>), m2::smem_floats(4, ENGINE) * sizeof(float));
+    return NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, ENGINE, 16, FUSE, ESR, DCP>), m2::smem_floats(16, ENGINE) * sizeof(float));
+}
+
+// a.dd set: the DiffDelRNN step in one launch (FUSE; the carried delay buffer is moved on by delay_update_kernel,
+// aux_kernels.hip, behind it).  a.tgt set: + the per-stream ESR sums (ESR), a.dcp_out too: + the DCPreESR sums (DCP).
 hipError_t launch_gru_mfma2(const GruArgs &a, hipStream_t stream)
 {
-    constexpr size_t smem16 = m2::smem_floats(16) * sizeof(float);   // 151 680 B: one workgroup per CU
-    constexpr size_t smem4 = m2::smem_floats(4) * sizeof(float);     //  53 376 B: up to three per CU
-    static_assert(smem16 <= 160 * 1024, "LDS carve-up");
-    const unsigned grid = (unsigned)((a.B + m2::SG - 1) / m2::SG);
-    // More stream groups than CUs: the small-LDS build lets two or three groups share a CU instead of running a
-    // second round of workgroups (B = 6144: 7.1 ms instead of 7.7 per 4096 steps; B >= 8192: 0.76-0.80 of peak).
-    const bool many = grid > (unsigned)device_cus();
+    const bool fuse = a.dd != nullptr, esr = a.tgt != nullptr, dcp = esr && a.dcp_out != nullptr;
+    // the fused kernel: contiguous rows, 32-bit BYTE offsets inside a 16-row block
+    if (fuse && (!a.yd || (a.D > 0 && !a.dl_buf) || a.abl || a.dbg || a.T >= (1LL << 26) || a.ys != a.T))
+        return hipErrorInvalidValue;
+    if (esr && (!a.esr_out || (a.esr_skip & 3) || a.esr_skip < 0 || a.warmup)) return hipErrorInvalidValue;
 #ifdef NTM_LAB
     // libntm_lab.so only: the diagnostic instantiations (s_memtime stamps, timing ablations) behind
     // ntm_debug_gru_stamps / ntm_debug_gru_ablate -- never compiled into the product library
+    constexpr size_t smem16 = m2::smem_floats(16) * sizeof(float);
 #define NTM2_ABL_CASE(M) case M: return NTM2_LAUNCH((gru_mfma2_kernel<true, false, M>), smem16);
     switch (a.abl) {
         NTM2_ABL_CASE(1) NTM2_ABL_CASE(2) NTM2_ABL_CASE(4) NTM2_ABL_CASE(8) NTM2_ABL_CASE(16) NTM2_ABL_CASE(32)
@@ -1408,47 +1423,22 @@ hipError_t launch_gru_mfma2(const GruArgs &a, hipStream_t stream)
 #else
     if (a.abl || a.dbg) return hipErrorInvalidValue;      // diagnostics live in libntm_lab.so
 #endif
-    constexpr size_t smem16b = m2::smem_floats(16, 2) * sizeof(float);   // ENGINE 2: 2 KB more exchange buffer
-    constexpr size_t smem4b = m2::smem_floats(4, 2) * sizeof(float);
-    static_assert(smem16b <= 160 * 1024, "LDS carve-up");
-    if (a.tgt) {        // predict + ESR sums in one launch (exact fp32 engine)
-        if (!a.esr_out || a.engine || (a.esr_skip & 3) || a.esr_skip < 0) return hipErrorInvalidValue;
-        if (a.dcp_out)  // ... + the DCPreESR sums
-            return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 4, false, true, true>), smem4)
-                        : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 16, false, true, true>), smem16);
-        return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 4, false, true>), smem4)
-                    : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 16, false, true>), smem16);
-    }
-    if (a.engine == 2)
-        return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 2, 4>), smem4b)
-                    : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 2, 16>), smem16b);
-    if (a.engine == 1)
-        return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 1, 4>), smem4)
-                    : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 1, 16>), smem16);
-    return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 4>), smem4)
-                : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 16>), smem16);
-}
-
-// The DiffDelRNN step in one launch (exact fp32 engine).  The carried delay buffer is moved on by delay_update_kernel
-// (aux_kernels.hip) behind this launch.
-hipError_t launch_gru_mfma2_fused(const GruArgs &a, hipStream_t stream)
-{
-    constexpr size_t smem16 = m2::smem_floats(16) * sizeof(float);
-    constexpr size_t smem4 = m2::smem_floats(4) * sizeof(float);
-    if (!a.dd || !a.yd || (a.D > 0 && !a.dl_buf) || a.abl || a.dbg || a.engine) return hipErrorInvalidValue;
-    if (a.T >= (1LL << 26) || a.ys != a.T) return hipErrorInvalidValue;   // contiguous rows; 32-bit BYTE offsets inside a 16-row block
-    const unsigned grid = (unsigned)((a.B + m2::SG - 1) / m2::SG);
-    const bool many = grid > (unsigned)device_cus();
-    if (a.tgt) {        // + the ESR sums of the delayed output against a target, in the fused delay stage
-        if (!a.esr_out || (a.esr_skip & 3) || a.esr_skip < 0 || a.warmup) return hipErrorInvalidValue;
-        if (a.dcp_out)  // ... + its DCPreESR sums
-            return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 4, true, true, true>), smem4)
-                        : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 16, true, true, true>), smem16);
-        return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 4, true, true>), smem4)
-                    : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 16, true, true>), smem16);
-    }
-    return many ? NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 4, true>), smem4)
-                : NTM2_LAUNCH((gru_mfma2_kernel<true, false, 0, 0, 16, true>), smem16);
+    // the product instantiations, one per row (tools/kernel_resources.py PINNED_VGPRS keys each at both YPN): the split
+    // engines have neither the fused delay stage nor the loss sums, so those combinations find no row
+    using Launch = hipError_t (*)(const GruArgs &, hipStream_t);
+    static constexpr struct { int engine; bool fuse, esr, dcp; Launch launch; } kTable[] = {
+        {0, false, false, false, launch_cfg<0, false, false, false>},
+        {1, false, false, false, launch_cfg<1, false, false, false>},
+        {2, false, false, false, launch_cfg<2, false, false, false>},
+        {0, false, true, false, launch_cfg<0, false, true, false>},
+        {0, false, true, true, launch_cfg<0, false, true, true>},
+        {0, true, false, false, launch_cfg<0, true, false, false>},
+        {0, true, true, false, launch_cfg<0, true, true, false>},
+        {0, true, true, true, launch_cfg<0, true, true, true>},
+    };
+    for (const auto &c : kTable)
+        if (c.engine == a.engine && c.fuse == fuse && c.esr == esr && c.dcp == dcp) return c.launch(a, stream);
+    return hipErrorInvalidValue;
 }
 
 #ifdef NTM_LAB

@@ -73,123 +73,133 @@ int ntm_gru_forward_io(const float *w_ih, const float *w_hh, const float *b_ih, 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_forward_io");
 }
 
-int ntm_gru_forward_ex(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
-                       const float *b_o, int H, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
-                       int64_t y_stride_b, float *h_state, int variant, void *stream)
+// How many of B streams the matrix-pipe kernel takes under NTM_GRU_AUTO (the low-latency kernel takes the rest): none up to
+// NTM_GRU_LAT_MAX_B, otherwise all of them -- except when B is a whole number of full device rounds (16 streams x CUs) plus
+// a remainder the low-latency kernel can take: the remainder goes there instead of opening another round of workgroups
+// (B = 4112: 5.4 ms instead of 7.2 per 4096 steps)
+static int64_t mfma2_streams(int64_t B)
 {
-    if (H < 1 || H > NTM_MAX_HIDDEN) return fail(NTM_EINVAL, "ntm_gru_forward: hidden size must lie in [1, 1024]");
-    if (B < 0 || T < 0) return fail(NTM_EINVAL, "ntm_gru_forward: negative B or T");
-    if (B == 0 || T == 0) return NTM_OK;
-    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y) return fail(NTM_EINVAL, "ntm_gru_forward: null pointer");
-    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, "ntm_gru_forward: stride < T");
+    if (B <= NTM_GRU_LAT_MAX_B) return 0;
+    const int64_t round = 16 * (int64_t)ntm::device_cus();
+    const int64_t full = (B / round) * round, rem = B - full;
+    return (full > 0 && rem > 0 && rem <= NTM_GRU_LAT_MAX_B) ? full : B;
+}
+
+// the per-stream loss sums a call forms beside its output: ESR sums of y against target over [skip, T); with dcp_out also the
+// DC-pre-emphasised ones (pole R)
+struct LossSums {
+    const float *target;
+    int64_t skip;
+    double *esr_out;
+    float R;
+    double *dcp_out;
+};
+
+static int zero_sums(const LossSums &ls, int64_t B, const char *who, void *stream)      // no samples: the sums are zero
+{
+    hipError_t e = hipMemsetAsync(ls.esr_out, 0, (size_t)B * 2 * sizeof(double), (hipStream_t)stream);
+    if (e == hipSuccess && ls.dcp_out) e = hipMemsetAsync(ls.dcp_out, 0, (size_t)B * 2 * sizeof(double), (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, who);
+}
+
+// the streaming passes (one row per stream) over rows [from, B) of contiguous y and target
+static int loss_passes(const LossSums &ls, const float *y, int64_t from, int64_t B, int64_t T, const char *who, void *stream)
+{
+    const float *yr = y + from * T, *tr = ls.target + from * T;
+    hipError_t e = ntm::launch_esr(yr, tr, B - from, T, ls.skip, 1, ls.esr_out + 2 * from, (hipStream_t)stream);
+    if (e == hipSuccess && ls.dcp_out)
+        e = ntm::launch_esr_dcpre(yr, tr, B - from, T, ls.skip, ls.R, ls.dcp_out + 2 * from, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, who);
+}
+
+// ntm_gru_forward[_ex] (ls == NULL) and ntm_gru_forward_esr / _losses share this body.  Every argument is checked BEFORE
+// anything is enqueued: an NTM_EINVAL leaves y, h_state and the sums untouched.
+static int gru_impl(const char *who, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                    const float *b_o, int H, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
+                    int64_t y_stride_b, float *h_state, int variant, const LossSums *ls, void *stream)
+{
+    const std::string w(who);
+    if (H < 1 || H > NTM_MAX_HIDDEN) return fail(NTM_EINVAL, w + ": hidden size must lie in [1, 1024]");
+    if (B < 0 || T < 0) return fail(NTM_EINVAL, w + ": negative B or T");
+    if (ls && (ls->skip < 0 || ls->skip > T)) return fail(NTM_EINVAL, w + ": bad size");
+    if (ls && ls->dcp_out && !(ls->R >= 0.0f && ls->R < 1.0f)) return fail(NTM_EINVAL, w + ": R must be in [0,1)");
+    if (B == 0) return NTM_OK;
+    if (ls && (!ls->target || !ls->esr_out)) return fail(NTM_EINVAL, w + ": null pointer");
+    if (T == 0) return ls ? zero_sums(*ls, B, who, stream) : NTM_OK;
+    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y) return fail(NTM_EINVAL, w + ": null pointer");
+    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, w + ": stride < T");
+    if (ls && ls->target == y) return fail(NTM_EINVAL, w + ": target must not alias y");
     if (H != NTM_HIDDEN) {
         // every other hidden size (the reference's constructor / training defaults 8 and 16, code/model.py:22,
         // code/train.py:50, and whatever --HIDDEN_SIZE a user trained with): gru_small.hip -- 64/HP streams per wavefront at
         // the next power of two HP for H < 64, a workgroup per stream above; the matrix-pipe variants exist for H = 64 only
         if (variant != NTM_GRU_AUTO && variant != NTM_GRU_LAT && variant != NTM_GRU_VALU)
-            return fail(NTM_EINVAL, "ntm_gru_forward: the matrix-pipe kernel variants are compiled for hidden size 64 only");
-        if (H > NTM_HIDDEN && B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_gru_forward: at most 2^31 - 1 streams per call for H > 64");
-        ntm::GruArgs as{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, B, T, x_stride_b, y_stride_b, nullptr, 0, 0};
-        hipError_t es = ntm::launch_gru_small(as, H, (hipStream_t)stream);
-        return es == hipSuccess ? NTM_OK : hip_fail(es, "ntm_gru_forward");
+            return fail(NTM_EINVAL, w + ": the matrix-pipe kernel variants are compiled for hidden size 64 only");
+        if (H > NTM_HIDDEN && B > 0x7fffffff) return fail(NTM_EINVAL, w + ": at most 2^31 - 1 streams per call for H > 64");
+    } else if (variant == NTM_GRU_VALU && (reinterpret_cast<uintptr_t>(w_hh) & 15))
+        return fail(NTM_EINVAL, w + ": NTM_GRU_VALU reads W_hh with 16-byte loads; w_hh must be 16-byte aligned");
+    // streams [0, m) take the matrix-pipe kernel under AUTO; the sums of streams [0, from) ride in that launch
+    const int64_t m = (variant == NTM_GRU_AUTO && H == NTM_HIDDEN) ? mfma2_streams(B) : 0;
+    const int64_t from = (ls && (ls->skip & 3) == 0) ? m : 0;
+    if (ls && from < B && y_stride_b != T)
+        return fail(NTM_EINVAL, w + ": the streaming loss passes (streams outside the matrix-pipe launch) need contiguous y rows (stride T)");
+    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, m, T, x_stride_b, y_stride_b, nullptr, 0, 0};
+    hipError_t e = hipSuccess;
+    if (m > 0) {
+        if (from > 0) {
+            a.tgt = ls->target;
+            a.esr_out = ls->esr_out;
+            a.esr_skip = ls->skip;
+            a.dcp_out = ls->dcp_out;
+            a.dcp_R = ls->R;
+        }
+        e = ntm::launch_gru_mfma2(a, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_fail(e, who);
     }
-    if (variant == NTM_GRU_VALU && (reinterpret_cast<uintptr_t>(w_hh) & 15))
-        return fail(NTM_EINVAL, "ntm_gru_forward: NTM_GRU_VALU reads W_hh with 16-byte loads; w_hh must be 16-byte aligned");
-    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, B, T, x_stride_b, y_stride_b, nullptr, 0, 0};
-    hipError_t e;
-    if (variant == NTM_GRU_AUTO) {
-        // B <= 1024: the low-latency kernel.  Otherwise the matrix-pipe kernel; when B is a whole number of full
-        // device rounds (16 streams x CUs) plus a remainder the low-latency kernel can take, the remainder goes there
-        // instead of opening another round of workgroups (B = 4112: 5.4 ms instead of 7.2 per 4096 steps).
-        const int64_t round = 16 * (int64_t)ntm::device_cus();
-        const int64_t full = (B / round) * round, rem = B - full;
-        if (B <= NTM_GRU_LAT_MAX_B) variant = NTM_GRU_LAT;
-        else if (full > 0 && rem > 0 && rem <= NTM_GRU_LAT_MAX_B) {
-            ntm::GruArgs a0 = a, a1 = a;
-            a0.B = full;
-            a1.B = rem;
-            a1.x = x + full * x_stride_b;
-            a1.y = y + full * y_stride_b;
-            a1.h_state = h_state ? h_state + full * NTM_HIDDEN : nullptr;
-            e = ntm::launch_gru_mfma2(a0, (hipStream_t)stream);
-            if (e == hipSuccess) e = ntm::launch_gru_lat(a1, (hipStream_t)stream);
-            return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_forward");
-        } else variant = NTM_GRU_MFMA2;
+    if (m < B) {        // the rest: the kernel `variant` names (under AUTO, the low-latency kernel)
+        ntm::GruArgs r{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x + m * x_stride_b, y + m * y_stride_b, h_state ? h_state + m * H : nullptr,
+                       B - m, T, x_stride_b, y_stride_b, nullptr, 0, 0};
+        if (H != NTM_HIDDEN) e = ntm::launch_gru_small(r, H, (hipStream_t)stream);
+        else switch (variant) {
+            case NTM_GRU_AUTO: case NTM_GRU_LAT: e = ntm::launch_gru_lat(r, (hipStream_t)stream); break;
+            case NTM_GRU_MFMA2: e = ntm::launch_gru_mfma2(r, (hipStream_t)stream); break;
+            case NTM_GRU_F16X3: r.engine = 1; e = ntm::launch_gru_mfma2(r, (hipStream_t)stream); break;
+            case NTM_GRU_BF16X3: r.engine = 2; e = ntm::launch_gru_mfma2(r, (hipStream_t)stream); break;
+            case NTM_GRU_MFMA: case NTM_GRU_VALU:
+                return fail(NTM_EINVAL, w + ": laboratory kernel variant -- those live in libntm_lab.so "
+                                            "(ntm_lab_gru_forward, include/ntm_lab.h), not in the product library");
+            case NTM_GRU_MFMA3: case NTM_GRU_MFMA4:
+                return fail(NTM_EINVAL, w + ": kernel variant retired in round 6 (a measured negative result)");
+            default: return fail(NTM_EINVAL, w + ": unknown kernel variant");
+        }
+        if (e != hipSuccess) return hip_fail(e, who);
     }
-    switch (variant) {
-        case NTM_GRU_MFMA2: e = ntm::launch_gru_mfma2(a, (hipStream_t)stream); break;
-        case NTM_GRU_LAT: e = ntm::launch_gru_lat(a, (hipStream_t)stream); break;
-        case NTM_GRU_F16X3: a.engine = 1; e = ntm::launch_gru_mfma2(a, (hipStream_t)stream); break;
-        case NTM_GRU_BF16X3: a.engine = 2; e = ntm::launch_gru_mfma2(a, (hipStream_t)stream); break;
-        case NTM_GRU_MFMA: case NTM_GRU_VALU:
-            return fail(NTM_EINVAL, "ntm_gru_forward: laboratory kernel variant -- those live in libntm_lab.so "
-                                    "(ntm_lab_gru_forward, include/ntm_lab.h), not in the product library");
-        case NTM_GRU_MFMA3: case NTM_GRU_MFMA4:
-            return fail(NTM_EINVAL, "ntm_gru_forward: kernel variant retired in round 6 (a measured negative result)");
-        default: return fail(NTM_EINVAL, "ntm_gru_forward: unknown kernel variant");
-    }
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_forward");
+    return ls && from < B ? loss_passes(*ls, y, from, B, T, who, stream) : NTM_OK;
 }
 
-// ntm_gru_forward_esr (dcp_out == NULL) and ntm_gru_forward_losses share this body
-static int gru_losses_impl(const char *who, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
-                           const float *b_o, int H, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
-                           int64_t y_stride_b, float *h_state, const float *target, int64_t skip, double *esr_out, float R,
-                           double *dcp_out, void *stream)
+int ntm_gru_forward_ex(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                       const float *b_o, int H, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
+                       int64_t y_stride_b, float *h_state, int variant, void *stream)
 {
-    const std::string w(who);
-    // every argument is checked BEFORE anything is enqueued: an NTM_EINVAL leaves y, h_state and the sums untouched
-    if (H < 1 || H > NTM_MAX_HIDDEN) return fail(NTM_EINVAL, w + ": hidden size must lie in [1, 1024]");
-    if (B < 0 || T < 0 || skip < 0 || skip > T) return fail(NTM_EINVAL, w + ": bad size");
-    if (dcp_out && !(R >= 0.0f && R < 1.0f)) return fail(NTM_EINVAL, w + ": R must be in [0,1)");
-    if (B == 0) return NTM_OK;
-    if (!target || !esr_out) return fail(NTM_EINVAL, w + ": null pointer");
-    if (T == 0) {                                // no samples: the sums are zero
-        hipError_t ez = hipMemsetAsync(esr_out, 0, (size_t)B * 2 * sizeof(double), (hipStream_t)stream);
-        if (ez == hipSuccess && dcp_out) ez = hipMemsetAsync(dcp_out, 0, (size_t)B * 2 * sizeof(double), (hipStream_t)stream);
-        return ez == hipSuccess ? NTM_OK : hip_fail(ez, who);
-    }
-    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y) return fail(NTM_EINVAL, w + ": null pointer");
-    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, w + ": stride < T");
-    if (target == y) return fail(NTM_EINVAL, w + ": target must not alias y");
-    // streams the matrix-pipe kernel takes (as ntm_gru_forward's NTM_GRU_AUTO decides): there the sums ride in the launch
-    int64_t fused = 0;
-    if (H == NTM_HIDDEN && B > NTM_GRU_LAT_MAX_B && (skip & 3) == 0) {
-        const int64_t round = 16 * (int64_t)ntm::device_cus();
-        const int64_t full = (B / round) * round, rem = B - full;
-        fused = (full > 0 && rem > 0 && rem <= NTM_GRU_LAT_MAX_B) ? full : B;
-    }
-    if (fused < B && y_stride_b != T)
-        return fail(NTM_EINVAL, w + ": the streaming loss passes (streams outside the matrix-pipe launch) need contiguous y rows (stride T)");
-    if (fused > 0) {
-        ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, fused, T, x_stride_b, y_stride_b, nullptr, 0, 0};
-        a.tgt = target;
-        a.esr_out = esr_out;
-        a.esr_skip = skip;
-        a.dcp_out = dcp_out;
-        a.dcp_R = R;
-        hipError_t e = ntm::launch_gru_mfma2(a, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, who);
-    }
-    if (fused < B) {            // the rest: the forward launch the library would pick, then the streaming passes (one row per stream)
-        const int64_t r = B - fused;
-        int rc = ntm_gru_forward(w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x + fused * x_stride_b, y + fused * y_stride_b, r, T,
-                                 x_stride_b, y_stride_b, h_state ? h_state + fused * H : nullptr, stream);
-        if (rc != NTM_OK) return rc;
-        hipError_t e = ntm::launch_esr(y + fused * T, target + fused * T, r, T, skip, 1, esr_out + 2 * fused, (hipStream_t)stream);
-        if (e == hipSuccess && dcp_out)
-            e = ntm::launch_esr_dcpre(y + fused * T, target + fused * T, r, T, skip, R, dcp_out + 2 * fused, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, who);
-    }
-    return NTM_OK;
+    return gru_impl("ntm_gru_forward", w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x, y, B, T, x_stride_b, y_stride_b, h_state, variant,
+                    nullptr, stream);
+}
+
+int ntm_gru_forward(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                    const float *b_o, int H, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
+                    int64_t y_stride_b, float *h_state, void *stream)
+{
+    return gru_impl("ntm_gru_forward", w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x, y, B, T, x_stride_b, y_stride_b, h_state,
+                    NTM_GRU_AUTO, nullptr, stream);
 }
 
 int ntm_gru_forward_esr(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
                         const float *b_o, int H, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
                         int64_t y_stride_b, float *h_state, const float *target, int64_t skip, double *esr_out, void *stream)
 {
-    return gru_losses_impl("ntm_gru_forward_esr", w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x, y, B, T, x_stride_b, y_stride_b, h_state, target,
-                           skip, esr_out, 0.0f, nullptr, stream);
+    const LossSums ls{target, skip, esr_out, 0.0f, nullptr};
+    return gru_impl("ntm_gru_forward_esr", w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x, y, B, T, x_stride_b, y_stride_b, h_state,
+                    NTM_GRU_AUTO, &ls, stream);
 }
 
 int ntm_gru_forward_losses(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
@@ -199,16 +209,9 @@ int ntm_gru_forward_losses(const float *w_ih, const float *w_hh, const float *b_
 {
     if (!dcpre_out) return fail(NTM_EINVAL, "ntm_gru_forward_losses: null pointer");
     if (dcpre_out == esr_out) return fail(NTM_EINVAL, "ntm_gru_forward_losses: esr_out and dcpre_out must be distinct");
-    return gru_losses_impl("ntm_gru_forward_losses", w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x, y, B, T, x_stride_b, y_stride_b, h_state,
-                           target, skip, esr_out, dcpre_R, dcpre_out, stream);
-}
-
-int ntm_gru_forward(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
-                    const float *b_o, int H, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
-                    int64_t y_stride_b, float *h_state, void *stream)
-{
-    return ntm_gru_forward_ex(w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x, y, B, T, x_stride_b, y_stride_b, h_state,
-                              NTM_GRU_AUTO, stream);
+    const LossSums ls{target, skip, esr_out, dcpre_R, dcpre_out};
+    return gru_impl("ntm_gru_forward_losses", w_ih, w_hh, b_ih, b_hh, w_o, b_o, H, x, y, B, T, x_stride_b, y_stride_b, h_state,
+                    NTM_GRU_AUTO, &ls, stream);
 }
 
 int ntm_delay_forward(const float *x, const float *d, float *y, int64_t B, int64_t T, float *dl_state, int D,
@@ -222,16 +225,13 @@ int ntm_delay_forward(const float *x, const float *d, float *y, int64_t B, int64
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_delay_forward");
 }
 
+// ntm_diffdel_gru_forward[_ex] (ls == NULL) and ntm_diffdel_gru_forward_esr / _losses share this body
 static int diffdel_impl(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o, int H,
                         const float *x, const float *d, float *y, float *pre_d, int64_t B, int64_t T, float *h_state,
-                        float *dl_state, int D, int warmup, int32_t *err_flag, int mode, const float *target, int64_t skip,
-                        double *esr_out, void *stream, float dcp_R = 0.0f, double *dcp_out = nullptr)
+                        float *dl_state, int D, int warmup, int32_t *err_flag, int mode, const LossSums *ls, void *stream)
 {
-    // dcp_out != NULL (ntm_diffdel_gru_forward_losses): also the DC-pre-emphasised sums, beside the ESR sums wherever those are formed
-    // target != NULL: also the per-stream ESR sums of y against target over [skip, T) (ntm_diffdel_gru_forward_esr): inside the
-    // fused launch where it runs and skip is a multiple of 4, by the streaming pass (one row per stream) everywhere else
-    const bool esr_in_kernel = target && (skip & 3) == 0 && !warmup;
-    // every argument is checked BEFORE anything is enqueued: an NTM_EINVAL leaves y, pre_d, the states and esr_out untouched
+    const char *who = ls ? "ntm_diffdel_gru_forward_esr" : "ntm_diffdel_gru_forward";
+    // every argument is checked BEFORE anything is enqueued: an NTM_EINVAL leaves y, pre_d, the states and the sums untouched
     if (B < 0 || T < 0 || D < 0) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: negative size");
     if (H < 1 || H > NTM_MAX_HIDDEN) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: hidden size must lie in [1, 1024]");
     if (B == 0) return NTM_OK;
@@ -240,32 +240,23 @@ static int diffdel_impl(const float *w_ih, const float *w_hh, const float *b_ih,
         return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: unknown mode");
     if (mode == NTM_DIFFDEL_FUSED && H != NTM_HIDDEN)
         return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: the fused kernel is compiled for hidden size 64 only");
-    if (target && T == 0) {            // no samples: the sums are zero
-        hipError_t ez = hipMemsetAsync(esr_out, 0, (size_t)B * 2 * sizeof(double), (hipStream_t)stream);
-        if (ez == hipSuccess && dcp_out) ez = hipMemsetAsync(dcp_out, 0, (size_t)B * 2 * sizeof(double), (hipStream_t)stream);
-        return ez == hipSuccess ? NTM_OK : hip_fail(ez, "ntm_diffdel_gru_forward_esr");
-    }
-    // how many streams take the fused matrix-pipe kernel: all of them when forced; under AUTO the streams
-    // ntm_gru_forward would give to that kernel (B > NTM_GRU_LAT_MAX_B; a remainder of at most that many streams behind
-    // whole device rounds goes to the low-latency kernel + the streaming delay pass, as there)
-    int64_t fused = 0;
     constexpr int64_t kFusedMaxT = (int64_t)1 << 26;     // the fused kernel addresses a 16-row block with 32-bit byte offsets
-    if (mode == NTM_DIFFDEL_FUSED) {
-        if (T >= kFusedMaxT) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: the fused kernel takes T < 2^26 samples per call");
-        fused = B;
-    } else if (mode == NTM_DIFFDEL_AUTO && H == NTM_HIDDEN && B > NTM_GRU_LAT_MAX_B && T < kFusedMaxT) {
-        const int64_t round = 16 * (int64_t)ntm::device_cus();
-        const int64_t full = (B / round) * round, rem = B - full;
-        fused = (full > 0 && rem > 0 && rem <= NTM_GRU_LAT_MAX_B) ? full : B;
-    }
-    // A warm-up call (code/model.py:288-292: the delay line only moves its buffer on, y = pre_d) takes the two-pass form in
-    // every mode: the fused kernel's delay stage is idle then and reads no delays, while the reference evaluates its range
-    // assert BEFORE the warm-up branch (code/model.py:284 vs :288) -- delay_apply_kernel does, in warm-up too.
-    if (warmup) fused = 0;
+    if (mode == NTM_DIFFDEL_FUSED && T >= kFusedMaxT)
+        return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: the fused kernel takes T < 2^26 samples per call");
+    if (T == 0) return ls ? zero_sums(*ls, B, who, stream) : NTM_OK;
+    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !d || !y || (D > 0 && !dl_state))
+        return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: null pointer");
+    // how many streams take the fused matrix-pipe kernel: all of them when forced; under AUTO the streams ntm_gru_forward
+    // would give to that kernel (the rest: the low-latency kernel + the streaming delay pass, as there).  A warm-up call
+    // (code/model.py:288-292: the delay line only moves its buffer on, y = pre_d) takes the two-pass form in every mode: the
+    // fused kernel's delay stage is idle then and reads no delays, while the reference evaluates its range assert BEFORE the
+    // warm-up branch (code/model.py:284 vs :288) -- delay_apply_kernel does, in warm-up too.
+    const int64_t fused = warmup ? 0
+                        : mode == NTM_DIFFDEL_FUSED ? B
+                        : (mode == NTM_DIFFDEL_AUTO && H == NTM_HIDDEN && T < kFusedMaxT) ? mfma2_streams(B) : 0;
+    // the sums ride in the fused launch where skip is a multiple of 4; the streaming passes form them everywhere else
+    const int64_t from = (ls && (ls->skip & 3) == 0) ? fused : 0;
     if (fused > 0) {
-        if (T == 0) return NTM_OK;
-        if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !d || !y || (D > 0 && !dl_state))
-            return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: null pointer");
         if (x == y || x == pre_d || d == y || d == pre_d)
             return fail(NTM_EINVAL, "ntm_diffdel_gru_forward: outputs must not alias x or d");
         ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, nullptr, x, pre_d, h_state, fused, T, T, T, nullptr, 0, 0};
@@ -274,15 +265,14 @@ static int diffdel_impl(const float *w_ih, const float *w_hh, const float *b_ih,
         a.dl_buf = dl_state;
         a.dl_flag = err_flag;
         a.D = D;
-        a.warmup = warmup;
-        if (esr_in_kernel) {
-            a.tgt = target;
-            a.esr_out = esr_out;
-            a.esr_skip = skip;
-            a.dcp_out = dcp_out;
-            a.dcp_R = dcp_R;
+        if (from > 0) {
+            a.tgt = ls->target;
+            a.esr_out = ls->esr_out;
+            a.esr_skip = ls->skip;
+            a.dcp_out = ls->dcp_out;
+            a.dcp_R = ls->R;
         }
-        hipError_t e = ntm::launch_gru_mfma2_fused(a, (hipStream_t)stream);
+        hipError_t e = ntm::launch_gru_mfma2(a, (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "ntm_diffdel_gru_forward");
     }
     if (fused < B) {            // the streams the fused kernel did not take: GRU launch, then the streaming delay pass
@@ -293,32 +283,20 @@ static int diffdel_impl(const float *w_ih, const float *w_hh, const float *b_ih,
         int rc = ntm_gru_forward_ex(w_ih, w_hh, b_ih, b_hh, w_o, nullptr, H, x + o, pre_d + o, r, T, T, T,
                                     h_state ? h_state + fused * H : nullptr, gv, stream);
         if (rc != NTM_OK) return rc;
-        if (r <= 0 || T <= 0) return NTM_OK;
-        if (!d || !y || (D > 0 && !dl_state)) return fail(NTM_EINVAL, "ntm_delay_forward: null pointer");
         if (fused == 0) {
             rc = ntm_delay_forward(pre_d, d, y, B, T, dl_state, D, warmup, err_flag, stream);
-            if (rc != NTM_OK || !target) return rc;
-            hipError_t ee = ntm::launch_esr(y, target, B, T, skip, 1, esr_out, (hipStream_t)stream);
-            if (ee == hipSuccess && dcp_out) ee = ntm::launch_esr_dcpre(y, target, B, T, skip, dcp_R, dcp_out, (hipStream_t)stream);
-            return ee == hipSuccess ? NTM_OK : hip_fail(ee, "ntm_diffdel_gru_forward_esr");
+            if (rc != NTM_OK) return rc;
+        } else {    // mixed: interpolate the remainder here; the ONE buffer update below reads the flag both parts raise
+            hipError_t e = ntm::launch_delay_apply(pre_d + o, d + o, y + o, r, T, dl_state ? dl_state + fused * D : nullptr, D,
+                                                   warmup, err_flag, (hipStream_t)stream);
+            if (e != hipSuccess) return hip_fail(e, "ntm_diffdel_gru_forward");
         }
-        // mixed: interpolate the remainder here, then ONE buffer update over all streams (it reads the flag both parts raise)
-        hipError_t e = ntm::launch_delay_apply(pre_d + o, d + o, y + o, r, T, dl_state ? dl_state + fused * D : nullptr, D, warmup,
-                                               err_flag, (hipStream_t)stream);
+    }
+    if (fused > 0) {
+        hipError_t e = ntm::launch_delay_update(pre_d, B, T, dl_state, D, err_flag, (hipStream_t)stream);
         if (e != hipSuccess) return hip_fail(e, "ntm_diffdel_gru_forward");
     }
-    hipError_t e = ntm::launch_delay_update(pre_d, B, T, dl_state, D, err_flag, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "ntm_diffdel_gru_forward");
-    if (target) {               // the streams whose sums did not ride in the fused launch
-        const int64_t from = esr_in_kernel ? fused : 0;
-        if (from < B) {
-            e = ntm::launch_esr(y + from * T, target + from * T, B - from, T, skip, 1, esr_out + 2 * from, (hipStream_t)stream);
-            if (e == hipSuccess && dcp_out)
-                e = ntm::launch_esr_dcpre(y + from * T, target + from * T, B - from, T, skip, dcp_R, dcp_out + 2 * from, (hipStream_t)stream);
-            if (e != hipSuccess) return hip_fail(e, "ntm_diffdel_gru_forward_esr");
-        }
-    }
-    return NTM_OK;
+    return ls && from < B ? loss_passes(*ls, y, from, B, T, who, stream) : NTM_OK;
 }
 
 int ntm_diffdel_gru_forward_ex(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
@@ -326,8 +304,8 @@ int ntm_diffdel_gru_forward_ex(const float *w_ih, const float *w_hh, const float
                                int64_t B, int64_t T, float *h_state, float *dl_state, int D, int warmup,
                                int32_t *err_flag, int mode, void *stream)
 {
-    return diffdel_impl(w_ih, w_hh, b_ih, b_hh, w_o, H, x, d, y, pre_d, B, T, h_state, dl_state, D, warmup, err_flag, mode, nullptr, 0,
-                        nullptr, stream);
+    return diffdel_impl(w_ih, w_hh, b_ih, b_hh, w_o, H, x, d, y, pre_d, B, T, h_state, dl_state, D, warmup, err_flag, mode, nullptr,
+                        stream);
 }
 
 int ntm_diffdel_gru_forward_esr(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
@@ -338,8 +316,9 @@ int ntm_diffdel_gru_forward_esr(const float *w_ih, const float *w_hh, const floa
     if (!target || !esr_out) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward_esr: null pointer");
     if (skip < 0 || skip > T) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward_esr: bad skip");
     if (target == y || target == pre_d) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward_esr: target must not alias an output");
-    return diffdel_impl(w_ih, w_hh, b_ih, b_hh, w_o, H, x, d, y, pre_d, B, T, h_state, dl_state, D, 0, err_flag, NTM_DIFFDEL_AUTO, target,
-                        skip, esr_out, stream);
+    const LossSums ls{target, skip, esr_out, 0.0f, nullptr};
+    return diffdel_impl(w_ih, w_hh, b_ih, b_hh, w_o, H, x, d, y, pre_d, B, T, h_state, dl_state, D, 0, err_flag, NTM_DIFFDEL_AUTO, &ls,
+                        stream);
 }
 
 int ntm_diffdel_gru_forward_losses(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
@@ -352,8 +331,9 @@ int ntm_diffdel_gru_forward_losses(const float *w_ih, const float *w_hh, const f
     if (!(dcpre_R >= 0.0f && dcpre_R < 1.0f)) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward_losses: R must be in [0,1)");
     if (skip < 0 || skip > T) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward_losses: bad skip");
     if (target == y || target == pre_d) return fail(NTM_EINVAL, "ntm_diffdel_gru_forward_losses: target must not alias an output");
-    return diffdel_impl(w_ih, w_hh, b_ih, b_hh, w_o, H, x, d, y, pre_d, B, T, h_state, dl_state, D, 0, err_flag, NTM_DIFFDEL_AUTO, target,
-                        skip, esr_out, stream, dcpre_R, dcpre_out);
+    const LossSums ls{target, skip, esr_out, dcpre_R, dcpre_out};
+    return diffdel_impl(w_ih, w_hh, b_ih, b_hh, w_o, H, x, d, y, pre_d, B, T, h_state, dl_state, D, 0, err_flag, NTM_DIFFDEL_AUTO, &ls,
+                        stream);
 }
 
 int ntm_diffdel_gru_forward(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,

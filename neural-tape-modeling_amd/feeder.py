@@ -505,18 +505,9 @@ class SegmentFeeder:
             ev.record(side)
             return ev
 
+        model._predict_start(B)
         if is_dd:
-            model.initialize_hidden(1, model.max_delay)
-            model.warm_start()
-            if B != 1:
-                model.hidden = model.hidden.expand(1, B, model.hidden_size).contiguous()
-                model.diffdel.buffer = model.diffdel.buffer.expand(B, 1, -1).contiguous()
             deferred, model.diffdel.defer_check = model.diffdel.defer_check, True   # no host sync per chunk
-        else:
-            model.initialize_hidden()
-            model.warm_start()
-            if B != 1:
-                model.hidden = model.hidden.expand(1, B, model.hidden_size).contiguous()
         try:     # the deferred-check mode of the delay line is restored whatever the chunk loop does
             bounds = [(c0, min(L, c0 + chunk)) for c0 in range(0, L, chunk)]
             ev = send(*bounds[0])

@@ -124,53 +124,36 @@ class _GRUHead(torch.nn.Module):
             raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
         return self.hidden.to(device=device, dtype=torch.float32).clone()
 
-    def _gru(self, xbt):
-        """xbt [B,T] fp32 on HIP -> y [B,T]; carries self.hidden (code/model.py:81-82)."""
-        B, T = xbt.shape
-        _require_hip(self.GRU.weight_hh_l0, "model parameters (call .to('cuda'))")
-        h = self._hidden_for(B, xbt.device)
-        y = torch.empty_like(xbt)
-        g, o = self.GRU, self.output
-        fn, err = _lib.gru_forward_fn(self.kernel_variant, self.hidden_size)
-        rc = fn(ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(o.weight),
-                ptr(o.bias), self.hidden_size, ptr(xbt), ptr(y), B, T, T, T, ptr(h),
-                _lib.VARIANTS[self.kernel_variant], _lib.current_stream())
-        _lib.check(rc, "ntm_gru_forward", err)
-        self.hidden = h
-        return y
+    def _one_launch(self):
+        """Whether a loss entry forms its sums in the GRU's own C call (where the matrix-pipe kernel runs they ride in the
+        recurrent launch): the product "auto" variant and no skip connection (y = GRU(x) + x sits between the two)."""
+        return self.kernel_variant == "auto" and not self.skip
 
-    def _gru_esr(self, xbt, tbt, skip):
-        """xbt, tbt [B,T] fp32 on HIP -> (y [B,T], per-stream ESR sums (B,2) fp64 over samples [skip,T)) through ONE C-ABI
-        call (ntm_gru_forward_esr): where the matrix-pipe kernel runs the sums ride in the recurrent launch."""
-        B, T = xbt.shape
+    def _launch(self, x2d, y2d, tbt=None, skip=0, R=None):
+        """The GRU C call for a row-strided [B,T] fp32 input / output pair with unit stride along time; carries self.hidden
+        (code/model.py:81-82).  With a target [B,T]: + the per-stream ESR sums (B,2) fp64 over samples [skip,T)
+        (ntm_gru_forward_esr), with a pole R also the DCPreESR sums (ntm_gru_forward_losses); -> the tuple of those sums."""
+        if self.input_size != 1 or self.output_size != 1:
+            raise RuntimeError(f"input_size {self.input_size} / output_size {self.output_size}: the one-call entry points run the "
+                               "single-channel kernels; use forward() plus the loss functions (esr_sums, esr_dcpre_sums)")
+        B, T = x2d.shape
         _require_hip(self.GRU.weight_hh_l0, "model parameters (call .to('cuda'))")
-        h = self._hidden_for(B, xbt.device)
-        y = torch.empty_like(xbt)
-        sums = torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
-        g, o = self.GRU, self.output
-        rc = _lib.lib().ntm_gru_forward_esr(ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0),
-                                            ptr(o.weight), ptr(o.bias), self.hidden_size, ptr(xbt), ptr(y), B, T, T, T, ptr(h),
-                                            ptr(tbt), int(skip), ptr(sums), _lib.current_stream())
-        _lib.check(rc, "ntm_gru_forward_esr")
+        h = self._hidden_for(B, x2d.device)
+        g, o, L = self.GRU, self.output, _lib.lib()
+        args = (ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(o.weight), ptr(o.bias),
+                self.hidden_size, ptr(x2d), ptr(y2d), B, T, max(x2d.stride(0), T), max(y2d.stride(0), T), ptr(h))
+        sums = tuple(torch.empty(B, 2, device=x2d.device, dtype=torch.float64)
+                     for _ in range(0 if tbt is None else 1 if R is None else 2))
+        if tbt is None:
+            fn, err = _lib.gru_forward_fn(self.kernel_variant, self.hidden_size)
+            _lib.check(fn(*args, _lib.VARIANTS[self.kernel_variant], _lib.current_stream()), "ntm_gru_forward", err)
+        elif R is None:
+            _lib.check(L.ntm_gru_forward_esr(*args, ptr(tbt), int(skip), ptr(sums[0]), _lib.current_stream()), "ntm_gru_forward_esr")
+        else:
+            _lib.check(L.ntm_gru_forward_losses(*args, ptr(tbt), int(skip), ptr(sums[0]), float(R), ptr(sums[1]),
+                                                _lib.current_stream()), "ntm_gru_forward_losses")
         self.hidden = h
-        return y, sums
-
-    def _gru_losses(self, xbt, tbt, skip, R):
-        """As _gru_esr, plus the DC-pre-emphasised sums (B,2) fp64, through ONE C-ABI call (ntm_gru_forward_losses): where the
-        matrix-pipe kernel runs BOTH pairs of sums ride in the recurrent launch."""
-        B, T = xbt.shape
-        _require_hip(self.GRU.weight_hh_l0, "model parameters (call .to('cuda'))")
-        h = self._hidden_for(B, xbt.device)
-        y = torch.empty_like(xbt)
-        sums = torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
-        dsums = torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
-        g, o = self.GRU, self.output
-        rc = _lib.lib().ntm_gru_forward_losses(ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0),
-                                               ptr(o.weight), ptr(o.bias), self.hidden_size, ptr(xbt), ptr(y), B, T, T, T, ptr(h),
-                                               ptr(tbt), int(skip), ptr(sums), float(R), ptr(dsums), _lib.current_stream())
-        _lib.check(rc, "ntm_gru_forward_losses")
-        self.hidden = h
-        return y, sums, dsums
+        return sums
 
     @torch.no_grad()
     def forward_into(self, x2d, y2d):
@@ -183,15 +166,7 @@ class _GRUHead(torch.nn.Module):
                 raise RuntimeError(f"forward_into: {what} must be a 2-D float32 view with unit stride along time")
         if x2d.shape != y2d.shape:
             raise RuntimeError("forward_into: shape mismatch")
-        B, T = x2d.shape
-        h = self._hidden_for(B, x2d.device)
-        g, o = self.GRU, self.output
-        fn, err = _lib.gru_forward_fn(self.kernel_variant, self.hidden_size)
-        rc = fn(ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(o.weight),
-                ptr(o.bias), self.hidden_size, ptr(x2d), ptr(y2d), B, T, max(x2d.stride(0), T), max(y2d.stride(0), T), ptr(h),
-                _lib.VARIANTS[self.kernel_variant], _lib.current_stream())
-        _lib.check(rc, "ntm_gru_forward", err)
-        self.hidden = h
+        self._launch(x2d, y2d)
         if self.skip:
             y2d += x2d
 
@@ -268,7 +243,8 @@ class RNN(_GRUHead):
         if self._general_io:
             return self._forward_io(x)
         xbt = _as_bt(x, "RNN.forward")
-        y = self._gru(xbt)
+        y = torch.empty_like(xbt)
+        self._launch(xbt, y)
         if self.skip:
             y += xbt
         return y.view(xbt.shape[0], 1, xbt.shape[1])
@@ -279,25 +255,7 @@ class RNN(_GRUHead):
         by the ESR entry of the loss loop (code/test-model.py:346, :386-388) -- in one call: (y (N,1,T), sums (N,2) fp64 =
         [sum (t-y)^2, sum t^2]), the same numbers as `esr_sums(self(x), target, skip)` up to fp64 summation order.  With
         `kernel_variant == "auto"` and no skip connection it is ONE launch where the matrix-pipe kernel runs."""
-        xbt = _as_bt(x, "RNN.forward_esr")
-        tbt = _as_bt(target, "RNN.forward_esr")
-        if tbt.shape != xbt.shape:
-            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs target {tuple(target.shape)}")
-        if self.kernel_variant != "auto" or self.skip:
-            y = self.forward(x)
-            return y, esr_sums(y, target, skip)
-        y, sums = self._gru_esr(xbt, tbt, skip)
-        return y.view(xbt.shape[0], 1, xbt.shape[1]), sums
-
-    @torch.no_grad()
-    def predict_esr(self, input, target, skip=0):
-        """predict(input) + the ESR sums against `target` over [skip, T): initialize_hidden, warm_start, forward_esr."""
-        B = input.shape[0]
-        self.initialize_hidden()
-        self.warm_start()
-        if B != 1:
-            self.hidden = self.hidden.expand(1, B, self.hidden_size).contiguous()
-        return self.forward_esr(input, target, skip)
+        return self._forward_sums("RNN.forward_esr", x, target, skip, None)
 
     @torch.no_grad()
     def forward_losses(self, x, target, skip=0, R=None):
@@ -307,35 +265,47 @@ class RNN(_GRUHead):
         signals): the numbers of `esr_sums` / `esr_dcpre_sums` on `self(x)` (ESR up to fp64 summation order, DCPreESR up to
         the fp32 evaluation order of the one-pole filter, ~1e-6 relative).  With `kernel_variant == "auto"` and no skip
         connection it is ONE launch where the matrix-pipe kernel runs."""
-        R = DC_PRE_R if R is None else R
-        xbt = _as_bt(x, "RNN.forward_losses")
-        tbt = _as_bt(target, "RNN.forward_losses")
+        return self._forward_sums("RNN.forward_losses", x, target, skip, DC_PRE_R if R is None else R)
+
+    def _forward_sums(self, what, x, target, skip, R):
+        """forward_losses; R None: without the DCPreESR sums (forward_esr)."""
+        xbt = _as_bt(x, what)
+        tbt = _as_bt(target, what)
         if tbt.shape != xbt.shape:
             raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs target {tuple(target.shape)}")
-        if self.kernel_variant != "auto" or self.skip:
-            y = self.forward(x)
-            return y, esr_sums(y, target, skip), esr_dcpre_sums(y, target, skip, R)
-        y, sums, dsums = self._gru_losses(xbt, tbt, skip, R)
-        return y.view(xbt.shape[0], 1, xbt.shape[1]), sums, dsums
+        y = torch.empty_like(xbt)
+        y3 = y.view(xbt.shape[0], 1, xbt.shape[1])
+        if self._one_launch():
+            return (y3,) + self._launch(xbt, y, tbt, skip, R)
+        self._launch(xbt, y)
+        if self.skip:
+            y += xbt
+        return (y3, esr_sums(y3, target, skip)) + (() if R is None else (esr_dcpre_sums(y3, target, skip, R),))
 
-    @torch.no_grad()
-    def predict_losses(self, input, target, skip=0, R=None):
-        """predict(input) + the ESR and DCPreESR sums against `target` over [skip, T)."""
-        B = input.shape[0]
+    def _predict_start(self, B):
+        """The prologue of every predict: initialize_hidden, warm_start, the warm state broadcast to B streams."""
         self.initialize_hidden()
         self.warm_start()
         if B != 1:
             self.hidden = self.hidden.expand(1, B, self.hidden_size).contiguous()
+
+    @torch.no_grad()
+    def predict_esr(self, input, target, skip=0):
+        """predict(input) + the ESR sums against `target` over [skip, T): initialize_hidden, warm_start, forward_esr."""
+        self._predict_start(input.shape[0])
+        return self.forward_esr(input, target, skip)
+
+    @torch.no_grad()
+    def predict_losses(self, input, target, skip=0, R=None):
+        """predict(input) + the ESR and DCPreESR sums against `target` over [skip, T)."""
+        self._predict_start(input.shape[0])
         return self.forward_losses(input, target, skip, R)
 
     @torch.no_grad()
     def predict(self, input, segment_length=None):
         """initialize_hidden + warm_start + forward over the sequence (code/model.py:218-246)."""
-        B, T = input.shape[0], input.shape[-1]
-        self.initialize_hidden()
-        self.warm_start()
-        if B != 1:
-            self.hidden = self.hidden.expand(1, B, self.hidden_size).contiguous()
+        T = input.shape[-1]
+        self._predict_start(input.shape[0])
         if segment_length is None:
             return self.forward(input)
         output = torch.empty(input.shape, device=input.device, dtype=torch.float32)
@@ -503,6 +473,11 @@ class DiffDelRNN(_GRUHead):
     # (`kernel_variant` other than "auto") and `skip=True` (pre_d = GRU(x) + x sits between the two) take the two calls.
     delay_mode = "auto"
 
+    def _one_launch(self, losses=True):
+        """Whether a call takes the one-C-call step: forward() unless `delay_mode` is "two_pass", the loss entries (whose
+        C entry points run the "auto" mode) only under "auto"."""
+        return super()._one_launch() and (self.delay_mode == "auto" if losses else self.delay_mode != "two_pass")
+
     @torch.no_grad()
     def forward(self, x, del_traj, warmup=False, _events=None):
         """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424).  `_events`: three torch.cuda.Event objects
@@ -513,12 +488,13 @@ class DiffDelRNN(_GRUHead):
         if dbt.shape != xbt.shape:
             raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
         B, T = xbt.shape
-        if self.kernel_variant == "auto" and not self.skip and self.delay_mode != "two_pass":
+        if self._one_launch(losses=False):
             y, pre = self._fused_step(xbt, dbt, warmup, _events)
             return y.view(B, 1, T), pre.view(B, 1, T)
         if _events:
             _events[0].record()
-        pre = self._gru(xbt)
+        pre = torch.empty_like(xbt)
+        self._launch(xbt, pre)
         if self.skip:
             pre += xbt
         if _events:
@@ -534,17 +510,7 @@ class DiffDelRNN(_GRUHead):
         (`model(input, d_traj)` followed by the ESR entry of the loss loop, code/test-model.py:353, :386-388) in one call:
         (y, pre_d, sums (N,2) fp64).  ONE launch where the fused step runs (`delay_mode` / `kernel_variant` "auto", no skip
         connection): the sums are accumulated in the fused delay stage; otherwise forward() + esr_sums()."""
-        xbt = _as_bt(x, "DiffDelRNN.forward_esr")
-        dbt = _as_bt(del_traj, "DiffDelRNN.forward_esr")
-        tbt = _as_bt(target, "DiffDelRNN.forward_esr")
-        if dbt.shape != xbt.shape or tbt.shape != xbt.shape:
-            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)} vs target {tuple(target.shape)}")
-        if self.kernel_variant != "auto" or self.skip or self.delay_mode != "auto":
-            y, pre = self.forward(x, del_traj)
-            return y, pre, esr_sums(y, target, skip)
-        B, T = xbt.shape
-        y, pre, sums = self._fused_step(xbt, dbt, False, None, tbt, int(skip))
-        return y.view(B, 1, T), pre.view(B, 1, T), sums
+        return self._forward_sums("DiffDelRNN.forward_esr", x, del_traj, target, skip, None)
 
     @torch.no_grad()
     def forward_losses(self, x, del_traj, target, skip=0, R=None):
@@ -552,26 +518,34 @@ class DiffDelRNN(_GRUHead):
         samples [skip, T) (code/test-model.py:250-252,353,386-388) in one call: (y, pre_d, ESR sums (N,2) fp64, DCPreESR sums
         (N,2) fp64).  ONE launch where the fused step runs (`delay_mode` / `kernel_variant` "auto", no skip connection); otherwise
         forward() + the two streaming passes."""
-        R = DC_PRE_R if R is None else R
-        xbt = _as_bt(x, "DiffDelRNN.forward_losses")
-        dbt = _as_bt(del_traj, "DiffDelRNN.forward_losses")
-        tbt = _as_bt(target, "DiffDelRNN.forward_losses")
+        return self._forward_sums("DiffDelRNN.forward_losses", x, del_traj, target, skip, DC_PRE_R if R is None else R)
+
+    def _forward_sums(self, what, x, del_traj, target, skip, R):
+        """forward_losses; R None: without the DCPreESR sums (forward_esr)."""
+        xbt = _as_bt(x, what)
+        dbt = _as_bt(del_traj, what)
+        tbt = _as_bt(target, what)
         if dbt.shape != xbt.shape or tbt.shape != xbt.shape:
             raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)} vs target {tuple(target.shape)}")
-        if self.kernel_variant != "auto" or self.skip or self.delay_mode != "auto":
+        if not self._one_launch():
             y, pre = self.forward(x, del_traj)
-            return y, pre, esr_sums(y, target, skip), esr_dcpre_sums(y, target, skip, R)
+            return (y, pre, esr_sums(y, target, skip)) + (() if R is None else (esr_dcpre_sums(y, target, skip, R),))
         B, T = xbt.shape
-        y, pre, (sums, dsums) = self._fused_step(xbt, dbt, False, None, tbt, int(skip), R)
-        return y.view(B, 1, T), pre.view(B, 1, T), sums, dsums
+        y, pre, *sums = self._fused_step(xbt, dbt, False, None, tbt, int(skip), R)
+        return (y.view(B, 1, T), pre.view(B, 1, T), *sums)
 
-    def _predict_with(self, fn, input):
-        B = input.shape[0]
+    def _predict_start(self, B):
+        """The prologue of every predict: initialize_hidden, warm_start, the warm state and delay buffer broadcast to B streams."""
         self.initialize_hidden(1, self.max_delay)
         self.warm_start()
         if B != 1:
             self.hidden = self.hidden.expand(1, B, self.hidden_size).contiguous()
             self.diffdel.buffer = self.diffdel.buffer.expand(B, 1, -1).contiguous()
+
+    def _predict_with(self, fn, input):
+        """_predict_start, then fn() with the delay-range assert of code/model.py:284 evaluated ONCE, after the last launch
+        has been enqueued (no host synchronisation per chunk)."""
+        self._predict_start(input.shape[0])
         deferred, self.diffdel.defer_check = self.diffdel.defer_check, True
         try:
             out = fn()
@@ -594,7 +568,7 @@ class DiffDelRNN(_GRUHead):
     def _fused_step(self, xbt, dbt, warmup, _events=None, tbt=None, skip=0, dcp_R=None):
         """One C-ABI call for GRU + head + delay line (ntm_diffdel_gru_forward_ex); carries self.hidden and the delay
         buffer exactly as the two calls do.  With a target: + the ESR sums (ntm_diffdel_gru_forward_esr), with `dcp_R` also
-        the DCPreESR sums (ntm_diffdel_gru_forward_losses) of the delayed output."""
+        the DCPreESR sums (ntm_diffdel_gru_forward_losses) of the delayed output.  -> (y, pre_d, *sums)."""
         B, T = xbt.shape
         dl = self.diffdel
         D = int(dl.max_delay)
@@ -607,30 +581,22 @@ class DiffDelRNN(_GRUHead):
             dl._err = torch.zeros(1, device=xbt.device, dtype=torch.int32)
         h = self._hidden_for(B, xbt.device)
         y, pre = torch.empty_like(xbt), torch.empty_like(xbt)
+        sums = tuple(torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
+                     for _ in range(0 if tbt is None else 1 if dcp_R is None else 2))
         dl._fresh = False
-        g = self.GRU
+        g, L = self.GRU, _lib.lib()
+        args = (ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(self.output.weight),
+                self.hidden_size, ptr(xbt), ptr(dbt), ptr(y), ptr(pre), B, T, ptr(h), ptr(dl.buffer), D)
         if _events:
             _events[0].record()
-        sums = None
         if tbt is None:
-            rc = _lib.lib().ntm_diffdel_gru_forward_ex(
-                ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(self.output.weight),
-                self.hidden_size, ptr(xbt), ptr(dbt), ptr(y), ptr(pre), B, T, ptr(h), ptr(dl.buffer), D, int(bool(warmup)),
-                ptr(dl._err), _lib.DIFFDEL_MODES[self.delay_mode], _lib.current_stream())
-        elif dcp_R is not None:
-            sums = torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
-            dsums = torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
-            rc = _lib.lib().ntm_diffdel_gru_forward_losses(
-                ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(self.output.weight),
-                self.hidden_size, ptr(xbt), ptr(dbt), ptr(y), ptr(pre), B, T, ptr(h), ptr(dl.buffer), D, ptr(dl._err),
-                ptr(tbt), int(skip), ptr(sums), float(dcp_R), ptr(dsums), _lib.current_stream())
-            sums = (sums, dsums)
+            rc = L.ntm_diffdel_gru_forward_ex(*args, int(bool(warmup)), ptr(dl._err), _lib.DIFFDEL_MODES[self.delay_mode],
+                                              _lib.current_stream())
+        elif dcp_R is None:
+            rc = L.ntm_diffdel_gru_forward_esr(*args, ptr(dl._err), ptr(tbt), int(skip), ptr(sums[0]), _lib.current_stream())
         else:
-            sums = torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
-            rc = _lib.lib().ntm_diffdel_gru_forward_esr(
-                ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(self.output.weight),
-                self.hidden_size, ptr(xbt), ptr(dbt), ptr(y), ptr(pre), B, T, ptr(h), ptr(dl.buffer), D, ptr(dl._err),
-                ptr(tbt), int(skip), ptr(sums), _lib.current_stream())
+            rc = L.ntm_diffdel_gru_forward_losses(*args, ptr(dl._err), ptr(tbt), int(skip), ptr(sums[0]), float(dcp_R), ptr(sums[1]),
+                                                  _lib.current_stream())
         _lib.check(rc, "ntm_diffdel_gru_forward")
         if _events:
             _events[1].record()
@@ -640,34 +606,23 @@ class DiffDelRNN(_GRUHead):
             dl.raise_if_violated()
         else:
             dl._unchecked = True
-        return (y, pre) if tbt is None else (y, pre, sums)
+        return (y, pre) + sums
 
     @torch.no_grad()
     def predict(self, input, d_traj, segment_length=None, _events=None):
         """initialize_hidden + warm_start + forward (code/model.py:618-653); any batch size.  The delay-range assert
         of code/model.py:284 is evaluated ONCE, after the last chunk has been enqueued (no host synchronisation
         per chunk)."""
-        B, T = input.shape[0], input.shape[-1]
-        self.initialize_hidden(1, self.max_delay)
-        self.warm_start()
-        if B != 1:
-            self.hidden = self.hidden.expand(1, B, self.hidden_size).contiguous()
-            self.diffdel.buffer = self.diffdel.buffer.expand(B, 1, -1).contiguous()
-        deferred, self.diffdel.defer_check = self.diffdel.defer_check, True
-        try:
+        def run():
             if segment_length is None:
-                output, output_pre_d = self.forward(input, d_traj, _events=_events)
-            else:
-                output = torch.empty(input.shape, device=input.device, dtype=torch.float32)
-                output_pre_d = torch.empty(input.shape, device=input.device, dtype=torch.float32)
-                for i in range(int(np.ceil(T / segment_length))):
-                    sl = slice(i * segment_length, (i + 1) * segment_length)
-                    output[:, :, sl], output_pre_d[:, :, sl] = self.forward(input[:, :, sl], d_traj[:, :, sl])
-        finally:
-            self.diffdel.defer_check = deferred
-        if not deferred:
-            self.diffdel.raise_if_violated()
-        return output, output_pre_d
+                return self.forward(input, d_traj, _events=_events)
+            output = torch.empty(input.shape, device=input.device, dtype=torch.float32)
+            output_pre_d = torch.empty(input.shape, device=input.device, dtype=torch.float32)
+            for i in range(int(np.ceil(input.shape[-1] / segment_length))):
+                sl = slice(i * segment_length, (i + 1) * segment_length)
+                output[:, :, sl], output_pre_d[:, :, sl] = self.forward(input[:, :, sl], d_traj[:, :, sl])
+            return output, output_pre_d
+        return self._predict_with(run, input)
 
     @torch.no_grad()
     def validate(self, dataloader, loss_fcn, store_examples=True):

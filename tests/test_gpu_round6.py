@@ -166,6 +166,16 @@ def test_g22_general_input_and_output_sizes_against_the_reference(ntm, name):
     if I != 1:
         with pytest.raises(RuntimeError, match="Expected %d, got 1" % I):
             m.predict(x)
+    # the one-call entry points run the single-channel kernels: they refuse other sizes (they used to read row 0 of w_o and
+    # return a (B, 1, T) result); predict_* with input_size != 1 raise in warm_start() already, as predict() does
+    x1 = x[:, :1]
+    for call in (lambda: m.forward_esr(x1, x1), lambda: m.forward_losses(x1, x1, 4),
+                 lambda: m.forward_into(x1[:, 0], torch.empty_like(x1[:, 0]))):
+        with pytest.raises(RuntimeError, match=r"use forward\(\) plus the loss functions"):
+            call()
+    for call in (lambda: m.predict_esr(x1, x1), lambda: m.predict_losses(x1, x1)):
+        with pytest.raises(RuntimeError, match=r"use forward\(\) plus the loss functions" if I == 1 else "Expected %d, got 1" % I):
+            call()
 
 
 @pytest.mark.gpu
