@@ -352,6 +352,60 @@ int ntm_tcn_forward(const float *params, int L, int C, int K, const int *dil, co
 int64_t ntm_tcn_scratch_floats(int64_t B, int64_t T, int C);
 int64_t ntm_tcn_chunk_streams(int64_t B, int64_t T, int C);
 
+/*
+ * ---- Training of GRU-HS[64] (input_size = output_size = 1, no skip, exact fp32): what RNN.train_epoch of
+ * code/model.py:90-161 needs, run by code/train.py:181-267 with --HIDDEN_SIZE 64 and --LOSS ESR | DCPreESR.  These entry
+ * points were added without changing any existing one, so NTM_ABI_VERSION stays 9 (a caller of the version-9 ABI sees no
+ * difference).  GRU as torch.nn.GRU defines it (code/model.py:44-45,80-82), with gh_n = W_hn h_{t-1} + b_hn.
+ */
+#define NTM_TRAIN_SAVED 5             /* saved floats per step and unit: h_{t-1}, r, z, n, gh_n                          */
+#define NTM_TRAIN_GRAD_FLOATS 12929   /* w_ih 192 | w_hh 12288 | b_ih 192 | b_hh 192 | w_o 64 | b_o 1                    */
+
+/* Floats of the workspace ntm_gru_train_forward fills for B streams of T samples: B * T * NTM_TRAIN_SAVED * 64. */
+int64_t ntm_gru_train_workspace_floats(int64_t B, int64_t T);
+
+/*
+ * The forward of one TBPTT window with its activations saved (the `pred_mini = self.forward(input_mini)` of
+ * code/model.py:133-134 and the warm-up forward of :122, both under autograd): ntm_gru_forward_ex with NTM_GRU_LAT for
+ * H = 64, input / output size 1 -- y and h_state come out bit-identical to it -- plus, for every step t and unit u,
+ * ws[((b*T + t)*5 + j)*64 + u] = h_{t-1}, r, z, n, gh_n (j = 0..4; contiguous, ntm_gru_train_workspace_floats(B, T)).
+ * h_state [B,64] in / out (null: zero initial state, final state not written).  b_o may be null.
+ */
+int ntm_gru_train_forward(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                          const float *b_o, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
+                          int64_t y_stride_b, float *h_state, float *ws, void *stream);
+
+/*
+ * Backward through time of that window (the `loss.backward()` of code/model.py:140), one workgroup per stream, t = T-1 .. 0.
+ * dy [B,T] (row stride dy_stride_b; null = zeros) is dL/dy, dh_T [B,64] the gradient of the final hidden state (null =
+ * zeros; it chains a window to the one after it), ws the workspace of the forward.  Out: dh0 [B,64] (the gradient of the
+ * initial state; may be null) and part [B, NTM_TRAIN_GRAD_FLOATS], every stream's own parameter gradients.
+ */
+int ntm_gru_train_backward(const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b, const float *ws,
+                           const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t B, int64_t T, float *dh0,
+                           float *part, void *stream);
+
+/* grad[NTM_TRAIN_GRAD_FLOATS] = the B rows of part added in stream order (fp64 accumulation, no atomics: bit-reproducible). */
+int ntm_gru_train_reduce(const float *part, int64_t B, float *grad, void *stream);
+
+/*
+ * Adjoint of the ESRLoss of code/train.py:176 on the whole [B,T] tensor (contiguous):
+ *     dy = gout[0] * 2 (y - t) / (n (S_t / n + eps)),   n = B T,
+ * sums2 = the whole-batch [S_e, S_t] (fp64, device: the stream rows of ntm_esr_sums added up), gout the upstream gradient
+ * (one float, device), eps = 1e-5 (CoreAudioML).
+ */
+int ntm_esr_grad(const float *y, const float *t, int64_t B, int64_t T, const double *sums2, const float *gout, double eps,
+                 float *dy, void *stream);
+
+/*
+ * Adjoint of the DCPreESR(dc_pre=True) loss of code/train.py:174 (the sums of ntm_esr_dcpre_sums with skip 0): with
+ * e_f = H(y - t), H(z) = (1 - z^-1)/(1 - R z^-1) from zero state, and v = gout[0] * 2 e_f / (n (S_tf / n + eps)),
+ * dy = H^T v -- the anti-causal one-pole q[t] = v[t] + R q[t+1] followed by dy[t] = q[t] - q[t+1].  sums2 = the whole-batch
+ * [S_ef, S_tf] of ntm_esr_dcpre_sums.
+ */
+int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2, const float *gout,
+                       double eps, float *dy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,15 @@ _SIGNATURES = {
     "ntm_tcn_scratch_floats": (_i64, [_i64, _i64, _int]),
     "ntm_tcn_chunk_streams": (_i64, [_i64, _i64, _int]),
     "ntm_loss_scalars": (_int, [_vp, _i64, _i64, ctypes.c_double, _vp, _vp]),
+    # training of GRU-HS[64] (additions within ABI version 9)
+    "ntm_gru_train_workspace_floats": (_i64, [_i64, _i64]),
+    "ntm_gru_train_forward": (_int, [_vp] * 8 + [_i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "ntm_gru_train_backward": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "ntm_gru_train_reduce": (_int, [_vp, _i64, _vp, _vp]),
+    "ntm_esr_grad": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "ntm_esr_dcpre_grad": (_int, [_vp, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, ctypes.c_double, _vp, _vp]),
 }
+TRAIN_GRAD_FLOATS = 12929   # include/ntm.h NTM_TRAIN_GRAD_FLOATS: w_ih | w_hh | b_ih | b_hh | w_o | b_o of GRU(1, 64) + Linear(64, 1)
 
 # include/ntm_lab.h: libntm_lab.so (older / experimental GRU kernels, diagnostic builds) -- tests and tools only
 _LAB_SIGNATURES = {

@@ -1,0 +1,414 @@
+// Training kernels for GRU-HS[64] (input_size = output_size = 1, no skip, exact fp32): what RNN.train_epoch needs
+// (code/model.py:90-161) -- the forward with its activations saved, the backward through time (BPTT), the deterministic
+// reduction of the per-stream gradients, and the adjoints of the ESR / DCPreESR losses (code/train.py:173-176).
+//
+// GRU as torch defines it, with gh_n = W_hn h_{t-1} + b_hn:
+//   r, z = sigma(.),  n = tanh(W_in x + b_in + r o gh_n),  h_t = n + z o (h_{t-1} - n),  y_t = w_o . h_t + b_o.
+//
+// Workspace of the forward (and input of the backward): ws[s][t][j][u], j = 0..4 = h_{t-1}, r, z, n, gh_n (unscaled), fp32.
+// Per-stream gradient partials: part[s][NTM_TRAIN_GRAD_FLOATS] in the order w_ih | w_hh | b_ih | b_hh | w_o | b_o (12929).
+#include "ntm_common.h"
+
+#include <type_traits>
+
+namespace ntm {
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+namespace {
+
+constexpr int LT = 256;                  // samples per x / y tile (as gru_lat.hip)
+constexpr float LOG2E = 1.44269504088896340736f;
+constexpr int NSAVE = 5;                 // h_{t-1}, r, z, n, gh_n
+constexpr int OFF_WHH = 3 * kH, OFF_BIH = OFF_WHH + 3 * kH * kH, OFF_BHH = OFF_BIH + 3 * kH, OFF_WO = OFF_BHH + 3 * kH,
+              OFF_BO = OFF_WO + kH, NGRAD = OFF_BO + 1;
+static_assert(NGRAD == 12929, "w_ih + w_hh + b_ih + b_hh + w_o + b_o of GRU(1, 64) + Linear(64, 1)");
+
+// A workgroup barrier that orders LDS only: global stores and loads in flight (the flush of the forward's saves, the
+// backward's prefetch) are not drained by it, as they would be by the vmcnt(0) of a full __syncthreads().
+__device__ __forceinline__ void lds_barrier()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_shift_add(float v)
+{
+    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false);
+    return v + __builtin_bit_cast(float, moved);
+}
+
+// gru_lat.hip's head sum (same shifts, same order): total in lane 63
+__device__ __forceinline__ float wave_sum_lane63(float v)
+{
+    v = dpp_shift_add<0x111, 0xf>(v);
+    v = dpp_shift_add<0x112, 0xf>(v);
+    v = dpp_shift_add<0x114, 0xf>(v);
+    v = dpp_shift_add<0x118, 0xf>(v);
+    v = dpp_shift_add<0x142, 0xa>(v);
+    v = dpp_shift_add<0x143, 0xc>(v);
+    return v;
+}
+
+template <int PERM>
+__device__ __forceinline__ float quad_add(float v)
+{
+    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), PERM, 0xf, 0xf, true);
+    return v + __builtin_bit_cast(float, o);
+}
+
+// (a) Forward with saved activations: the step of gru_lat_kernel<true> (gru_lat.hip) operation for operation -- same lane
+// layout (wave w < 4, lane 4 ul + kq: K quarter kq of unit 16 w + ul), same summation order, same v_exp_f32 / v_rcp_f32 gate
+// forms, the head on a fifth wave -- so y and the final h are bit-identical to kernel_variant "lat" for every B (the head's
+// arithmetic does not depend on which wave evaluates it).  In addition lane kq of each quad writes one of the saved values of
+// its unit per step (kq = 0 also gh_n) to an LDS stage of SC steps, which the whole workgroup flushes to the workspace with
+// coalesced 16-byte stores after every SC steps.  (Stored straight from the step, each global store made the compiler wait
+// for its completion before the step's registers were reused: a store round trip inside the recurrence, every step.  The
+// flush's stores are waited for the same way, in the first step after the flush: one round trip per SC steps.)
+constexpr int SC = 32;                   // steps per LDS stage of the saves (divides the tile, 40 KB)
+
+__global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__restrict__ ws)
+{
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) float stg[SC * NSAVE * kH];   // saves of steps c0 .. c0 + SC - 1: [step][j][u]
+    __shared__ __attribute__((aligned(16))) float hb[2][kH];
+    __shared__ float xt[2][LT];
+    __shared__ float yt[2][LT];
+
+    const int tid = threadIdx.x, l = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ul = l >> 2, kq = l & 3;
+    const bool head_wave = w == 4;
+    const int u = 16 * (w & 3) + ul;
+    const int64_t s = blockIdx.x;
+    const int64_t T = a.T;
+    const float *xs = a.x + s * a.xs;
+    float *ys = a.y + s * a.ys;
+    float *const stg_l = stg + kq * kH + u;                              // this lane's save slot in the stage's step 0
+
+    constexpr float SRZ = -LOG2E, SN = 2.0f * LOG2E;
+    constexpr float INV_SN = 1.0f / SN;
+    f32x2 Wr[8], Wz[8], Wn[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float *pr = a.w_hh + (size_t)(0 * kH + u) * kH + 16 * kq + 2 * k;
+        const float *pz = a.w_hh + (size_t)(1 * kH + u) * kH + 16 * kq + 2 * k;
+        const float *pn = a.w_hh + (size_t)(2 * kH + u) * kH + 16 * kq + 2 * k;
+        Wr[k] = (f32x2){pr[0] * SRZ, pr[1] * SRZ};
+        Wz[k] = (f32x2){pz[0] * SRZ, pz[1] * SRZ};
+        Wn[k] = (f32x2){pn[0] * SN, pn[1] * SN};
+    }
+    const float wir = a.w_ih[u] * SRZ, wiz = a.w_ih[kH + u] * SRZ, win = a.w_ih[2 * kH + u] * SN;
+    const float br = (a.b_ih[u] + a.b_hh[u]) * SRZ, bz = (a.b_ih[kH + u] + a.b_hh[kH + u]) * SRZ;
+    const float bin_ = a.b_ih[2 * kH + u] * SN, bhn = a.b_hh[2 * kH + u] * SN;
+    const float bo = a.b_o ? a.b_o[0] : 0.0f;
+    const float wo_l = a.w_o[l];
+    float hold = a.h_state ? a.h_state[s * kH + u] : 0.0f;
+
+    if (kq == 0 && !head_wave) hb[0][u] = hold;
+    if (tid < LT && tid < T) xt[0][tid] = xs[tid];
+    __syncthreads();
+
+    const float *const hq_rd = &hb[0][16 * kq];
+    float *const hu_wr = &hb[0][u];
+    auto step = [&](const int ph, const int tb, const int64_t t, auto par_c) {
+        constexpr int par = decltype(par_c)::value;
+        if (head_wave) {
+            const float yv = wave_sum_lane63(wo_l * hb[par][l]) + bo;
+            if (l == 63) { if (ph > 0) yt[tb][ph - 1] = yv; else yt[tb ^ 1][LT - 1] = yv; }
+            lds_barrier();
+            return;
+        }
+        const f32x4 h0 = *(const f32x4 *)(hq_rd + par * kH + 0), h1 = *(const f32x4 *)(hq_rd + par * kH + 4);
+        const f32x4 h2 = *(const f32x4 *)(hq_rd + par * kH + 8), h3 = *(const f32x4 *)(hq_rd + par * kH + 12);
+        const float x = xt[tb][ph];
+        const f32x2 hq[8] = {{h0[0], h0[1]}, {h0[2], h0[3]}, {h1[0], h1[1]}, {h1[2], h1[3]},
+                             {h2[0], h2[1]}, {h2[2], h2[3]}, {h3[0], h3[1]}, {h3[2], h3[3]}};
+        f32x2 ar0 = Wr[0] * hq[0], ar1 = Wr[1] * hq[1], az0 = Wz[0] * hq[0], az1 = Wz[1] * hq[1];
+        f32x2 an0 = Wn[0] * hq[0], an1 = Wn[1] * hq[1];
+#pragma unroll
+        for (int k = 2; k < 8; k += 2) {
+            ar0 = __builtin_elementwise_fma(Wr[k], hq[k], ar0); ar1 = __builtin_elementwise_fma(Wr[k + 1], hq[k + 1], ar1);
+            az0 = __builtin_elementwise_fma(Wz[k], hq[k], az0); az1 = __builtin_elementwise_fma(Wz[k + 1], hq[k + 1], az1);
+            an0 = __builtin_elementwise_fma(Wn[k], hq[k], an0); an1 = __builtin_elementwise_fma(Wn[k + 1], hq[k + 1], an1);
+        }
+        const f32x2 sr = ar0 + ar1, sz = az0 + az1, sn = an0 + an1;
+        const float qr = quad_add<0x4E>(quad_add<0xB1>(sr[0] + sr[1]));
+        const float qz = quad_add<0x4E>(quad_add<0xB1>(sz[0] + sz[1]));
+        const float qn = quad_add<0x4E>(quad_add<0xB1>(sn[0] + sn[1]));
+        const float cr = __builtin_fmaf(wir, x, br), cz = __builtin_fmaf(wiz, x, bz), gi = __builtin_fmaf(win, x, bin_);
+        const float pr_ = cr + qr, pz_ = cz + qz, gh = bhn + qn;
+        const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pr_));
+        const float z = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pz_));
+        const float en = __builtin_amdgcn_exp2f(__builtin_fmaf(r, gh, gi));
+        const float n = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + en), 1.0f);
+        // saves of step t: lane kq writes row kq (h_{t-1}, r, z, n), lane 0 of the quad also row 4 (gh_n, unscaled)
+        float *wt = stg_l + (int)(t & (SC - 1)) * (NSAVE * kH);
+        wt[0] = kq == 0 ? hold : kq == 1 ? r : kq == 2 ? z : n;
+        if (kq == 0) wt[(NSAVE - 1) * kH] = gh * INV_SN;
+        hold = __builtin_fmaf(z, hold - n, n);
+        hu_wr[(par ^ 1) * kH] = hold;
+        lds_barrier();
+    };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    auto run = [&](int p0, const int p1, const int tb, const int64_t tile0) {
+        if (p0 < p1 && (p0 & 1)) { step(p0, tb, tile0 + p0, P1{}); ++p0; }
+        for (; p0 + 1 < p1; p0 += 2) { step(p0, tb, tile0 + p0, P0{}); step(p0 + 1, tb, tile0 + p0 + 1, P1{}); }
+        if (p0 < p1) step(p0, tb, tile0 + p0, P0{});
+    };
+
+    for (int64_t tile0 = 0; tile0 < T; tile0 += LT) {
+        const int ns = (int)((T - tile0) < LT ? (T - tile0) : LT);
+        const int tb = (int)((tile0 >> 8) & 1);
+        for (int c0 = 0; c0 < ns; c0 += SC) {
+            const int c1 = ns < c0 + SC ? ns : c0 + SC;
+            if (c0 == 0) {
+                run(0, c1 < 3 ? c1 : 3, tb, tile0);
+                if (ns > 2 && tile0 >= LT && tid < LT) ys[tile0 - LT + tid] = yt[tb ^ 1][tid];      // previous y tile is complete
+                run(c1 < 3 ? c1 : 3, c1, tb, tile0);
+            } else {
+                // the next x tile into its buffer (read from step 0 of the next tile on), loaded and written here: a load kept in
+                // flight in a register across the steps (as gru_lat.hip does) made the compiler wait for it at every copy of that
+                // register inside the step loop, i.e. in every step of the tile's second half
+                if (c0 == 128 && tid < LT) {
+                    const int64_t nx = tile0 + LT + tid;
+                    xt[tb ^ 1][tid] = nx < T ? xs[nx] : 0.0f;
+                }
+                run(c0, c1, tb, tile0);
+            }
+            // flush the stage: steps [c0, c1) are one contiguous run of the stream's workspace (the last step's barrier has
+            // ordered every write to it); the barrier behind orders these reads before the next stage's writes
+            const int nf = (c1 - c0) * (NSAVE * kH);
+            float *dst = ws + (s * T + tile0 + c0) * (NSAVE * kH);
+            for (int i = 4 * tid; i < nf; i += 4 * 320) *(f32x4 *)(dst + i) = *(const f32x4 *)(stg + i);
+            lds_barrier();
+        }
+    }
+    if (T > 0 && head_wave) {
+        const float yv = wave_sum_lane63(wo_l * hb[(int)(T & 1)][l]) + bo;
+        if (l == 63) yt[(int)(((T - 1) >> 8) & 1)][(int)((T - 1) & (LT - 1))] = yv;
+    }
+    __syncthreads();
+    const int64_t last0 = ((T - 1) >> 8) * LT;
+    if (T > 0 && tid < LT) {
+        if (last0 + tid < T) ys[last0 + tid] = yt[(last0 >> 8) & 1][tid];
+        if (last0 >= LT && (T - 1 - last0) < 2) ys[last0 - LT + tid] = yt[((last0 >> 8) & 1) ^ 1][tid];
+    }
+    if (a.h_state && kq == 0 && !head_wave) a.h_state[s * kH + u] = hold;
+}
+
+// (b) Backward through time, one workgroup (4 waves) per stream, t = T-1 down to 0: the transpose of the forward's layout.
+// Lane l = 4 kl + uq of wave w owns column k = 16 w + kl of W_hh and the output-unit quarter uq: it holds
+// W_hh[g][16 uq + i][k] (g = r, z, n; i < 16: 48 registers) and accumulates the same 48 entries of dW_hh.  Per step:
+//   * each quad evaluates the elementwise adjoints of unit k redundantly from the saved h_{t-1}, r, z, n, gh_n and
+//     g = dh_t + w_o dy_t;  lane uq = 0 publishes a_r, a_z, a_nh of unit k to LDS (double-buffered by step parity);
+//   * behind ONE barrier each lane reads the 48 adjoints of its quarter (12 broadcast ds_read_b128), does 48 FMAs for
+//     W_hh^T a and 48 for dW_hh += a h_{t-1}[k], and a DPP quad sum gives dh_{t-1}[k] = g z + W_hr^T a_r + W_hz^T a_z + W_hn^T a_nh.
+// The saved values of step t - PF are loaded while step t runs (a register ring, PF steps deep), so the global latency sits
+// behind the recurrence; the barrier orders LDS only and does not drain them.
+constexpr int PF = 4;
+
+__global__ __launch_bounds__(256) void gru_train_bwd_kernel(const float *__restrict__ w_hh, const float *__restrict__ w_o,
+                                                             const float *__restrict__ x, int64_t xs, const float *__restrict__ ws,
+                                                             const float *__restrict__ dy, int64_t dys,
+                                                             const float *__restrict__ dh_T, int64_t T, float *__restrict__ dh0,
+                                                             float *__restrict__ part)
+{
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) float ab[2][3][kH];       // a_r, a_z, a_nh of the step, by step parity
+
+    const int tid = threadIdx.x, l = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kl = l >> 2, uq = l & 3;
+    const int k = 16 * w + kl;
+    const int64_t s = blockIdx.x;
+    const float *xs_ = x + s * xs;
+    const float *dys_ = dy ? dy + s * dys : nullptr;
+    const float *wsk = ws + s * T * (NSAVE * kH) + k;
+
+    float W[3][16], dW[3][16];
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            W[g][i] = w_hh[(size_t)(g * kH + 16 * uq + i) * kH + k];
+            dW[g][i] = 0.0f;
+        }
+    const float wo = w_o[k];
+    float dh = dh_T ? dh_T[s * kH + k] : 0.0f;
+    // the per-unit sums over time (one of each per quad) in fp64: b_o's gradient alone is the sum of all T values of dy
+    double dwir = 0.0, dwiz = 0.0, dwin = 0.0, dbr = 0.0, dbz = 0.0, dbin = 0.0, dbhn = 0.0, dwo = 0.0, dbo = 0.0;
+
+    // the ring: slot j holds step values of t = (T - 1 - j) mod PF positions; indices below 0 are clamped (never consumed)
+    float rh[PF], rr[PF], rz[PF], rn[PF], rg[PF], rx[PF], rd[PF];
+    auto fetch = [&](const int j, int64_t t) {
+        t = t < 0 ? 0 : t;
+        const float *p = wsk + t * (NSAVE * kH);
+        rh[j] = p[0 * kH]; rr[j] = p[1 * kH]; rz[j] = p[2 * kH]; rn[j] = p[3 * kH]; rg[j] = p[4 * kH];
+        rx[j] = xs_[t];
+        rd[j] = dys_ ? dys_[t] : 0.0f;
+    };
+    if (T > 0) {
+#pragma unroll
+        for (int j = 0; j < PF; ++j) fetch(j, T - 1 - j);
+    }
+
+    const float *const aq = &ab[0][0][16 * uq];
+    auto step = [&](const int j, const int64_t t, auto par_c) {
+        constexpr int par = decltype(par_c)::value;
+        const float hp = rh[j], r = rr[j], z = rz[j], n = rn[j], ghn = rg[j], xv = rx[j], dyv = rd[j];
+        fetch(j, t - PF);
+        const float g = __builtin_fmaf(wo, dyv, dh);
+        const float dn = g * (1.0f - z), dz = g * (hp - n);
+        const float an = dn * (1.0f - n * n);
+        const float az = dz * (z * (1.0f - z));
+        const float ar = (an * ghn) * (r * (1.0f - r));
+        const float anh = an * r;
+        const float ht = __builtin_fmaf(z, hp - n, n);                  // h_t exactly as the forward formed it
+        dwir += (double)ar * xv; dwiz += (double)az * xv; dwin += (double)an * xv;
+        dbr += ar; dbz += az; dbin += an; dbhn += anh;
+        dwo += (double)dyv * ht; dbo += dyv;
+        if (uq == 0) { ab[par][0][k] = ar; ab[par][1][k] = az; ab[par][2][k] = anh; }
+        lds_barrier();
+        float p0 = 0.0f, p1 = 0.0f;
+#pragma unroll
+        for (int gg = 0; gg < 3; ++gg)
+#pragma unroll
+            for (int i = 0; i < 16; i += 4) {
+                const f32x4 av = *(const f32x4 *)(aq + par * 3 * kH + gg * kH + i);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (e & 1) p1 = __builtin_fmaf(W[gg][i + e], av[e], p1);
+                    else p0 = __builtin_fmaf(W[gg][i + e], av[e], p0);
+                    dW[gg][i + e] = __builtin_fmaf(av[e], hp, dW[gg][i + e]);
+                }
+            }
+        const float q = quad_add<0x4E>(quad_add<0xB1>(p0 + p1));
+        dh = __builtin_fmaf(g, z, q);
+    };
+    using P0 = std::integral_constant<int, 0>;
+    using P1 = std::integral_constant<int, 1>;
+    // steps in groups of PF (the ring slot and the LDS parity known at compile time: PF is even)
+    int64_t t = T - 1;
+    for (; t - (PF - 1) >= 0; t -= PF) {
+        step(0, t, P0{}); step(1, t - 1, P1{}); step(2, t - 2, P0{}); step(3, t - 3, P1{});
+    }
+    if (t >= 0) step(0, t, P0{});
+    if (t >= 1) step(1, t - 1, P1{});
+    if (t >= 2) step(2, t - 2, P0{});
+
+    float *ps = part + s * NGRAD;
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) ps[OFF_WHH + (g * kH + 16 * uq + i) * kH + k] = dW[g][i];
+    if (uq == 0) {
+        ps[0 * kH + k] = (float)dwir; ps[1 * kH + k] = (float)dwiz; ps[2 * kH + k] = (float)dwin;
+        ps[OFF_BIH + 0 * kH + k] = (float)dbr; ps[OFF_BIH + 1 * kH + k] = (float)dbz; ps[OFF_BIH + 2 * kH + k] = (float)dbin;
+        ps[OFF_BHH + 0 * kH + k] = (float)dbr; ps[OFF_BHH + 1 * kH + k] = (float)dbz; ps[OFF_BHH + 2 * kH + k] = (float)dbhn;
+        ps[OFF_WO + k] = (float)dwo;
+        if (dh0) dh0[s * kH + k] = dh;
+    }
+    if (tid == 0) ps[OFF_BO] = (float)dbo;
+}
+
+// (c) The parameter gradients: the B per-stream partials of every entry added in stream order, in fp64 (no atomics).
+__global__ __launch_bounds__(256) void gru_train_reduce_kernel(const float *__restrict__ part, int64_t B, float *__restrict__ grad)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= NGRAD) return;
+    double acc = 0.0;
+    for (int64_t b = 0; b < B; ++b) acc += (double)part[b * NGRAD + e];
+    grad[e] = (float)acc;
+}
+
+// (d) Loss adjoints.  ESR (code/train.py:176): L = (S_e / n) / (S_t / n + eps) with whole-batch sums S (sums2 = [S_e, S_t],
+// fp64, from ntm_esr_sums) -> dL/dy = 2 (y - t) / (n (S_t / n + eps)), times the upstream gradient gout[0].
+__global__ __launch_bounds__(256) void esr_grad_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t N,
+                                                       const double *__restrict__ sums2, const float *__restrict__ gout, double eps,
+                                                       float *__restrict__ dy)
+{
+    const double n = (double)N;
+    const double c = (double)gout[0] * 2.0 / (n * (sums2[1] / n + eps));
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
+        dy[i] = (float)(c * ((double)y[i] - (double)t[i]));
+}
+
+// DCPreESR (code/train.py:174): the same on the DC-blocked signals, f = (1 - z^-1)/(1 - R z^-1) from zero state.  With
+// e_f = f(y - t) and v = 2 e_f / (n (S_tf / n + eps)), dL/dy = f^T v: the anti-causal one-pole q[t] = v[t] + R q[t+1] followed
+// by the adjoint first difference dy[t] = q[t] - q[t+1].  One thread per stream, fp64 recursions; e_f is parked in dy between
+// the causal and the anti-causal pass.
+__global__ __launch_bounds__(64) void esr_dcpre_grad_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t B,
+                                                            int64_t T, float R, const double *__restrict__ sums2,
+                                                            const float *__restrict__ gout, double eps, float *__restrict__ dy)
+{
+    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float *yb = y + b * T, *tb = t + b * T;
+    float *db = dy + b * T;
+    const double Rd = (double)R;
+    double prev = 0.0, ef = 0.0;
+#pragma unroll 8
+    for (int64_t i = 0; i < T; ++i) {
+        const double wv = (double)yb[i] - (double)tb[i];
+        ef = (wv - prev) + Rd * ef;
+        prev = wv;
+        db[i] = (float)ef;
+    }
+    const double n = (double)(B * T);
+    const double c = (double)gout[0] * 2.0 / (n * (sums2[1] / n + eps));
+    double q1 = 0.0;                               // q[t + 1]
+#pragma unroll 8
+    for (int64_t i = T - 1; i >= 0; --i) {
+        const double q = c * (double)db[i] + Rd * q1;
+        db[i] = (float)(q - q1);
+        q1 = q;
+    }
+}
+
+}   // namespace
+
+int64_t train_grad_floats() { return NGRAD; }
+
+hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, hipStream_t stream)
+{
+    if (a.B == 0) return hipSuccess;
+    hipLaunchKernelGGL(gru_train_fwd_kernel, dim3((unsigned)a.B), dim3(320), 0, stream, a, ws);
+    return hipGetLastError();
+}
+
+hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float *x, int64_t xs, const float *ws, const float *dy,
+                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, hipStream_t stream)
+{
+    if (B == 0) return hipSuccess;
+    hipLaunchKernelGGL(gru_train_bwd_kernel, dim3((unsigned)B), dim3(256), 0, stream, w_hh, w_o, x, xs, ws, dy, dys, dh_T, T, dh0, part);
+    return hipGetLastError();
+}
+
+hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream)
+{
+    hipLaunchKernelGGL(gru_train_reduce_kernel, dim3((NGRAD + 255) / 256), dim3(256), 0, stream, part, B, grad);
+    return hipGetLastError();
+}
+
+hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const double *sums2, const float *gout, double eps, float *dy,
+                           hipStream_t stream)
+{
+    if (N == 0) return hipSuccess;
+    const int64_t blocks = (N + 255) / 256 < 4096 ? (N + 255) / 256 : 4096;
+    hipLaunchKernelGGL(esr_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, y, t, N, sums2, gout, eps, dy);
+    return hipGetLastError();
+}
+
+hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2,
+                                 const float *gout, double eps, float *dy, hipStream_t stream)
+{
+    if (B == 0 || T == 0) return hipSuccess;
+    hipLaunchKernelGGL(esr_dcpre_grad_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, y, t, B, T, R, sums2, gout, eps, dy);
+    return hipGetLastError();
+}
+
+}   // namespace ntm

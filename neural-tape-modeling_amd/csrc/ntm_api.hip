@@ -34,6 +34,15 @@ hipError_t launch_resample_fir(const double *x, double *y, int64_t B, int64_t N,
 hipError_t launch_fir_f64(const double *x, double *y, int64_t B, int64_t N, const double *h, int taps, int clamp, hipStream_t stream);
 hipError_t launch_tcn(const float *params, int L, int C, int K, const int *dil, const float *x, float *y, int64_t B,
                       int64_t T, float *scratch, hipStream_t stream);
+int64_t train_grad_floats();
+hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, hipStream_t stream);
+hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float *x, int64_t xs, const float *ws, const float *dy,
+                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, hipStream_t stream);
+hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream);
+hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const double *sums2, const float *gout, double eps, float *dy,
+                           hipStream_t stream);
+hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2,
+                                 const float *gout, double eps, float *dy, hipStream_t stream);
 }  // namespace ntm
 
 namespace {
@@ -610,6 +619,73 @@ int ntm_tcn_forward(const float *params, int L, int C, int K, const int *dil, co
         if (hipEventRecord(P.done[i], P.lane[i]) == hipSuccess) (void)hipStreamWaitEvent(user, P.done[i], 0);
     }
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_tcn_forward");
+}
+
+// ---- training of GRU-HS[64] (csrc/gru_train.hip)
+int64_t ntm_gru_train_workspace_floats(int64_t B, int64_t T)
+{
+    return (B < 0 || T < 0) ? 0 : B * T * NTM_TRAIN_SAVED * NTM_HIDDEN;
+}
+
+int ntm_gru_train_forward(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                          const float *b_o, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
+                          int64_t y_stride_b, float *h_state, float *ws, void *stream)
+{
+    static_assert(NTM_TRAIN_SAVED * NTM_HIDDEN == 5 * ntm::kH, "workspace layout");
+    if (B < 0 || T < 0) return fail(NTM_EINVAL, "ntm_gru_train_forward: negative B or T");
+    if (B == 0 || T == 0) return NTM_OK;
+    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y || !ws) return fail(NTM_EINVAL, "ntm_gru_train_forward: null pointer");
+    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, "ntm_gru_train_forward: row stride below T");
+    if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_gru_train_forward: at most 2^31 - 1 streams per call");
+    if (x == y) return fail(NTM_EINVAL, "ntm_gru_train_forward: y must not alias x");
+    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, B, T, x_stride_b, y_stride_b, nullptr, 0, 0};
+    hipError_t e = ntm::launch_gru_train_fwd(a, ws, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_forward");
+}
+
+int ntm_gru_train_backward(const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b, const float *ws,
+                           const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t B, int64_t T, float *dh0,
+                           float *part, void *stream)
+{
+    if (B < 0 || T < 0) return fail(NTM_EINVAL, "ntm_gru_train_backward: negative B or T");
+    if (B == 0) return NTM_OK;
+    if (!w_hh || !w_o || !part || (T > 0 && (!x || !ws))) return fail(NTM_EINVAL, "ntm_gru_train_backward: null pointer");
+    if (x_stride_b < T || (dy && dy_stride_b < T)) return fail(NTM_EINVAL, "ntm_gru_train_backward: row stride below T");
+    if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_gru_train_backward: at most 2^31 - 1 streams per call");
+    static_assert(NTM_TRAIN_GRAD_FLOATS == 12929, "parameter count of GRU(1, 64) + Linear(64, 1)");
+    if (ntm::train_grad_floats() != NTM_TRAIN_GRAD_FLOATS) return fail(NTM_EINVAL, "ntm_gru_train_backward: layout mismatch");
+    hipError_t e = ntm::launch_gru_train_bwd(w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, B, T, dh0, part, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_backward");
+}
+
+int ntm_gru_train_reduce(const float *part, int64_t B, float *grad, void *stream)
+{
+    if (B < 0) return fail(NTM_EINVAL, "ntm_gru_train_reduce: negative B");
+    if (!grad || (B > 0 && !part)) return fail(NTM_EINVAL, "ntm_gru_train_reduce: null pointer");
+    hipError_t e = ntm::launch_gru_train_reduce(part, B, grad, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_reduce");
+}
+
+int ntm_esr_grad(const float *y, const float *t, int64_t B, int64_t T, const double *sums2, const float *gout, double eps,
+                 float *dy, void *stream)
+{
+    if (B < 0 || T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_grad: bad size or eps");
+    if (B == 0 || T == 0) return NTM_OK;
+    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_grad: null pointer");
+    hipError_t e = ntm::launch_esr_grad(y, t, B * T, sums2, gout, eps, dy, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_grad");
+}
+
+int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2, const float *gout,
+                       double eps, float *dy, void *stream)
+{
+    if (B < 0 || T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: bad size or eps");
+    if (!(R >= 0.0f && R < 1.0f)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: R must be in [0,1)");
+    if (B == 0 || T == 0) return NTM_OK;
+    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: null pointer");
+    if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: at most 2^31 - 1 streams per call");
+    hipError_t e = ntm::launch_esr_dcpre_grad(y, t, B, T, R, sums2, gout, eps, dy, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_dcpre_grad");
 }
 
 }  // extern "C"

@@ -13,8 +13,11 @@ Deliberate differences from the reference (documented in DESIGN.md):
   * predict() runs the whole sequence in one persistent launch; `segment_length=2048` reproduces
     the reference's chunk loop (same result, state is carried either way).
   * validate() (code/model.py:163-216, :513-616 -- the reference's own batched, inference-only use of forward,
-    called by code/train.py:242) and detach_hidden / detach_buffer are here; train_epoch (backward) is out of
-    scope.
+    called by code/train.py:242) and detach_hidden / detach_buffer are here.  RNN.train_epoch (code/model.py:90-161) trains
+    GRU-HS[64] with input_size = output_size = 1 and no skip connection on the kernels of csrc/gru_train.hip (training.py);
+    parameters are created with requires_grad=False and train_epoch turns it on.  forward() builds a graph only when grad
+    mode is on AND a parameter requires grad; every other call is the inference path, unchanged.  DiffDelRNN training is
+    not implemented: its forward refuses grad-requiring parameters.
   * warm_start() from a fresh state is a pure function of the parameters.  With `warm_cache = True` its result (hidden
     state; for the DiffDelGRU also the delay buffer) is computed by the kernel ONCE per (parameter storage + torch version
     counter, device, kernel variant, delay-line length) and kept, so a predict() is one launch instead of two -- same numbers
@@ -28,7 +31,7 @@ Deliberate differences from the reference (documented in DESIGN.md):
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, training
 from ._lib import ptr
 
 
@@ -233,13 +236,46 @@ class RNN(_GRUHead):
             self._warm = (key, self.hidden.clone())
 
     def detach_hidden(self):
-        """Detach the hidden state from the computational graph (code/model.py:54-56): a clone here, there is no graph."""
+        """Detach the hidden state from the computational graph (code/model.py:54-56)."""
         self.hidden = self.hidden.clone().detach()
 
-    @torch.no_grad()
+    def _check_trainable(self, what):
+        """The configuration the training kernels cover (csrc/gru_train.hip), else a RuntimeError that names it."""
+        if self.hidden_size != training.HIDDEN or self._general_io or self.skip:
+            raise RuntimeError(f"{what}: training runs for {training.SUPPORTED} only; this model is RNN(input_size="
+                               f"{self.input_size}, hidden_size={self.hidden_size}, output_size={self.output_size}, skip={self.skip})")
+        _require_hip(self.GRU.weight_hh_l0, what)
+
     def forward(self, x):
         """x (N_BATCHES, N_CHANNELS = input_size, N_SAMPLES) -> y (N_BATCHES, output_size, N_SAMPLES); stateful
-        (code/model.py:67-88).  input_size = output_size = 1 (every shipped checkpoint and caller) runs the kernels of DESIGN.md 0."""
+        (code/model.py:67-88).  input_size = output_size = 1 (every shipped checkpoint and caller) runs the kernels of DESIGN.md 0.
+        With grad mode on and a parameter that requires grad (RNN.train_epoch) the call is a node of the autograd graph
+        (training.GRUTrainStep: the low-latency kernel's step with its activations saved, same y bits) and self.hidden
+        becomes its differentiable final state; otherwise nothing is recorded and the output does not require grad."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._forward_train(x)
+        with torch.no_grad():
+            return self._forward_infer(x)
+
+    def _forward_train(self, x):
+        self._check_trainable("RNN.forward")
+        if x.requires_grad:
+            raise RuntimeError("RNN.forward: the input requires grad; the training kernels give gradients for the parameters "
+                               "and the hidden state only (no caller of the reference needs d/dx)")
+        xbt = _as_bt(x, "RNN.forward")
+        B, T = xbt.shape
+        if self.hidden is None:
+            h0 = torch.zeros(B, self.hidden_size, device=xbt.device, dtype=torch.float32)
+        elif tuple(self.hidden.shape) != (1, B, self.hidden_size):
+            raise RuntimeError(f"Expected hidden size (1, {B}, {self.hidden_size}), got {list(self.hidden.shape)}")
+        else:
+            h0 = self.hidden.reshape(B, self.hidden_size)
+        g, o = self.GRU, self.output
+        y, h = training.GRUTrainStep.apply(xbt, h0, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, o.weight, o.bias)
+        self.hidden = h.view(1, B, self.hidden_size)
+        return y.view(B, 1, T)
+
+    def _forward_infer(self, x):
         if self._general_io:
             return self._forward_io(x)
         xbt = _as_bt(x, "RNN.forward")
@@ -313,6 +349,58 @@ class RNN(_GRUHead):
             sl = slice(i * segment_length, (i + 1) * segment_length)
             output[:, :, sl] = self.forward(input[:, :, sl])
         return output
+
+    def train_epoch(self, dataloader, loss_fcn, optimizer):
+        """One epoch of truncated back-propagation through time (code/model.py:90-161, run by code/train.py): per batch the
+        hidden state is reset, aggregated on the first 1024 samples, then every whole window of 1024 samples is predicted,
+        scored with `loss_fcn(pred, target)`, back-propagated and followed by `optimizer.step()`; returns the mean over batches
+        of the mean window loss.  As in the reference the warm-up forward runs with grad enabled and is not detached, so the
+        first window's backward reaches through it (2048 samples); detach_hidden cuts the graph after every window.
+        `dataloader`: any iterable of batches whose first two items are input and target (B, C, T) -- `(x, t, meta)` as the
+        reference's DataLoader gives, or SegmentFeeder.batches; only channel 0 is used.  `loss_fcn`: ESRLoss / DCPreESR (or
+        any function of (pred, target) that is differentiable through torch); `optimizer`: any torch.optim optimizer over
+        model.parameters().
+        Supported: RNN(1, 64, 1, skip=False) on a HIP device (RuntimeError otherwise).  On entry it sets requires_grad on the
+        GRU and head parameters (they are created without it, so that inference never records a graph)."""
+        TBPTT_INIT = 2**10
+        TBPTT_LEN = 2**10
+        self._check_trainable("RNN.train_epoch")
+        for p in self.parameters():
+            p.requires_grad_(True)
+        device = self.GRU.weight_hh_l0.device
+        self.train()
+
+        num_batches = 0             # counted, so that a generator (SegmentFeeder.batches) serves as well as a DataLoader
+        epoch_loss = 0
+        for _, batch in enumerate(dataloader):
+            input, target = batch[0], batch[1]
+            if input.shape[1] > 1:  # only the audio channel counts for training
+                input, target = input[:, :1, :], target[:, :1, :]
+            input, target = input.to(device), target.to(device)
+
+            self.initialize_hidden()
+            num_minibatches = (input.shape[2] - TBPTT_INIT) // TBPTT_LEN
+            _ = self.forward(input[:, :, :TBPTT_INIT])          # a graph node: window 1's backward reaches it
+            self.zero_grad()
+
+            minibatch_loss = 0
+            sample_offset = TBPTT_INIT
+            for _ in range(num_minibatches):
+                input_mini = input[:, :, sample_offset:sample_offset + TBPTT_LEN]
+                target_mini = target[:, :, sample_offset:sample_offset + TBPTT_LEN]
+                pred_mini = self.forward(input_mini)
+                loss = loss_fcn(pred_mini, target_mini)
+                loss.backward()
+                optimizer.step()
+                self.detach_hidden()
+                self.zero_grad()
+                minibatch_loss += loss.item()
+                sample_offset += TBPTT_LEN
+            minibatch_loss /= num_minibatches      # ZeroDivisionError for T < 2048, as in the reference
+            epoch_loss += minibatch_loss
+            num_batches += 1
+        epoch_loss /= num_batches
+        return epoch_loss
 
     @torch.no_grad()
     def validate(self, dataloader, loss_fcn, store_examples=True):
@@ -478,8 +566,16 @@ class DiffDelRNN(_GRUHead):
         C entry points run the "auto" mode) only under "auto"."""
         return super()._one_launch() and (self.delay_mode == "auto" if losses else self.delay_mode != "two_pass")
 
-    @torch.no_grad()
     def forward(self, x, del_traj, warmup=False, _events=None):
+        """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424); inference only -- with grad mode on and a parameter that
+        requires grad it raises (DiffDelRNN training needs the delay line's adjoint, which is not implemented)."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError(f"DiffDelRNN.forward: parameters require grad, but DiffDelRNN training is not implemented; training "
+                               f"runs for {training.SUPPORTED} only")
+        with torch.no_grad():
+            return self._forward_infer(x, del_traj, warmup, _events)
+
+    def _forward_infer(self, x, del_traj, warmup=False, _events=None):
         """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424).  `_events`: three torch.cuda.Event objects
         recorded before the GRU launch, between it and the delay pass, and after (bench.py's per-kernel timing; with the
         fused step the middle one is recorded right behind the fused launch, ahead of the buffer update)."""
@@ -698,13 +794,20 @@ def esr_per_segment(output, target, skip=0):
     return (s[:, 0] / n) / (s[:, 1] / n + ESR_EPS)
 
 
+def _esr_value(output, target):
+    s = esr_sums(output, target).sum(dim=0)
+    n = output.numel()
+    return ((s[0] / n) / (s[1] / n + ESR_EPS)).float(), s
+
+
 class ESRLoss(torch.nn.Module):
-    """ESR of a whole (B,1,T) tensor, as `loss_fcn(output, target)` in code/test-model.py:386-388."""
+    """ESR of a whole (B,1,T) tensor, as `loss_fcn(output, target)` in code/test-model.py:386-388.  With an output that
+    requires grad (RNN.train_epoch, code/train.py:176) the same value as a differentiable scalar (adjoint: ntm_esr_grad)."""
 
     def forward(self, output, target):
-        s = esr_sums(output, target).sum(dim=0)
-        n = output.numel()
-        return ((s[0] / n) / (s[1] / n + ESR_EPS)).float()
+        if output.requires_grad and torch.is_grad_enabled():
+            return training.loss_with_grad(output, target, _esr_value, None)
+        return _esr_value(output, target)[0]
 
 
 DC_PRE_R = 0.995
@@ -730,10 +833,17 @@ class DCPreESR(torch.nn.Module):
         super().__init__()
         self.dc_pre, self.R = dc_pre, R
 
-    def forward(self, output, target):
+    def _value(self, output, target):
         s = (esr_dcpre_sums(output, target, 0, self.R) if self.dc_pre else esr_sums(output, target)).sum(dim=0)
         n = output.numel()
-        return ((s[0] / n) / (s[1] / n + ESR_EPS)).float()
+        return ((s[0] / n) / (s[1] / n + ESR_EPS)).float(), s
+
+    def forward(self, output, target):
+        """With an output that requires grad (RNN.train_epoch, code/train.py:174) the same value as a differentiable scalar
+        (adjoint: ntm_esr_dcpre_grad, or ntm_esr_grad with dc_pre=False)."""
+        if output.requires_grad and torch.is_grad_enabled():
+            return training.loss_with_grad(output, target, self._value, self.R if self.dc_pre else None)
+        return self._value(output, target)[0]
 
 
 MRSTFT_FFT_SIZES, MRSTFT_HOP_SIZES, MRSTFT_WIN_LENGTHS = (1024, 2048, 512), (120, 240, 50), (600, 1200, 240)

@@ -1,0 +1,92 @@
+"""Autograd nodes of the training path (RNN.train_epoch, code/model.py:90-161): GRU-HS[64] with input_size = output_size = 1 and
+no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
+
+  * GRUTrainStep: one stateful forward call of the GRU + head as a graph node.  forward = ntm_gru_train_forward (the step of the
+    low-latency kernel, bit-identical to kernel_variant "lat", plus the activations saved for BPTT); backward =
+    ntm_gru_train_backward (one workgroup per stream) + ntm_gru_train_reduce (fixed-order sum over the streams): the gradients of
+    the six parameters and of the initial state h0.  dh0 is what chains a window to the one before it (the warm-up of
+    train_epoch is such a node: code/model.py:122 runs it with grad enabled and does not detach it).
+  * ESRLossFn / DCPreESRLossFn: the loss value exactly as the no-grad path computes it, and its adjoint on the device
+    (ntm_esr_grad / ntm_esr_dcpre_grad).
+"""
+import torch
+
+from . import _lib
+from ._lib import ptr
+
+HIDDEN = 64
+SUPPORTED = "RNN(input_size=1, hidden_size=64, output_size=1, skip=False) on a HIP device"
+
+
+class GRUTrainStep(torch.autograd.Function):
+    """(x [B,T] fp32 contiguous, h0 [B,64], w_ih, w_hh, b_ih, b_hh, w_o, b_o) -> (y [B,T], h_T [B,64]), both fresh tensors."""
+
+    @staticmethod
+    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, w_o, b_o):
+        B, T = x.shape
+        L = _lib.lib()
+        h = h0.detach().to(torch.float32).reshape(B, HIDDEN).clone(memory_format=torch.contiguous_format)
+        y = torch.empty(B, T, device=x.device, dtype=torch.float32)
+        ws = torch.empty(max(int(L.ntm_gru_train_workspace_floats(B, T)), 1), device=x.device, dtype=torch.float32)
+        _lib.check(L.ntm_gru_train_forward(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(x), ptr(y), B, T, T, T,
+                                           ptr(h), ptr(ws), _lib.current_stream()), "ntm_gru_train_forward")
+        # the weights through save_for_backward: torch's version counters then refuse a backward after an in-place update
+        ctx.save_for_backward(x, ws, w_ih, w_hh, b_ih, b_hh, w_o, b_o)
+        ctx.h0_shape = h0.shape
+        ctx.set_materialize_grads(False)
+        return y, h
+
+    @staticmethod
+    def backward(ctx, dy, dh):
+        x, ws, w_ih, w_hh, b_ih, b_hh, w_o, b_o = ctx.saved_tensors
+        B, T = x.shape
+        dev = x.device
+        dy = None if dy is None else dy.to(torch.float32).contiguous()
+        dh = None if dh is None else dh.to(torch.float32).reshape(B, HIDDEN).contiguous()
+        dh0 = torch.empty(B, HIDDEN, device=dev, dtype=torch.float32)
+        part = torch.empty(max(B, 1), _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
+        grad = torch.empty(_lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
+        L, s = _lib.lib(), _lib.current_stream()
+        _lib.check(L.ntm_gru_train_backward(ptr(w_hh), ptr(w_o), ptr(x), T, ptr(ws), ptr(dy), T, ptr(dh), B, T, ptr(dh0), ptr(part), s),
+                   "ntm_gru_train_backward")
+        _lib.check(L.ntm_gru_train_reduce(ptr(part), B, ptr(grad), s), "ntm_gru_train_reduce")
+        H3 = 3 * HIDDEN
+        sizes = [w_ih.numel(), w_hh.numel(), H3, H3, HIDDEN, 1]
+        g_wih, g_whh, g_bih, g_bhh, g_wo, g_bo = torch.split(grad, sizes)
+        return (None, dh0.view(ctx.h0_shape), g_wih.view(w_ih.shape), g_whh.view(w_hh.shape), g_bih.view(b_ih.shape),
+                g_bhh.view(b_hh.shape), g_wo.view(w_o.shape), None if b_o is None else g_bo.view(b_o.shape))
+
+
+class _LossFn(torch.autograd.Function):
+    """Shared body of the two loss nodes: `value(output, target)` -> (loss, whole-batch sums [2] fp64) runs under no_grad."""
+
+    @staticmethod
+    def forward(ctx, output, target, value, R):
+        loss, sums = value(output, target)
+        ctx.save_for_backward(output, target, sums)
+        ctx.R = R
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from .model import ESR_EPS, _as_bt
+        output, target, sums = ctx.saved_tensors
+        y = _as_bt(output, "loss backward")
+        t = _as_bt(target, "loss backward")
+        B, T = y.shape
+        g = gout.detach().to(device=y.device, dtype=torch.float32).reshape(1).contiguous()
+        dy = torch.empty(B, T, device=y.device, dtype=torch.float32)
+        L, s = _lib.lib(), _lib.current_stream()
+        if ctx.R is None:
+            _lib.check(L.ntm_esr_grad(ptr(y), ptr(t), B, T, ptr(sums), ptr(g), ESR_EPS, ptr(dy), s), "ntm_esr_grad")
+        else:
+            _lib.check(L.ntm_esr_dcpre_grad(ptr(y), ptr(t), B, T, float(ctx.R), ptr(sums), ptr(g), ESR_EPS, ptr(dy), s),
+                       "ntm_esr_dcpre_grad")
+        return dy.view(output.shape).to(output.dtype), None, None, None
+
+
+def loss_with_grad(output, target, value, R):
+    """The loss node: `value` computes the no-grad path's value and the whole-batch sums; R None = ESR, else DCPreESR."""
+    if target.requires_grad:
+        raise RuntimeError("ESRLoss / DCPreESR: gradients flow to the prediction only; the target must not require grad")
+    return _LossFn.apply(output, target, value, R)

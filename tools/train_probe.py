@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Time of one TBPTT window of RNN.train_epoch (code/model.py:126-153: forward + loss + backward + Adam step) for GRU-HS[64] at
+L = 1024 samples, B = 32 (code/train.py's BATCH_SIZE) and B = 4096 (a throughput point): this engine (csrc/gru_train.hip) and
+torch.nn.GRU + Linear (MIOpen) on the same GPU, the latter in a fresh child process.  With --rocprof the engine's part is re-run
+in a child under `rocprofv3 --kernel-trace --stats` and the per-kernel times are listed.
+usage: python tools/train_probe.py [--iters N] [--rocprof]"""
+import argparse
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+L = 1024
+
+
+def _time(fn, iters):
+    import torch
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def engine(B, iters):
+    import torch
+    import ntm_amd
+    torch.manual_seed(0)
+    m = ntm_amd.RNN(1, 64, 1).cuda()
+    for p in m.parameters():
+        p.requires_grad_(True)
+    opt = torch.optim.Adam(m.parameters(), 1e-3)
+    loss_fcn = ntm_amd.ESRLoss()
+    x = torch.rand(B, 1, L, device="cuda") - 0.5
+    t = 0.5 * x
+    m.hidden = torch.zeros(1, B, 64, device="cuda")
+
+    def window():
+        y = m(x)
+        loss = loss_fcn(y, t)
+        loss.backward()
+        opt.step()
+        m.detach_hidden()
+        m.zero_grad()
+    return _time(window, iters)
+
+
+def miopen(B, iters, native=False):
+    """torch.nn.GRU + Linear training; `native`: with torch's own GRU cell kernels instead of MIOpen (cudnn backend off)."""
+    import torch
+    torch.backends.cudnn.enabled = not native
+    torch.manual_seed(0)
+    gru = torch.nn.GRU(1, 64, batch_first=True).cuda()
+    lin = torch.nn.Linear(64, 1).cuda()
+    opt = torch.optim.Adam(list(gru.parameters()) + list(lin.parameters()), 1e-3)
+    x = torch.rand(B, L, 1, device="cuda") - 0.5
+    t = 0.5 * x
+    state = {"h": torch.zeros(1, B, 64, device="cuda")}
+
+    def window():
+        out, h = gru(x, state["h"])
+        y = lin(out)
+        loss = ((t - y) ** 2).mean() / ((t ** 2).mean() + 1e-5)
+        loss.backward()
+        opt.step()
+        state["h"] = h.detach()
+        opt.zero_grad()
+    return _time(window, iters)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rocprof", action="store_true")
+    ap.add_argument("--child", choices=["engine", "miopen", "native"])
+    ap.add_argument("--sizes", default="32,4096")
+    a = ap.parse_args()
+    sizes = [int(b) for b in a.sizes.split(",")]
+    if a.child:
+        out = {}
+        for B in sizes:
+            if a.child == "engine":
+                out[str(B)] = engine(B, a.iters)
+                continue
+            # a torch-side RuntimeError (e.g. a MIOpen status) is reported as data: the child still exits normally, so that the
+            # parent can tell it from a crash
+            try:
+                out[str(B)] = miopen(B, a.iters, native=a.child == "native")
+            except RuntimeError as e:
+                out[str(B)] = f"error: {str(e).splitlines()[0][:200]}"
+        print(json.dumps(out))
+        return
+
+    def child(cmd, what):
+        """Run one GPU child; anything but a clean exit (a Python error, a signal, an abort, a time limit) ends the probe before
+        another GPU process is started."""
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"{what}: time limit; nothing more is started")
+        if r.returncode != 0:
+            raise SystemExit(f"{what} exited with status {r.returncode}; nothing more is started\n{r.stderr[-2000:]}")
+        return r
+
+    rows = {}
+    for kind in ("engine", "miopen", "native"):
+        r = child([sys.executable, __file__, "--child", kind, "--iters", str(a.iters), "--sizes", a.sizes], f"{kind} child")
+        rows[kind] = json.loads(r.stdout.strip().splitlines()[-1])
+    fmt = lambda v: f"{v:.3f}" if isinstance(v, float) else "n/a"      # noqa: E731
+    print("ms per TBPTT window (L = 1024; forward + ESR loss + backward + Adam):")
+    print(f"{'B':>6} {'this engine':>12} {'MIOpen':>10} {'torch native':>13}")
+    for B in map(str, sizes):
+        print(f"{B:>6} {fmt(rows['engine'][B]):>12} {fmt(rows['miopen'][B]):>10} {fmt(rows['native'][B]):>13}")
+    for kind in ("miopen", "native"):
+        for B in map(str, sizes):
+            if not isinstance(rows[kind][B], float):
+                print(f"  {kind} B={B}: {rows[kind][B]}")
+    if a.rocprof:
+        import csv
+        for B in sizes:
+            with tempfile.TemporaryDirectory() as d:
+                child(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "probe", "--output-format", "csv", "--", sys.executable,
+                       __file__, "--child", "engine", "--iters", str(a.iters), "--sizes", str(B)], f"rocprofv3 engine child B={B}")
+                stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
+                if not stats:
+                    raise SystemExit("rocprofv3 wrote no kernel stats")
+                krows = list(csv.DictReader(open(stats[0])))
+            total = sum(float(x["TotalDurationNs"]) for x in krows)
+            print(f"\nper-kernel time of the engine at B = {B} ({a.iters} + 3 warm-up windows):")
+            for x in sorted(krows, key=lambda x: -float(x["TotalDurationNs"]))[:8]:
+                print(f"{float(x['TotalDurationNs']) / total * 100:6.1f}%  {int(x['Calls']):6d} calls  "
+                      f"{float(x['AverageNs']) / 1e3:10.1f} us avg  {x['Name'][:90]}")
+
+
+if __name__ == "__main__":
+    main()
