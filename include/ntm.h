@@ -406,6 +406,20 @@ int ntm_esr_grad(const float *y, const float *t, int64_t B, int64_t T, const dou
 int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2, const float *gout,
                        double eps, float *dy, void *stream);
 
+/*
+ * Adjoint of the time-varying fractional delay line (ntm_delay_forward) over one call of B streams of L samples with a buffer of
+ * D samples (the backward of DiffDelRNN.train_epoch's delay step, code/model.py:269-320,456-496).  With z = [buffer, x] the
+ * forward is y[n] = sum_m w_m(n) z[D + n - m] over the taps m in {k+1, k}, k = floor(d[n]), that it counts, and the new buffer
+ * is z[L : L + D]; warmup: y = x.  Writes gz = [gbuf (D), gpre (L)] per stream:
+ *     gz[i] = g_newbuf[i - L] (i >= L) + the terms w_m(n) gy[n] with D + n - m = i, added in ascending n.
+ * gy [B,L] (null: no gradient from y), d [B,L] in samples (read unless warmup; no gradient flows to it), g_newbuf [B,D] (null:
+ * none), gpre [B,L], gbuf [B,D] (null: not computed).  All contiguous fp32.  Deterministic: repeated calls give the same bits.
+ * flags: 0, or NTM_DELAY_BWD_SCAN to take the general path for every tile (it gives the same bits as the default one).
+ */
+#define NTM_DELAY_BWD_SCAN 1
+int ntm_delay_backward(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
+                       int D, int warmup, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -369,9 +369,121 @@ __global__ __launch_bounds__(64) void esr_dcpre_grad_kernel(const float *__restr
     }
 }
 
+// (e) Adjoint of the time-varying fractional delay line (TimeVaryingDelayLine.forward, code/model.py:269-320) over one call.
+// With z = [buffer (D), pre (L)] the forward is y[n] = sum over the taps m in {k+1, k} that delay_sample() counts of
+// w_m(n) z[D + n - m], and the new buffer is z[L : L + D].  So
+//     gz[i] = g_newbuf[i - L] (i >= L) + sum over ascending n of w_m(n) gy[n] where D + n - m = i,
+// gbuf = gz[:D], gpre = gz[D:].  Warm-up: y = pre, gz[D + n] adds gy[n].  No gradient flows to d (the trajectory is data).
+// One workgroup per stream.  Target i belongs to thread i % DB_T in every phase (its initial value, then one read-modify-write
+// per tile of samples), and it adds its terms in ascending n: no atomics on floats, the bits do not depend on scheduling.
+// Per tile of DB_NT samples the taps are staged in LDS: the target of tap a (m = k) D + q with q = n - k, of tap b (m = k + 1)
+// D + q - 1, -1 where delay_sample() skips the tap, and the products w gy (rounded as the reference's autograd rounds them).
+//   * gather: every d of the tile in [0, D] and q non-decreasing (a delay that never grows by 1 sample or more within one
+//     sample, as every wow / flutter trajectory): the terms of target i are the run of n with q = i - D (tap a), followed by
+//     the run with q = i - D + 1 (tap b).  A binary search over the tile's tap-a targets and a walk over those runs.
+//   * scan (any other tile, or DB_SCAN): every owner looks at every sample of the tile in ascending n.
+// Both add the same terms in the same order, so they give the same bits.
+constexpr int DB_T = 256, DB_NT = 2048;
+
+__global__ __launch_bounds__(DB_T) void delay_bwd_kernel(const float *__restrict__ gy, const float *__restrict__ d,
+                                                         const float *__restrict__ gnb, float *__restrict__ gpre,
+                                                         float *__restrict__ gbuf, int L, int D, int warmup, int force_scan)
+{
+#pragma clang fp contract(off)
+    __shared__ int ta[DB_NT], tb[DB_NT];
+    __shared__ float pa[DB_NT], pb[DB_NT];
+    __shared__ int red[3];                  // lowest and highest target of the tile, scan needed
+
+    const int t = threadIdx.x;
+    const int64_t s = blockIdx.x;
+    const float *gys = gy ? gy + s * L : nullptr;
+    const float *ds = d ? d + s * L : nullptr;
+    const float *gn = gnb ? gnb + s * D : nullptr;
+    float *gp = gpre + s * L;
+    float *gb = gbuf ? gbuf + s * D : nullptr;
+    const int R = D + L;
+
+    for (int i = t; i < R; i += DB_T) {     // the initial value of every target
+        const float v = (gn && i >= L) ? gn[i - L] : 0.0f;
+        if (i < D) {
+            if (gb) gb[i] = v;
+        } else {
+            gp[i - D] = (warmup && gys) ? v + gys[i - D] : v;
+        }
+    }
+    if (warmup || !gys) return;
+
+    const float Dmax = (float)D;
+    for (int n0 = 0; n0 < L; n0 += DB_NT) {
+        const int nt = L - n0 < DB_NT ? L - n0 : DB_NT;
+        if (t == 0) { red[0] = 0x7fffffff; red[1] = -1; red[2] = force_scan; }
+        __syncthreads();
+        int lo = 0x7fffffff, hi = -1, bad = 0;
+        for (int j = t; j < nt; j += DB_T) {
+            const int n = n0 + j;
+            const float dn = ds[n], g = gys[n];
+            const float kf = floorf(dn);
+            int tg[2];
+            float pr[2];
+#pragma unroll
+            for (int tap = 1; tap >= 0; --tap) {     // the tests of delay_sample()
+                const float mf = kf + (float)tap;
+                const float w = 1.0f - fabsf(mf - dn);
+                const bool on = !(mf < 0.0f || mf > Dmax) && w > 0.0f;
+                tg[tap] = on ? D + n - (int)mf : -1;
+                pr[tap] = w * g;
+            }
+            tb[j] = tg[1]; pb[j] = pr[1];
+            ta[j] = tg[0]; pa[j] = pr[0];
+            bad |= !(dn >= 0.0f && dn <= Dmax);     // NaN too; in [0, D] tap a always counts
+            if (tg[1] >= 0) { lo = min(lo, tg[1]); hi = max(hi, tg[1]); }
+            if (tg[0] >= 0) { lo = min(lo, tg[0]); hi = max(hi, tg[0]); }
+        }
+        atomicMin(&red[0], lo);
+        atomicMax(&red[1], hi);
+        __syncthreads();
+        for (int j = t; j + 1 < nt; j += DB_T) bad |= ta[j] > ta[j + 1];
+        if (bad) red[2] = 1;
+        __syncthreads();
+        const int tlo = red[0], thi = red[1];
+        const bool scan = red[2] != 0;
+        for (int i = (tlo & ~(DB_T - 1)) + t; i <= thi; i += DB_T) {       // empty when no tap of the tile counts
+            if (i < tlo || (i < D && !gb)) continue;
+            float acc = i < D ? gb[i] : gp[i - D];
+            if (scan) {
+                for (int j = 0; j < nt; ++j) {
+                    if (tb[j] == i) acc = acc + pb[j];
+                    if (ta[j] == i) acc = acc + pa[j];
+                }
+            } else {
+                int a = 0, b = nt;                  // first j with ta[j] >= i
+                while (a < b) {
+                    const int m = (a + b) >> 1;
+                    if (ta[m] < i) a = m + 1; else b = m;
+                }
+                for (int j = a; j < nt && ta[j] <= i + 1; ++j) {
+                    if (ta[j] == i) acc = acc + pa[j];
+                    else if (tb[j] == i) acc = acc + pb[j];
+                }
+            }
+            if (i < D) gb[i] = acc; else gp[i - D] = acc;
+        }
+        __syncthreads();                        // the stage and red[] are rewritten by the next tile
+    }
+}
+
 }   // namespace
 
 int64_t train_grad_floats() { return NGRAD; }
+
+hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
+                            int D, int warmup, int force_scan, hipStream_t stream)
+{
+    if (B == 0 || L + D == 0) return hipSuccess;
+    hipLaunchKernelGGL(delay_bwd_kernel, dim3((unsigned)B), dim3(DB_T), 0, stream, gy, d, g_newbuf, gpre, gbuf, (int)L, D, warmup,
+                       force_scan);
+    return hipGetLastError();
+}
 
 hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, hipStream_t stream)
 {

@@ -43,6 +43,8 @@ hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const doub
                            hipStream_t stream);
 hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2,
                                  const float *gout, double eps, float *dy, hipStream_t stream);
+hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
+                            int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm
 
 namespace {
@@ -686,6 +688,21 @@ int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, flo
     if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: at most 2^31 - 1 streams per call");
     hipError_t e = ntm::launch_esr_dcpre_grad(y, t, B, T, R, sums2, gout, eps, dy, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_dcpre_grad");
+}
+
+int ntm_delay_backward(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
+                       int D, int warmup, int flags, void *stream)
+{
+    if (B < 0 || L < 0 || D < 0) return fail(NTM_EINVAL, "ntm_delay_backward: negative size");
+    if (flags & ~NTM_DELAY_BWD_SCAN) return fail(NTM_EINVAL, "ntm_delay_backward: unknown flags");
+    if (B == 0 || L + D == 0) return NTM_OK;
+    if (L > 0 && !gpre) return fail(NTM_EINVAL, "ntm_delay_backward: null gpre");
+    if (!warmup && gy && !d) return fail(NTM_EINVAL, "ntm_delay_backward: null d");
+    if ((gy && gy == gpre) || (g_newbuf && g_newbuf == gbuf)) return fail(NTM_EINVAL, "ntm_delay_backward: an output aliases an input");
+    if (D > (1 << 24) || L + D > 0x7fffffffLL - 4096) return fail(NTM_EINVAL, "ntm_delay_backward: D above 2^24 or D + L above 2^31");
+    if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_delay_backward: at most 2^31 - 1 streams per call");
+    hipError_t e = ntm::launch_delay_bwd(gy, d, g_newbuf, gpre, gbuf, B, L, D, warmup, flags & NTM_DELAY_BWD_SCAN, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_delay_backward");
 }
 
 }  // extern "C"

@@ -16,8 +16,8 @@ Deliberate differences from the reference (documented in DESIGN.md):
     called by code/train.py:242) and detach_hidden / detach_buffer are here.  RNN.train_epoch (code/model.py:90-161) trains
     GRU-HS[64] with input_size = output_size = 1 and no skip connection on the kernels of csrc/gru_train.hip (training.py);
     parameters are created with requires_grad=False and train_epoch turns it on.  forward() builds a graph only when grad
-    mode is on AND a parameter requires grad; every other call is the inference path, unchanged.  DiffDelRNN training is
-    not implemented: its forward refuses grad-requiring parameters.
+    mode is on AND a parameter requires grad; every other call is the inference path, unchanged.  DiffDelRNN.train_epoch
+    (code/model.py:426-511) trains DiffDelGRU-HS[64] the same way, with the delay line's adjoint on the device.
   * warm_start() from a fresh state is a pure function of the parameters.  With `warm_cache = True` its result (hidden
     state; for the DiffDelGRU also the delay buffer) is computed by the kernel ONCE per (parameter storage + torch version
     counter, device, kernel variant, delay-line length) and kept, so a predict() is one launch instead of two -- same numbers
@@ -567,13 +567,65 @@ class DiffDelRNN(_GRUHead):
         return super()._one_launch() and (self.delay_mode == "auto" if losses else self.delay_mode != "two_pass")
 
     def forward(self, x, del_traj, warmup=False, _events=None):
-        """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424); inference only -- with grad mode on and a parameter that
-        requires grad it raises (DiffDelRNN training needs the delay line's adjoint, which is not implemented)."""
+        """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424).  With grad mode on and a parameter that requires grad
+        (DiffDelRNN.train_epoch) the call is two nodes of the autograd graph: training.GRUTrainStep (the low-latency kernel's
+        step, no head bias) and training.DelayLineStep; y, pre_d, self.hidden and the delay buffer are then in the graph, with
+        the bits of kernel_variant "lat" / delay_mode "two_pass".  Otherwise nothing is recorded."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError(f"DiffDelRNN.forward: parameters require grad, but DiffDelRNN training is not implemented; training "
-                               f"runs for {training.SUPPORTED} only")
+            return self._forward_train(x, del_traj, warmup)
         with torch.no_grad():
             return self._forward_infer(x, del_traj, warmup, _events)
+
+    def _check_trainable(self, what):
+        """The configuration the training kernels cover, else a RuntimeError that names it."""
+        if self.hidden_size != training.HIDDEN or self.skip:
+            raise RuntimeError(f"{what}: training runs for {training.SUPPORTED_DIFFDEL} only; this model is DiffDelRNN(input_size="
+                               f"{self.input_size}, hidden_size={self.hidden_size}, output_size={self.output_size}, skip={self.skip})")
+        dev = self.GRU.weight_hh_l0.device
+        if not self.GRU.weight_hh_l0.is_cuda:
+            raise RuntimeError(f"{what}: DiffDelRNN training is not implemented for parameters on '{dev}': it runs on a HIP "
+                               f"device only ({training.SUPPORTED_DIFFDEL})")
+
+    def _forward_train(self, x, del_traj, warmup):
+        """forward() as graph nodes.  The new delay buffer is a fresh tensor (the warm-up's outputs in it stay in the graph of
+        the first window); a delay above the buffer raises AssertionError (code/model.py:284) with the buffer as it was -- the
+        hidden state has moved on by then, as in the reference, where the GRU runs before the delay line asserts."""
+        self._check_trainable("DiffDelRNN.forward")
+        if x.requires_grad or del_traj.requires_grad:
+            raise RuntimeError("DiffDelRNN.forward: the input or the delay trajectory requires grad; the training kernels give "
+                               f"gradients for the parameters, the hidden state and the delay buffer only ({training.SUPPORTED_DIFFDEL})")
+        xbt = _as_bt(x, "DiffDelRNN.forward")
+        dbt = _as_bt(del_traj, "DiffDelRNN.forward")
+        if dbt.shape != xbt.shape:
+            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        B, T = xbt.shape
+        H = self.hidden_size
+        dl = self.diffdel
+        D = int(dl.max_delay)
+        if dl.buffer.shape[0] != B or dl.buffer.shape[2] != D:
+            raise RuntimeError(f"Sizes of tensors must match: buffer {list(dl.buffer.shape)} vs input batch {B}")
+        if dl.buffer.device != xbt.device or dl.buffer.dtype != torch.float32:
+            dl.buffer = dl.buffer.to(device=xbt.device, dtype=torch.float32)
+        if dl._err is None or dl._err.device != xbt.device:
+            dl._err = torch.zeros(1, device=xbt.device, dtype=torch.int32)
+        if self.hidden is None:
+            h0 = torch.zeros(B, H, device=xbt.device, dtype=torch.float32)
+        elif tuple(self.hidden.shape) != (1, B, H):
+            raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
+        else:
+            h0 = self.hidden.reshape(B, H)
+        g = self.GRU
+        pre, h = training.GRUTrainStep.apply(xbt, h0, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0,
+                                             self.output.weight, None)
+        self.hidden = h.view(1, B, H)
+        y, buf = training.DelayLineStep.apply(pre, dl.buffer, dbt, bool(warmup), dl._err)
+        dl._fresh = False
+        if not dl.defer_check:
+            dl.raise_if_violated()
+        else:
+            dl._unchecked = True
+        dl.buffer = buf
+        return y.view(B, 1, T), pre.view(B, 1, T)
 
     def _forward_infer(self, x, del_traj, warmup=False, _events=None):
         """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424).  `_events`: three torch.cuda.Event objects
@@ -719,6 +771,69 @@ class DiffDelRNN(_GRUHead):
                 output[:, :, sl], output_pre_d[:, :, sl] = self.forward(input[:, :, sl], d_traj[:, :, sl])
             return output, output_pre_d
         return self._predict_with(run, input)
+
+    def train_epoch(self, dataloader, loss_fcn, optimizer, dataset=None):
+        """One epoch of truncated back-propagation through time (code/model.py:426-511, run by code/train.py --MODEL DiffDelGRU):
+        per batch the state is reset (zero delay buffer of max_delay + 1 samples), aggregated with grad enabled on the first
+        TBPTT_INIT = nextpow2(int(analyser max_delay * fs)) samples (`warmup=True`: the delay line only fills its buffer), then
+        every whole window of 2048 samples is predicted, scored with `loss_fcn(pred, target)`, back-propagated and followed by
+        `optimizer.step()`; returns the mean over batches of the mean window loss.  As in the reference the warm-up is not
+        detached: the first window's backward reaches it through the hidden state and through the delay taps that read the
+        buffer.  `dataset` (default `dataloader.dataset`): `fs` and `delay_analyzer.max_delay` (the reference's dataset) or
+        `max_delay` (SegmentFeeder), in seconds.  `dataloader`: the reference's (x, t, meta) batches with
+        meta['delay_trajectory'] (B, T) in seconds, or SegmentFeeder.batches' (x, t, d_seconds (B,1,T), metas).  The delays are
+        the fp32 product d_seconds * fs, as the reference forms them.
+        Supported: DiffDelRNN(1, 64, 1, skip=False) on a HIP device (RuntimeError otherwise).  On entry it sets requires_grad on
+        the GRU and head parameters."""
+        from .utilities import nextpow2
+        self._check_trainable("DiffDelRNN.train_epoch")
+        dataset = dataloader.dataset if dataset is None else dataset
+        fs = dataset.fs
+        max_delay = dataset.delay_analyzer.max_delay if hasattr(dataset, "delay_analyzer") else dataset.max_delay
+        TBPTT_INIT = nextpow2(int(max_delay * fs))
+        TBPTT_LEN = 2**11
+        for p in self.parameters():
+            p.requires_grad_(True)
+        device = self.GRU.weight_hh_l0.device
+        self.train()
+
+        num_batches = 0             # counted, so that a generator (SegmentFeeder.batches) serves as well as a DataLoader
+        epoch_loss = 0
+        for _, batch in enumerate(dataloader):
+            input, target = batch[0], batch[1]
+            if input.shape[1] > 1:  # only the audio channel counts for training
+                input, target = input[:, :1, :], target[:, :1, :]
+            if isinstance(batch[2], dict):
+                d_traj = batch[2]["delay_trajectory"].float()
+                d_traj = d_traj.unsqueeze(1) * fs
+            elif batch[2] is not None:
+                d_traj = batch[2][:, :1, :].float() * fs
+            else:
+                raise RuntimeError("DiffDelRNN.train_epoch: the batch carries no delay trajectory")
+            input, target, d_traj = input.to(device), target.to(device), d_traj.to(device)
+
+            num_minibatches = int(np.ceil((input.shape[-1] - TBPTT_INIT) // TBPTT_LEN))
+            self.initialize_hidden(input.shape[0], self.max_delay)
+            _, __ = self.forward(input[:, :, :TBPTT_INIT], d_traj[:, :, :TBPTT_INIT], warmup=True)     # graph nodes
+            self.zero_grad()
+
+            minibatch_loss = 0
+            sample_offset = TBPTT_INIT
+            for _ in range(num_minibatches):
+                sl = slice(sample_offset, sample_offset + TBPTT_LEN)
+                pred_mini, _ = self.forward(input[:, :, sl], d_traj[:, :, sl])
+                loss = loss_fcn(pred_mini, target[:, :, sl])
+                loss.backward()
+                optimizer.step()
+                self.detach_hidden()
+                self.zero_grad()
+                minibatch_loss += loss.item()
+                sample_offset += TBPTT_LEN
+            minibatch_loss /= num_minibatches      # ZeroDivisionError when no whole window follows the warm-up, as in the reference
+            epoch_loss += minibatch_loss
+            num_batches += 1
+        epoch_loss /= num_batches
+        return epoch_loss
 
     @torch.no_grad()
     def validate(self, dataloader, loss_fcn, store_examples=True):

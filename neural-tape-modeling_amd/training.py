@@ -6,6 +6,10 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
     ntm_gru_train_backward (one workgroup per stream) + ntm_gru_train_reduce (fixed-order sum over the streams): the gradients of
     the six parameters and of the initial state h0.  dh0 is what chains a window to the one before it (the warm-up of
     train_epoch is such a node: code/model.py:122 runs it with grad enabled and does not detach it).
+  * DelayLineStep: one call of the time-varying fractional delay line of DiffDelRNN (code/model.py:269-320) as a graph node.
+    forward = ntm_delay_forward into a FRESH new-buffer tensor (the old buffer stays as it was: an in-place update would cut
+    the edge from the first window back to the warm-up, whose outputs fill the buffer the first window's taps read);
+    backward = ntm_delay_backward, the deterministic adjoint (gradients for pre and, where it is in the graph, the old buffer).
   * ESRLossFn / DCPreESRLossFn: the loss value exactly as the no-grad path computes it, and its adjoint on the device
     (ntm_esr_grad / ntm_esr_dcpre_grad).
 """
@@ -16,6 +20,7 @@ from ._lib import ptr
 
 HIDDEN = 64
 SUPPORTED = "RNN(input_size=1, hidden_size=64, output_size=1, skip=False) on a HIP device"
+SUPPORTED_DIFFDEL = "DiffDelRNN(input_size=1, hidden_size=64, output_size=1, skip=False) on a HIP device"
 
 
 class GRUTrainStep(torch.autograd.Function):
@@ -55,6 +60,38 @@ class GRUTrainStep(torch.autograd.Function):
         g_wih, g_whh, g_bih, g_bhh, g_wo, g_bo = torch.split(grad, sizes)
         return (None, dh0.view(ctx.h0_shape), g_wih.view(w_ih.shape), g_whh.view(w_hh.shape), g_bih.view(b_ih.shape),
                 g_bhh.view(b_hh.shape), g_wo.view(w_o.shape), None if b_o is None else g_bo.view(b_o.shape))
+
+
+class DelayLineStep(torch.autograd.Function):
+    """(pre [B,L] fp32 contiguous, buffer [B,1,D], d [B,L] in samples, warmup, err_flag) -> (y [B,L], new_buffer [B,1,D]), both
+    fresh tensors.  The range check (code/model.py:284) raises the caller's sticky device flag; the new buffer is then the old
+    one unchanged (ntm_delay_forward skips its update), and the caller raises AssertionError before it keeps anything."""
+
+    @staticmethod
+    def forward(ctx, pre, buffer, d, warmup, err):
+        B, T = pre.shape
+        D = buffer.shape[-1]
+        y = torch.empty_like(pre)
+        nb = buffer.detach().to(torch.float32).reshape(B, D).clone(memory_format=torch.contiguous_format)
+        _lib.check(_lib.lib().ntm_delay_forward(ptr(pre), ptr(d), ptr(y), B, T, ptr(nb), D, int(bool(warmup)), ptr(err),
+                                                _lib.current_stream()), "ntm_delay_forward")
+        ctx.save_for_backward(d)
+        ctx.warmup, ctx.buf_shape = bool(warmup), buffer.shape
+        ctx.set_materialize_grads(False)
+        return y, nb.view(buffer.shape)
+
+    @staticmethod
+    def backward(ctx, gy, gnb):
+        d, = ctx.saved_tensors
+        B, T = d.shape
+        D = ctx.buf_shape[-1]
+        gy = None if gy is None else gy.to(torch.float32).contiguous()
+        gnb = None if gnb is None else gnb.to(torch.float32).reshape(B, D).contiguous()
+        gpre = torch.empty(B, T, device=d.device, dtype=torch.float32)
+        gbuf = torch.empty(B, D, device=d.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().ntm_delay_backward(ptr(gy), ptr(d), ptr(gnb), ptr(gpre), ptr(gbuf), B, T, D, int(ctx.warmup), 0,
+                                                 _lib.current_stream()), "ntm_delay_backward")
+        return gpre, None if gbuf is None else gbuf.view(ctx.buf_shape), None, None, None
 
 
 class _LossFn(torch.autograd.Function):

@@ -3,7 +3,10 @@
 L = 1024 samples, B = 32 (code/train.py's BATCH_SIZE) and B = 4096 (a throughput point): this engine (csrc/gru_train.hip) and
 torch.nn.GRU + Linear (MIOpen) on the same GPU, the latter in a fresh child process.  With --rocprof the engine's part is re-run
 in a child under `rocprofv3 --kernel-trace --stats` and the per-kernel times are listed.
-usage: python tools/train_probe.py [--iters N] [--rocprof]"""
+With --model diffdel: one TBPTT window of DiffDelRNN.train_epoch (code/model.py:464-497) for DiffDelGRU-HS[64] at L = 2048, D = 11 001
+(forward: GRU + delay line, loss, backward: delay adjoint + BPTT + reduce, Adam), and the backward of a 16 384-sample warm-up
+(TBPTT_INIT at that D) reached through the first window; its GRU workspace is B * 16 384 * 1280 B (0.67 GB at B = 32).
+usage: python tools/train_probe.py [--model gru|diffdel] [--iters N] [--rocprof]"""
 import argparse
 import glob
 import json
@@ -54,6 +57,54 @@ def engine(B, iters):
     return _time(window, iters)
 
 
+DD_L, DD_D, DD_INIT = 2048, 11001, 16384
+
+
+def engine_diffdel(B, iters):
+    """-> (ms per window, ms per warm-up + first window, ms of the delay adjoint alone per window)."""
+    import torch
+    import ntm_amd
+    torch.manual_seed(0)
+    m = ntm_amd.DiffDelRNN(1, 64, 1, max_delay=DD_D - 1).cuda()
+    for p in m.parameters():
+        p.requires_grad_(True)
+    opt = torch.optim.Adam(m.parameters(), 1e-3)
+    loss_fcn = ntm_amd.ESRLoss()
+    n = torch.arange(DD_INIT + DD_L, device="cuda", dtype=torch.float32)
+    d = (5500.0 + 4000.0 * torch.sin(n / 7000.0) + 20.0 * torch.sin(n / 300.0)).expand(B, 1, -1).contiguous()
+    x = torch.rand(B, 1, DD_INIT + DD_L, device="cuda") - 0.5
+    t = 0.5 * x
+    m.initialize_hidden(B, m.max_delay)
+    m(x[:, :, :DD_INIT], d[:, :, :DD_INIT], warmup=True)
+    m.detach_hidden()
+    xs, ds, ts = x[:, :, DD_INIT:], d[:, :, DD_INIT:], t[:, :, DD_INIT:]
+
+    def window():
+        y, _ = m(xs, ds)
+        loss = loss_fcn(y, ts)
+        loss.backward()
+        opt.step()
+        m.detach_hidden()
+        m.zero_grad()
+
+    def first_window():
+        m.initialize_hidden(B, m.max_delay)
+        m(x[:, :, :DD_INIT], d[:, :, :DD_INIT], warmup=True)
+        window()
+
+    L_ = ntm_amd._lib.lib()
+    gy = torch.randn(B, DD_L, device="cuda")
+    dd = ds.reshape(B, DD_L).contiguous()
+    gpre = torch.empty(B, DD_L, device="cuda")
+    gbuf = torch.empty(B, DD_D, device="cuda")
+    p = ntm_amd._lib.ptr
+
+    def adjoint():
+        ntm_amd._lib.check(L_.ntm_delay_backward(p(gy), p(dd), None, p(gpre), p(gbuf), B, DD_L, DD_D, 0, 0,
+                                                 ntm_amd._lib.current_stream()), "ntm_delay_backward")
+    return _time(window, iters), _time(first_window, max(iters // 4, 2)), _time(adjoint, iters)
+
+
 def miopen(B, iters, native=False):
     """torch.nn.GRU + Linear training; `native`: with torch's own GRU cell kernels instead of MIOpen (cudnn backend off)."""
     import torch
@@ -81,10 +132,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rocprof", action="store_true")
-    ap.add_argument("--child", choices=["engine", "miopen", "native"])
+    ap.add_argument("--child", choices=["engine", "miopen", "native", "diffdel"])
     ap.add_argument("--sizes", default="32,4096")
+    ap.add_argument("--model", choices=["gru", "diffdel"], default="gru")
     a = ap.parse_args()
     sizes = [int(b) for b in a.sizes.split(",")]
+    if a.child == "diffdel":
+        print(json.dumps({str(B): engine_diffdel(B, a.iters) for B in sizes}))
+        return
     if a.child:
         out = {}
         for B in sizes:
@@ -111,6 +166,18 @@ def main():
             raise SystemExit(f"{what} exited with status {r.returncode}; nothing more is started\n{r.stderr[-2000:]}")
         return r
 
+    if a.model == "diffdel":
+        r = child([sys.executable, __file__, "--child", "diffdel", "--iters", str(a.iters), "--sizes", a.sizes], "diffdel child")
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        print(f"DiffDelGRU-HS[64], ms (L = {DD_L}, D = {DD_D}; window = forward + ESR loss + backward + Adam):")
+        print(f"{'B':>6} {'window':>9} {'warm-up + window 1':>19} {'delay adjoint':>14} {'adjoint share':>14}")
+        for B in map(str, sizes):
+            w, f, adj = res[B]
+            print(f"{B:>6} {w:9.3f} {f:19.3f} {adj:14.4f} {adj / w * 100:13.2f}%")
+        if a.rocprof:
+            _rocprof(child, a, sizes, "diffdel")
+        return
+
     rows = {}
     for kind in ("engine", "miopen", "native"):
         r = child([sys.executable, __file__, "--child", kind, "--iters", str(a.iters), "--sizes", a.sizes], f"{kind} child")
@@ -125,20 +192,25 @@ def main():
             if not isinstance(rows[kind][B], float):
                 print(f"  {kind} B={B}: {rows[kind][B]}")
     if a.rocprof:
-        import csv
-        for B in sizes:
-            with tempfile.TemporaryDirectory() as d:
-                child(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "probe", "--output-format", "csv", "--", sys.executable,
-                       __file__, "--child", "engine", "--iters", str(a.iters), "--sizes", str(B)], f"rocprofv3 engine child B={B}")
-                stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-                if not stats:
-                    raise SystemExit("rocprofv3 wrote no kernel stats")
-                krows = list(csv.DictReader(open(stats[0])))
-            total = sum(float(x["TotalDurationNs"]) for x in krows)
-            print(f"\nper-kernel time of the engine at B = {B} ({a.iters} + 3 warm-up windows):")
-            for x in sorted(krows, key=lambda x: -float(x["TotalDurationNs"]))[:8]:
-                print(f"{float(x['TotalDurationNs']) / total * 100:6.1f}%  {int(x['Calls']):6d} calls  "
-                      f"{float(x['AverageNs']) / 1e3:10.1f} us avg  {x['Name'][:90]}")
+        _rocprof(child, a, sizes, "engine")
+
+
+def _rocprof(child, a, sizes, kind):
+    """The per-kernel split of the `kind` child under rocprofv3 --kernel-trace --stats, one child per batch size."""
+    import csv
+    for B in sizes:
+        with tempfile.TemporaryDirectory() as d:
+            child(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "probe", "--output-format", "csv", "--", sys.executable,
+                   __file__, "--child", kind, "--iters", str(a.iters), "--sizes", str(B)], f"rocprofv3 {kind} child B={B}")
+            stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
+            if not stats:
+                raise SystemExit("rocprofv3 wrote no kernel stats")
+            krows = list(csv.DictReader(open(stats[0])))
+        total = sum(float(x["TotalDurationNs"]) for x in krows)
+        print(f"\nper-kernel time of the engine at B = {B} ({a.iters} + 3 warm-up windows):")
+        for x in sorted(krows, key=lambda x: -float(x["TotalDurationNs"]))[:12]:
+            print(f"{float(x['TotalDurationNs']) / total * 100:6.1f}%  {int(x['Calls']):6d} calls  "
+                  f"{float(x['AverageNs']) / 1e3:10.1f} us avg  {x['Name'][:90]}")
 
 
 if __name__ == "__main__":
