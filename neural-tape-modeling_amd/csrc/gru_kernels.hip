@@ -11,7 +11,7 @@
 //                    in VGPRs as MFMA A-operands, h exchanged between the 4 waves through LDS.
 //   gru_valu_kernel  NS streams per wavefront; lane j owns hidden unit j with its three W_hh rows in
 //                    192 VGPRs, h broadcast through LDS, v_fma_f32 GEMV, DPP wave reduction for the head.
-#include "ntm_common.h"
+#include "gru_lat_step.h"
 
 namespace ntm {
 
@@ -271,24 +271,7 @@ __global__ __launch_bounds__(256, 1) void gru_mfma_kernel(GruArgs a)
 // =====================================================================================
 // Variant 2: VALU, NS streams per wavefront (workgroup = one wave).
 // =====================================================================================
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_shift_add(float v)
-{
-    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false);
-    return v + __builtin_bit_cast(float, moved);
-}
-
-// Sum over the 64 lanes; the total is valid in lane 63 (gfx9 row_shr / row_bcast scan).
-__device__ __forceinline__ float wave_sum_lane63(float v)
-{
-    v = dpp_shift_add<0x111, 0xf>(v);  // row_shr:1
-    v = dpp_shift_add<0x112, 0xf>(v);  // row_shr:2
-    v = dpp_shift_add<0x114, 0xf>(v);  // row_shr:4
-    v = dpp_shift_add<0x118, 0xf>(v);  // row_shr:8
-    v = dpp_shift_add<0x142, 0xa>(v);  // row_bcast:15 -> rows 1,3
-    v = dpp_shift_add<0x143, 0xc>(v);  // row_bcast:31 -> rows 2,3
-    return v;
-}
+using lat::wave_sum_lane63;   // the head sum of the low-latency step (gru_lat_step.h): total valid in lane 63
 
 template <int NS>
 __global__ __launch_bounds__(64, 2) void gru_valu_kernel(GruArgs a)

@@ -7,62 +7,22 @@
 //
 // Workspace of the forward (and input of the backward): ws[s][t][j][u], j = 0..4 = h_{t-1}, r, z, n, gh_n (unscaled), fp32.
 // Per-stream gradient partials: part[s][NTM_TRAIN_GRAD_FLOATS] in the order w_ih | w_hh | b_ih | b_hh | w_o | b_o (12929).
-#include "ntm_common.h"
-
-#include <type_traits>
+#include "gru_lat_step.h"
 
 namespace ntm {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-constexpr int LT = 256;                  // samples per x / y tile (as gru_lat.hip)
-constexpr float LOG2E = 1.44269504088896340736f;
+using namespace lat;                     // the low-latency step and its DPP helpers, shared with gru_lat.hip
+
 constexpr int NSAVE = 5;                 // h_{t-1}, r, z, n, gh_n
 constexpr int OFF_WHH = 3 * kH, OFF_BIH = OFF_WHH + 3 * kH * kH, OFF_BHH = OFF_BIH + 3 * kH, OFF_WO = OFF_BHH + 3 * kH,
               OFF_BO = OFF_WO + kH, NGRAD = OFF_BO + 1;
 static_assert(NGRAD == 12929, "w_ih + w_hh + b_ih + b_hh + w_o + b_o of GRU(1, 64) + Linear(64, 1)");
 
-// A workgroup barrier that orders LDS only: global stores and loads in flight (the flush of the forward's saves, the
-// backward's prefetch) are not drained by it, as they would be by the vmcnt(0) of a full __syncthreads().
-__device__ __forceinline__ void lds_barrier()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_shift_add(float v)
-{
-    const int moved = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false);
-    return v + __builtin_bit_cast(float, moved);
-}
-
-// gru_lat.hip's head sum (same shifts, same order): total in lane 63
-__device__ __forceinline__ float wave_sum_lane63(float v)
-{
-    v = dpp_shift_add<0x111, 0xf>(v);
-    v = dpp_shift_add<0x112, 0xf>(v);
-    v = dpp_shift_add<0x114, 0xf>(v);
-    v = dpp_shift_add<0x118, 0xf>(v);
-    v = dpp_shift_add<0x142, 0xa>(v);
-    v = dpp_shift_add<0x143, 0xc>(v);
-    return v;
-}
-
-template <int PERM>
-__device__ __forceinline__ float quad_add(float v)
-{
-    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), PERM, 0xf, 0xf, true);
-    return v + __builtin_bit_cast(float, o);
-}
-
-// (a) Forward with saved activations: the step of gru_lat_kernel<true> (gru_lat.hip) operation for operation -- same lane
-// layout (wave w < 4, lane 4 ul + kq: K quarter kq of unit 16 w + ul), same summation order, same v_exp_f32 / v_rcp_f32 gate
-// forms, the head on a fifth wave -- so y and the final h are bit-identical to kernel_variant "lat" for every B (the head's
-// arithmetic does not depend on which wave evaluates it).  In addition lane kq of each quad writes one of the saved values of
+// (a) Forward with saved activations: gru_lat_kernel<true> (gru_lat.hip) built from the same pieces of gru_lat_step.h -- the
+// lane constants, the gate evaluation, the head on a fifth wave, the parity unroller, the epilogue -- so y and the final h
+// are bit-identical to kernel_variant "lat" for every B because they are computed by the same code (the head's arithmetic
+// does not depend on which wave evaluates it).  In addition lane kq of each quad writes one of the saved values of
 // its unit per step (kq = 0 also gh_n) to an LDS stage of SC steps, which the whole workgroup flushes to the workspace with
 // coalesced 16-byte stores after every SC steps.  (Stored straight from the step, each global store made the compiler wait
 // for its completion before the step's registers were reused: a store round trip inside the recurrence, every step.  The
@@ -88,23 +48,11 @@ __global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__
     float *ys = a.y + s * a.ys;
     float *const stg_l = stg + kq * kH + u;                              // this lane's save slot in the stage's step 0
 
-    constexpr float SRZ = -LOG2E, SN = 2.0f * LOG2E;
     constexpr float INV_SN = 1.0f / SN;
-    f32x2 Wr[8], Wz[8], Wn[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float *pr = a.w_hh + (size_t)(0 * kH + u) * kH + 16 * kq + 2 * k;
-        const float *pz = a.w_hh + (size_t)(1 * kH + u) * kH + 16 * kq + 2 * k;
-        const float *pn = a.w_hh + (size_t)(2 * kH + u) * kH + 16 * kq + 2 * k;
-        Wr[k] = (f32x2){pr[0] * SRZ, pr[1] * SRZ};
-        Wz[k] = (f32x2){pz[0] * SRZ, pz[1] * SRZ};
-        Wn[k] = (f32x2){pn[0] * SN, pn[1] * SN};
-    }
-    const float wir = a.w_ih[u] * SRZ, wiz = a.w_ih[kH + u] * SRZ, win = a.w_ih[2 * kH + u] * SN;
-    const float br = (a.b_ih[u] + a.b_hh[u]) * SRZ, bz = (a.b_ih[kH + u] + a.b_hh[kH + u]) * SRZ;
-    const float bin_ = a.b_ih[2 * kH + u] * SN, bhn = a.b_hh[2 * kH + u] * SN;
-    const float bo = a.b_o ? a.b_o[0] : 0.0f;
-    const float wo_l = a.w_o[l];
+    Lane c;
+    c.load(a, u, kq);
+    Head hd;
+    hd.load(a, l);
     float hold = a.h_state ? a.h_state[s * kH + u] : 0.0f;
 
     if (kq == 0 && !head_wave) hb[0][u] = hold;
@@ -113,51 +61,25 @@ __global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__
 
     const float *const hq_rd = &hb[0][16 * kq];
     float *const hu_wr = &hb[0][u];
-    auto step = [&](const int ph, const int tb, const int64_t t, auto par_c) {
+    auto step = [&](const int ph, auto par_c, const int tb) {
         constexpr int par = decltype(par_c)::value;
         if (head_wave) {
-            const float yv = wave_sum_lane63(wo_l * hb[par][l]) + bo;
-            if (l == 63) { if (ph > 0) yt[tb][ph - 1] = yv; else yt[tb ^ 1][LT - 1] = yv; }
+            hd.sample_before(hb[par], l, yt, tb, ph);
             lds_barrier();
             return;
         }
         const f32x4 h0 = *(const f32x4 *)(hq_rd + par * kH + 0), h1 = *(const f32x4 *)(hq_rd + par * kH + 4);
         const f32x4 h2 = *(const f32x4 *)(hq_rd + par * kH + 8), h3 = *(const f32x4 *)(hq_rd + par * kH + 12);
         const float x = xt[tb][ph];
-        const f32x2 hq[8] = {{h0[0], h0[1]}, {h0[2], h0[3]}, {h1[0], h1[1]}, {h1[2], h1[3]},
-                             {h2[0], h2[1]}, {h2[2], h2[3]}, {h3[0], h3[1]}, {h3[2], h3[3]}};
-        f32x2 ar0 = Wr[0] * hq[0], ar1 = Wr[1] * hq[1], az0 = Wz[0] * hq[0], az1 = Wz[1] * hq[1];
-        f32x2 an0 = Wn[0] * hq[0], an1 = Wn[1] * hq[1];
-#pragma unroll
-        for (int k = 2; k < 8; k += 2) {
-            ar0 = __builtin_elementwise_fma(Wr[k], hq[k], ar0); ar1 = __builtin_elementwise_fma(Wr[k + 1], hq[k + 1], ar1);
-            az0 = __builtin_elementwise_fma(Wz[k], hq[k], az0); az1 = __builtin_elementwise_fma(Wz[k + 1], hq[k + 1], az1);
-            an0 = __builtin_elementwise_fma(Wn[k], hq[k], an0); an1 = __builtin_elementwise_fma(Wn[k + 1], hq[k + 1], an1);
-        }
-        const f32x2 sr = ar0 + ar1, sz = az0 + az1, sn = an0 + an1;
-        const float qr = quad_add<0x4E>(quad_add<0xB1>(sr[0] + sr[1]));
-        const float qz = quad_add<0x4E>(quad_add<0xB1>(sz[0] + sz[1]));
-        const float qn = quad_add<0x4E>(quad_add<0xB1>(sn[0] + sn[1]));
-        const float cr = __builtin_fmaf(wir, x, br), cz = __builtin_fmaf(wiz, x, bz), gi = __builtin_fmaf(win, x, bin_);
-        const float pr_ = cr + qr, pz_ = cz + qz, gh = bhn + qn;
-        const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pr_));
-        const float z = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pz_));
-        const float en = __builtin_amdgcn_exp2f(__builtin_fmaf(r, gh, gi));
-        const float n = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + en), 1.0f);
-        // saves of step t: lane kq writes row kq (h_{t-1}, r, z, n), lane 0 of the quad also row 4 (gh_n, unscaled)
-        float *wt = stg_l + (int)(t & (SC - 1)) * (NSAVE * kH);
+        float r, z, n, gh;
+        gates(c, h0, h1, h2, h3, x, r, z, n, gh);
+        // saves of the step (SC divides the tile): lane kq writes row kq (h_{t-1}, r, z, n), lane 0 of the quad also row 4 (gh_n, unscaled)
+        float *wt = stg_l + (ph & (SC - 1)) * (NSAVE * kH);
         wt[0] = kq == 0 ? hold : kq == 1 ? r : kq == 2 ? z : n;
         if (kq == 0) wt[(NSAVE - 1) * kH] = gh * INV_SN;
         hold = __builtin_fmaf(z, hold - n, n);
         hu_wr[(par ^ 1) * kH] = hold;
         lds_barrier();
-    };
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    auto run = [&](int p0, const int p1, const int tb, const int64_t tile0) {
-        if (p0 < p1 && (p0 & 1)) { step(p0, tb, tile0 + p0, P1{}); ++p0; }
-        for (; p0 + 1 < p1; p0 += 2) { step(p0, tb, tile0 + p0, P0{}); step(p0 + 1, tb, tile0 + p0 + 1, P1{}); }
-        if (p0 < p1) step(p0, tb, tile0 + p0, P0{});
     };
 
     for (int64_t tile0 = 0; tile0 < T; tile0 += LT) {
@@ -166,9 +88,9 @@ __global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__
         for (int c0 = 0; c0 < ns; c0 += SC) {
             const int c1 = ns < c0 + SC ? ns : c0 + SC;
             if (c0 == 0) {
-                run(0, c1 < 3 ? c1 : 3, tb, tile0);
+                run(0, c1 < 3 ? c1 : 3, step, tb);
                 if (ns > 2 && tile0 >= LT && tid < LT) ys[tile0 - LT + tid] = yt[tb ^ 1][tid];      // previous y tile is complete
-                run(c1 < 3 ? c1 : 3, c1, tb, tile0);
+                run(c1 < 3 ? c1 : 3, c1, step, tb);
             } else {
                 // the next x tile into its buffer (read from step 0 of the next tile on), loaded and written here: a load kept in
                 // flight in a register across the steps (as gru_lat.hip does) made the compiler wait for it at every copy of that
@@ -177,7 +99,7 @@ __global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__
                     const int64_t nx = tile0 + LT + tid;
                     xt[tb ^ 1][tid] = nx < T ? xs[nx] : 0.0f;
                 }
-                run(c0, c1, tb, tile0);
+                run(c0, c1, step, tb);
             }
             // flush the stage: steps [c0, c1) are one contiguous run of the stream's workspace (the last step's barrier has
             // ordered every write to it); the barrier behind orders these reads before the next stage's writes
@@ -187,16 +109,7 @@ __global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__
             lds_barrier();
         }
     }
-    if (T > 0 && head_wave) {
-        const float yv = wave_sum_lane63(wo_l * hb[(int)(T & 1)][l]) + bo;
-        if (l == 63) yt[(int)(((T - 1) >> 8) & 1)][(int)((T - 1) & (LT - 1))] = yv;
-    }
-    __syncthreads();
-    const int64_t last0 = ((T - 1) >> 8) * LT;
-    if (T > 0 && tid < LT) {
-        if (last0 + tid < T) ys[last0 + tid] = yt[(last0 >> 8) & 1][tid];
-        if (last0 >= LT && (T - 1 - last0) < 2) ys[last0 - LT + tid] = yt[((last0 >> 8) & 1) ^ 1][tid];
-    }
+    finish(a, hd, hb, yt, head_wave);
     if (a.h_state && kq == 0 && !head_wave) a.h_state[s * kH + u] = hold;
 }
 
@@ -289,8 +202,6 @@ __global__ __launch_bounds__(256) void gru_train_bwd_kernel(const float *__restr
         const float q = quad_add<0x4E>(quad_add<0xB1>(p0 + p1));
         dh = __builtin_fmaf(g, z, q);
     };
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
     // steps in groups of PF (the ring slot and the LDS parity known at compile time: PF is even)
     int64_t t = T - 1;
     for (; t - (PF - 1) >= 0; t -= PF) {

@@ -34,17 +34,6 @@ hipError_t launch_resample_fir(const double *x, double *y, int64_t B, int64_t N,
 hipError_t launch_fir_f64(const double *x, double *y, int64_t B, int64_t N, const double *h, int taps, int clamp, hipStream_t stream);
 hipError_t launch_tcn(const float *params, int L, int C, int K, const int *dil, const float *x, float *y, int64_t B,
                       int64_t T, float *scratch, hipStream_t stream);
-int64_t train_grad_floats();
-hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, hipStream_t stream);
-hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float *x, int64_t xs, const float *ws, const float *dy,
-                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, hipStream_t stream);
-hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream);
-hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const double *sums2, const float *gout, double eps, float *dy,
-                           hipStream_t stream);
-hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2,
-                                 const float *gout, double eps, float *dy, hipStream_t stream);
-hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
-                            int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm
 
 namespace {

@@ -71,4 +71,16 @@ hipError_t launch_gru_lat(const GruArgs &a, hipStream_t stream);
 hipError_t launch_gru_small(const GruArgs &a, int H, hipStream_t stream);   // any H in [1, 1024] but 64
 hipError_t launch_gru_io(const GruArgs &a, int H, int I, int O, hipStream_t stream);   // any input_size / output_size (gru_small.hip)
 hipError_t launch_debug_transpose(const float *in, float *out, hipStream_t stream);
+// training (gru_train.hip)
+int64_t train_grad_floats();
+hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, hipStream_t stream);
+hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float *x, int64_t xs, const float *ws, const float *dy,
+                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, hipStream_t stream);
+hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream);
+hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const double *sums2, const float *gout, double eps, float *dy,
+                           hipStream_t stream);
+hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2,
+                                 const float *gout, double eps, float *dy, hipStream_t stream);
+hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
+                            int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm

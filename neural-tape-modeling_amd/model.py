@@ -119,13 +119,20 @@ class _GRUHead(torch.nn.Module):
         self.hidden = None
         self._warm = None          # (key, state tensors) of the last warm_start() from a fresh state
 
-    def _hidden_for(self, B, device):
+    def _h0(self, B, device):
+        """The initial hidden state (B,H) fp32 on `device`: zeros when none is carried, else a VIEW of self.hidden that stays in
+        its graph (the training paths chain dh0 to the previous window through it)."""
         H = self.hidden_size
         if self.hidden is None:
-            return torch.zeros(1, B, H, device=device, dtype=torch.float32)
+            return torch.zeros(B, H, device=device, dtype=torch.float32)
         if tuple(self.hidden.shape) != (1, B, H):
             raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
-        return self.hidden.to(device=device, dtype=torch.float32).clone()
+        return self.hidden.to(device=device, dtype=torch.float32).reshape(B, H)
+
+    def _hidden_for(self, B, device):
+        """_h0 as the (1,B,H) tensor of its own that the inference kernels update in place."""
+        h = self._h0(B, device)
+        return (h if self.hidden is None else h.clone()).view(1, B, self.hidden_size)
 
     def _one_launch(self):
         """Whether a loss entry forms its sums in the GRU's own C call (where the matrix-pipe kernel runs they ride in the
@@ -264,14 +271,8 @@ class RNN(_GRUHead):
                                "and the hidden state only (no caller of the reference needs d/dx)")
         xbt = _as_bt(x, "RNN.forward")
         B, T = xbt.shape
-        if self.hidden is None:
-            h0 = torch.zeros(B, self.hidden_size, device=xbt.device, dtype=torch.float32)
-        elif tuple(self.hidden.shape) != (1, B, self.hidden_size):
-            raise RuntimeError(f"Expected hidden size (1, {B}, {self.hidden_size}), got {list(self.hidden.shape)}")
-        else:
-            h0 = self.hidden.reshape(B, self.hidden_size)
         g, o = self.GRU, self.output
-        y, h = training.GRUTrainStep.apply(xbt, h0, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, o.weight, o.bias)
+        y, h = training.GRUTrainStep.apply(xbt, self._h0(B, xbt.device), g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, o.weight, o.bias)
         self.hidden = h.view(1, B, self.hidden_size)
         return y.view(B, 1, T)
 
@@ -481,25 +482,35 @@ class TimeVaryingDelayLine(torch.nn.Module):
             self._err.zero_()
             raise AssertionError("max_delay >= max(dt) violated")
 
-    def _run(self, xbt, dbt, warmup):
-        """[B,T] fp32 -> y [B,T]; the carried buffer is updated IN PLACE (no clone, no scratch, no host sync)."""
-        B, T = xbt.shape
+    def _prepare(self, B, device):
+        """Before every launch for batch B on `device`: the buffer is (B,1,max_delay), fp32, contiguous and there, and so is
+        the violation flag; the buffer no longer counts as fresh.  -> max_delay as an int."""
         D = int(self.max_delay)
         if self.buffer.shape[0] != B or self.buffer.shape[2] != D:
             raise RuntimeError(f"Sizes of tensors must match: buffer {list(self.buffer.shape)} vs input batch {B}")
-        if self.buffer.device != xbt.device or self.buffer.dtype != torch.float32 or not self.buffer.is_contiguous():
-            self.buffer = self.buffer.to(device=xbt.device, dtype=torch.float32).contiguous()
-        if self._err is None or self._err.device != xbt.device:
-            self._err = torch.zeros(1, device=xbt.device, dtype=torch.int32)
-        y = torch.empty_like(xbt)
+        if self.buffer.device != device or self.buffer.dtype != torch.float32 or not self.buffer.is_contiguous():
+            self.buffer = self.buffer.to(device=device, dtype=torch.float32).contiguous()
+        if self._err is None or self._err.device != device:
+            self._err = torch.zeros(1, device=device, dtype=torch.int32)
         self._fresh = False
-        rc = _lib.lib().ntm_delay_forward(ptr(xbt), ptr(dbt), ptr(y), B, T, ptr(self.buffer), D, int(bool(warmup)),
-                                          ptr(self._err), _lib.current_stream())
-        _lib.check(rc, "ntm_delay_forward")
+        return D
+
+    def _launched(self):
+        """After every launch: look at the violation flag now, or note that a deferred launch is waiting for that."""
         if not self.defer_check:
             self.raise_if_violated()
         else:
             self._unchecked = True
+
+    def _run(self, xbt, dbt, warmup):
+        """[B,T] fp32 -> y [B,T]; the carried buffer is updated IN PLACE (no clone, no scratch, no host sync)."""
+        B, T = xbt.shape
+        D = self._prepare(B, xbt.device)
+        y = torch.empty_like(xbt)
+        rc = _lib.lib().ntm_delay_forward(ptr(xbt), ptr(dbt), ptr(y), B, T, ptr(self.buffer), D, int(bool(warmup)),
+                                          ptr(self._err), _lib.current_stream())
+        _lib.check(rc, "ntm_delay_forward")
+        self._launched()
         return y
 
     @torch.no_grad()
@@ -586,6 +597,15 @@ class DiffDelRNN(_GRUHead):
             raise RuntimeError(f"{what}: DiffDelRNN training is not implemented for parameters on '{dev}': it runs on a HIP "
                                f"device only ({training.SUPPORTED_DIFFDEL})")
 
+    @staticmethod
+    def _bt_pair(x, del_traj):
+        """(x, del_traj) (N,1,T) -> their [B,T] fp32 forms, of one shape."""
+        xbt = _as_bt(x, "DiffDelRNN.forward")
+        dbt = _as_bt(del_traj, "DiffDelRNN.forward")
+        if dbt.shape != xbt.shape:
+            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        return xbt, dbt
+
     def _forward_train(self, x, del_traj, warmup):
         """forward() as graph nodes.  The new delay buffer is a fresh tensor (the warm-up's outputs in it stay in the graph of
         the first window); a delay above the buffer raises AssertionError (code/model.py:284) with the buffer as it was -- the
@@ -594,36 +614,16 @@ class DiffDelRNN(_GRUHead):
         if x.requires_grad or del_traj.requires_grad:
             raise RuntimeError("DiffDelRNN.forward: the input or the delay trajectory requires grad; the training kernels give "
                                f"gradients for the parameters, the hidden state and the delay buffer only ({training.SUPPORTED_DIFFDEL})")
-        xbt = _as_bt(x, "DiffDelRNN.forward")
-        dbt = _as_bt(del_traj, "DiffDelRNN.forward")
-        if dbt.shape != xbt.shape:
-            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        xbt, dbt = self._bt_pair(x, del_traj)
         B, T = xbt.shape
-        H = self.hidden_size
         dl = self.diffdel
-        D = int(dl.max_delay)
-        if dl.buffer.shape[0] != B or dl.buffer.shape[2] != D:
-            raise RuntimeError(f"Sizes of tensors must match: buffer {list(dl.buffer.shape)} vs input batch {B}")
-        if dl.buffer.device != xbt.device or dl.buffer.dtype != torch.float32:
-            dl.buffer = dl.buffer.to(device=xbt.device, dtype=torch.float32)
-        if dl._err is None or dl._err.device != xbt.device:
-            dl._err = torch.zeros(1, device=xbt.device, dtype=torch.int32)
-        if self.hidden is None:
-            h0 = torch.zeros(B, H, device=xbt.device, dtype=torch.float32)
-        elif tuple(self.hidden.shape) != (1, B, H):
-            raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
-        else:
-            h0 = self.hidden.reshape(B, H)
+        dl._prepare(B, xbt.device)
         g = self.GRU
-        pre, h = training.GRUTrainStep.apply(xbt, h0, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0,
-                                             self.output.weight, None)
-        self.hidden = h.view(1, B, H)
+        pre, h = training.GRUTrainStep.apply(xbt, self._h0(B, xbt.device), g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0,
+                                             g.bias_hh_l0, self.output.weight, None)
+        self.hidden = h.view(1, B, self.hidden_size)
         y, buf = training.DelayLineStep.apply(pre, dl.buffer, dbt, bool(warmup), dl._err)
-        dl._fresh = False
-        if not dl.defer_check:
-            dl.raise_if_violated()
-        else:
-            dl._unchecked = True
+        dl._launched()               # raises BEFORE the buffer moves on: a violating call leaves it as it was
         dl.buffer = buf
         return y.view(B, 1, T), pre.view(B, 1, T)
 
@@ -631,10 +631,7 @@ class DiffDelRNN(_GRUHead):
         """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424).  `_events`: three torch.cuda.Event objects
         recorded before the GRU launch, between it and the delay pass, and after (bench.py's per-kernel timing; with the
         fused step the middle one is recorded right behind the fused launch, ahead of the buffer update)."""
-        xbt = _as_bt(x, "DiffDelRNN.forward")
-        dbt = _as_bt(del_traj, "DiffDelRNN.forward")
-        if dbt.shape != xbt.shape:
-            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        xbt, dbt = self._bt_pair(x, del_traj)
         B, T = xbt.shape
         if self._one_launch(losses=False):
             y, pre = self._fused_step(xbt, dbt, warmup, _events)
@@ -719,19 +716,12 @@ class DiffDelRNN(_GRUHead):
         the DCPreESR sums (ntm_diffdel_gru_forward_losses) of the delayed output.  -> (y, pre_d, *sums)."""
         B, T = xbt.shape
         dl = self.diffdel
-        D = int(dl.max_delay)
         _require_hip(self.GRU.weight_hh_l0, "model parameters (call .to('cuda'))")
-        if dl.buffer.shape[0] != B or dl.buffer.shape[2] != D:
-            raise RuntimeError(f"Sizes of tensors must match: buffer {list(dl.buffer.shape)} vs input batch {B}")
-        if dl.buffer.device != xbt.device or dl.buffer.dtype != torch.float32 or not dl.buffer.is_contiguous():
-            dl.buffer = dl.buffer.to(device=xbt.device, dtype=torch.float32).contiguous()
-        if dl._err is None or dl._err.device != xbt.device:
-            dl._err = torch.zeros(1, device=xbt.device, dtype=torch.int32)
+        D = dl._prepare(B, xbt.device)
         h = self._hidden_for(B, xbt.device)
         y, pre = torch.empty_like(xbt), torch.empty_like(xbt)
         sums = tuple(torch.empty(B, 2, device=xbt.device, dtype=torch.float64)
                      for _ in range(0 if tbt is None else 1 if dcp_R is None else 2))
-        dl._fresh = False
         g, L = self.GRU, _lib.lib()
         args = (ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(self.output.weight),
                 self.hidden_size, ptr(xbt), ptr(dbt), ptr(y), ptr(pre), B, T, ptr(h), ptr(dl.buffer), D)
@@ -750,10 +740,7 @@ class DiffDelRNN(_GRUHead):
             _events[1].record()
             _events[2].record()
         self.hidden = h
-        if not dl.defer_check:
-            dl.raise_if_violated()
-        else:
-            dl._unchecked = True
+        dl._launched()
         return (y, pre) + sums
 
     @torch.no_grad()

@@ -2,7 +2,8 @@
 no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
 
   * GRUTrainStep: one stateful forward call of the GRU + head as a graph node.  forward = ntm_gru_train_forward (the step of the
-    low-latency kernel, bit-identical to kernel_variant "lat", plus the activations saved for BPTT); backward =
+    low-latency kernel -- the same code, csrc/gru_lat_step.h, so the same bits as kernel_variant "lat" -- plus the activations
+    saved for BPTT); backward =
     ntm_gru_train_backward (one workgroup per stream) + ntm_gru_train_reduce (fixed-order sum over the streams): the gradients of
     the six parameters and of the initial state h0.  dh0 is what chains a window to the one before it (the warm-up of
     train_epoch is such a node: code/model.py:122 runs it with grad enabled and does not detach it).
