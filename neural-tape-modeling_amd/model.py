@@ -952,6 +952,14 @@ MRSTFT_FFT_SIZES, MRSTFT_HOP_SIZES, MRSTFT_WIN_LENGTHS = (1024, 2048, 512), (120
 STFT_EPS = 1e-8
 
 
+def _n_frames(T, skip, hop, what):
+    """Frames of a centred STFT over samples [skip, T): 1 + (T - skip) // hop.  A hop below 1 is refused here with the
+    library's own error type: the division would otherwise raise ZeroDivisionError before the library sees the call."""
+    if int(hop) <= 0:
+        raise _lib.NtmError(f"{what}: bad hop or win_length (hop = {hop})")
+    return 1 + (T - int(skip)) // int(hop)
+
+
 @torch.no_grad()
 def stft_sums(output, target, skip=0, n_fft=1024, hop=120, win_length=600, eps=STFT_EPS):
     """Per-stream sums of one STFT resolution over samples [skip, T) (ntm_stft_sums):
@@ -960,7 +968,7 @@ def stft_sums(output, target, skip=0, n_fft=1024, hop=120, win_length=600, eps=S
     y = _as_bt(output, "stft_sums")
     t = _as_bt(target, "stft_sums")
     B, T = y.shape
-    n_frames = 1 + (T - int(skip)) // int(hop)
+    n_frames = _n_frames(T, skip, hop, "stft_sums")
     # enough workgroups to fill 256 CUs a few times over, at least ~8 frames per wave
     chunks = max(1, min(-(-2048 // max(B, 1)), n_frames // 32))
     out = torch.empty(B, 4 * chunks, 4, device=y.device, dtype=torch.float64)
@@ -1016,7 +1024,7 @@ def spec_sums(output, target, skip=0, n_fft=1024, hop=None, win_length=None, log
     y = _as_bt(output, "spec_sums")
     t = _as_bt(target, "spec_sums")
     B, T = y.shape
-    n_frames = 1 + (T - int(skip)) // hop
+    n_frames = _n_frames(T, skip, hop, "spec_sums")
     chunks = max(1, min(-(-2048 // max(B, 1)), n_frames // 32))
     out = torch.empty(B, 4 * chunks, 4, device=y.device, dtype=torch.float64)
     rc = _lib.lib().ntm_spec_sums(ptr(y), ptr(t), B, T, int(skip), int(n_fft), hop, win_length, float(log_floor), chunks,
@@ -1044,7 +1052,7 @@ def mel_sums(output, target, skip=0, n_fft=2048, hop=None, n_mels=160, sampling_
         first, start, w = mel_filterbank_sparse(sampling_rate, n_fft, n_mels)
         _MEL_CACHE[key] = tuple(torch.from_numpy(a).to(y.device) for a in (first, start, w))
     first, start, w = _MEL_CACHE[key]
-    n_frames = 1 + (T - int(skip)) // hop
+    n_frames = _n_frames(T, skip, hop, "mel_sums")
     chunks = max(1, min(-(-2048 // max(B, 1)), n_frames // 32))
     out = torch.empty(B, 4 * chunks, 4, device=y.device, dtype=torch.float64)
     rc = _lib.lib().ntm_mel_sums(ptr(y), ptr(t), B, T, int(skip), int(n_fft), hop, int(n_fft), float(log_floor), chunks,

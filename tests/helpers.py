@@ -44,6 +44,90 @@ def validate_batches(seed, n_batches, b, t, fs):
     return out
 
 
+def _torch_power(x, n_fft, hop, win, dtype):
+    """|torch.stft|^2 of a (B, L) array in `dtype` (centred, reflect padding, periodic Hann of `win` samples) -> torch
+    tensor (B, bins, frames) in `dtype`."""
+    import torch
+    X = torch.stft(torch.from_numpy(np.ascontiguousarray(x)).to(dtype), n_fft, hop, win,
+                   torch.hann_window(win, dtype=dtype), return_complex=True)
+    return X.real ** 2 + X.imag ** 2
+
+
+def torch_stft_sums(y, t, skip, n_fft, hop, win, eps=1e-8, dtype=None):
+    """The four per-stream sums of ntm_stft_sums / oracle.stft_sums from `torch.stft` and the auraloss formula that
+    tools/make_goldens_stft.py uses (mag = sqrt(clamp(re^2 + im^2, eps))), with the spectra and the per-cell terms in
+    `dtype` (default float64) and the sums over the cells in float64 -> ((B, 4) float64, cells per stream)."""
+    import torch
+    dtype = dtype or torch.float64
+    my = torch.sqrt(torch.clamp(_torch_power(y[:, skip:], n_fft, hop, win, dtype), min=eps))
+    mt = torch.sqrt(torch.clamp(_torch_power(t[:, skip:], n_fft, hop, win, dtype), min=eps))
+    terms = ((mt - my) ** 2, mt ** 2, (torch.log(my) - torch.log(mt)).abs(), (my - mt).abs())
+    return torch.stack([c.double().sum(dim=(1, 2)) for c in terms], dim=1).numpy(), my.shape[1] * my.shape[2]
+
+
+def torch_spec_sums(y, t, skip, n_fft, hop=None, win=None, floor=1e-5, dtype=None):
+    """The same for ntm_spec_sums / oracle.spec_sums (power spectrogram: |P_y - P_t|, |log10 of the clamped powers|,
+    P_t, P_y)."""
+    import torch
+    dtype = dtype or torch.float64
+    hop = n_fft // 4 if hop is None else hop
+    win = n_fft if win is None else win
+    py = _torch_power(y[:, skip:], n_fft, hop, win, dtype)
+    pt = _torch_power(t[:, skip:], n_fft, hop, win, dtype)
+    terms = ((py - pt).abs(), (torch.log10(torch.clamp(py, min=floor)) - torch.log10(torch.clamp(pt, min=floor))).abs(), pt, py)
+    return torch.stack([c.double().sum(dim=(1, 2)) for c in terms], dim=1).numpy(), py.shape[1] * py.shape[2]
+
+
+def torch_mel_sums(y, t, skip, n_fft, hop, basis, floor=1e-5, dtype=None):
+    """The same for ntm_mel_sums / oracle.mel_sums: the power spectrogram (window = n_fft) projected by `basis`
+    [n_mels, 1 + n_fft/2], used as it is given."""
+    import torch
+    dtype = dtype or torch.float64
+    hop = n_fft // 4 if hop is None else hop
+    bm = torch.from_numpy(np.asarray(basis)).to(dtype)
+    my = torch.matmul(bm, _torch_power(y[:, skip:], n_fft, hop, n_fft, dtype))          # (B, mels, frames)
+    mt = torch.matmul(bm, _torch_power(t[:, skip:], n_fft, hop, n_fft, dtype))
+    terms = ((my - mt).abs(), (torch.log10(torch.clamp(my, min=floor)) - torch.log10(torch.clamp(mt, min=floor))).abs(), mt, my)
+    return torch.stack([c.double().sum(dim=(1, 2)) for c in terms], dim=1).numpy(), my.shape[1] * my.shape[2]
+
+
+def noise_pair(seed, B, T, amp=0.3):
+    """Two UNRELATED white-noise signals (B, T) float32: nothing cancels in the difference terms of the spectral sums."""
+    rng = np.random.default_rng(seed)
+    return ((amp * rng.standard_normal((B, T))).astype(np.float32), (amp * rng.standard_normal((B, T))).astype(np.float32))
+
+
+# frames per workgroup and iteration of stft_sums_kernel (4 waves x 64/SUB frame slots)
+STFT_FRAMES_PER_ITERATION = {64: 16, 128: 8, 256: 4, 512: 4, 1024: 4, 2048: 4}
+
+
+def structural_cases(n_fft):
+    """[(L, hop, win, skip, B)]: every frame count of {1, 2, F-1, F, F+1, 2F+1} twice -- with a hop that divides L = T - skip
+    and one that does not -- from the hops {n_fft/4, n_fft/4+1, n_fft+3} (enlarged where L would fall below the minimum:
+    two frames at the minimum length is hop = L); the minimum length and n_fft+1 with the short hops (and hop 1 for the
+    frames of 64 / 128 samples: 34 ... 66 frames); one frame by hop = L+1.  Windows, skips and batch sizes rotate with
+    coprime periods, so every window meets every skip and both batch sizes over the six frame sizes and three modes."""
+    F, lmin = STFT_FRAMES_PER_ITERATION[n_fft], n_fft // 2 + 1
+    hops = (n_fft // 4, n_fft // 4 + 1, n_fft + 3)
+    lh, k = [], 0
+    for nf in (1, 2, F - 1, F, F + 1, 2 * F + 1):
+        for divides in (True, False):
+            if nf == 1:
+                L, hop = (lmin, lmin + 1) if divides else (n_fft + 1, n_fft + 3)
+            else:
+                hop = max(hops[k % 3], -(-lmin // (nf - 1)))
+                k += 1
+                L = (nf - 1) * hop + (0 if divides else hop // 2)
+            assert 1 + L // hop == nf and L >= lmin and (nf == 1 or (L % hop == 0) == divides)
+            lh.append((L, hop))
+    lh += [(lmin, n_fft // 4), (lmin, n_fft // 4 + 1), (n_fft + 1, n_fft // 4), (n_fft + 1, n_fft // 4 + 1), (n_fft + 1, n_fft + 2)]
+    if n_fft <= 128:
+        lh += [(lmin, 1)] + ([(n_fft + 1, 1)] if n_fft == 64 else [])
+    wins, skips, Bs = (2, 3, n_fft // 2 - 1, n_fft - 1, n_fft), (0, 1, 37), (1, 3)
+    off = list(STFT_FRAMES_PER_ITERATION).index(n_fft)
+    return [(L, hop, wins[(j + off) % 5], skips[(j + off) % 3], Bs[(j + off) % 2]) for j, (L, hop) in enumerate(lh)]
+
+
 def bench_record(stdout, detail=True):
     """bench.py's output contract: exactly ONE JSON line on stdout, the last one, shorter than 4 KB (the driver's parser lost
     round 5's 20 KB line), naming the detail file that holds the full record.  -> (compact line dict, full record dict);
