@@ -407,6 +407,43 @@ int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, flo
                        double eps, float *dy, void *stream);
 
 /*
+ * ---- R replicas of that training configuration in one launch each (additions within ABI version 9): what an array of
+ * independent runs of one configuration (scripts/sbatch-train-exp1a.sh:7-15, --array=0-2) needs on one device.  The streams
+ * are stacked replica-major -- stream s of R * Bper belongs to replica s / Bper -- and the parameters arrive as contiguous
+ * stacks: w_ih [R,192,1], w_hh [R,192,64], b_ih, b_hh [R,192], w_o [R,1,64], b_o [R,1] (may be null).  Everything is per
+ * stream and free of atomics, so every replica's outputs are bit-identical to those of the single-model entry point above
+ * called on that replica's slice with that replica's parameters.  R and Bper must be positive (R <= 65535).
+ */
+
+/* ntm_gru_train_forward for R replicas: x, y, h_state [R*Bper, .], ws = ntm_gru_train_workspace_floats(R * Bper, T). */
+int ntm_gru_train_forward_replicas(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                                   const float *b_o, const float *x, float *y, int64_t R, int64_t Bper, int64_t T,
+                                   int64_t x_stride_b, int64_t y_stride_b, float *h_state, float *ws, void *stream);
+
+/* ntm_gru_train_backward for R replicas: dh0 [R*Bper,64] (may be null), part [R*Bper, NTM_TRAIN_GRAD_FLOATS]. */
+int ntm_gru_train_backward_replicas(const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b, const float *ws,
+                                    const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t R, int64_t Bper, int64_t T,
+                                    float *dh0, float *part, void *stream);
+
+/* grad[R, NTM_TRAIN_GRAD_FLOATS]: row r = the Bper rows of replica r added in stream order in fp64 (ntm_gru_train_reduce's order). */
+int ntm_gru_train_reduce_replicas(const float *part, int64_t R, int64_t Bper, float *grad, void *stream);
+
+/*
+ * sums2[R,2] fp64 from the per-stream rows of ntm_esr_sums (rows [R*Bper, splits, 2]) or ntm_esr_dcpre_sums (splits = 1):
+ * per replica the `splits` (<= 255) partial rows of each stream, then the Bper stream sums, both in the fixed order given in
+ * csrc/gru_train.hip -- the order in which ESRLoss / DCPreESR add them for one model, so the same bits.
+ */
+int ntm_loss_sums_replicas(const double *rows, int64_t R, int64_t Bper, int splits, double *sums2, void *stream);
+
+/* ntm_esr_grad for R losses: every element takes sums2[r], gout[r] and n = Bper T of its replica; y, t, dy [R*Bper, T] contiguous. */
+int ntm_esr_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, const double *sums2, const float *gout,
+                          double eps, float *dy, void *stream);
+
+/* ntm_esr_dcpre_grad for R losses (pole: the DC blocker's R). */
+int ntm_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, float pole, const double *sums2,
+                                const float *gout, double eps, float *dy, void *stream);
+
+/*
  * Adjoint of the time-varying fractional delay line (ntm_delay_forward) over one call of B streams of L samples with a buffer of
  * D samples (the backward of DiffDelRNN.train_epoch's delay step, code/model.py:269-320,456-496).  With z = [buffer, x] the
  * forward is y[n] = sum_m w_m(n) z[D + n - m] over the taps m in {k+1, k}, k = floor(d[n]), that it counts, and the new buffer

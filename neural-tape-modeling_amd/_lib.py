@@ -59,6 +59,13 @@ _SIGNATURES = {
     "ntm_esr_grad": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "ntm_esr_dcpre_grad": (_int, [_vp, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "ntm_delay_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _vp]),
+    # R replicas per launch (additions within ABI version 9)
+    "ntm_gru_train_forward_replicas": (_int, [_vp] * 8 + [_i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "ntm_gru_train_backward_replicas": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "ntm_gru_train_reduce_replicas": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "ntm_loss_sums_replicas": (_int, [_vp, _i64, _i64, _int, _vp, _vp]),
+    "ntm_esr_grad_replicas": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "ntm_esr_dcpre_grad_replicas": (_int, [_vp, _vp, _i64, _i64, _i64, ctypes.c_float, _vp, _vp, ctypes.c_double, _vp, _vp]),
 }
 TRAIN_GRAD_FLOATS = 12929   # include/ntm.h NTM_TRAIN_GRAD_FLOATS: w_ih | w_hh | b_ih | b_hh | w_o | b_o of GRU(1, 64) + Linear(64, 1)
 

@@ -28,10 +28,20 @@ static_assert(NGRAD == 12929, "w_ih + w_hh + b_ih + b_hh + w_o + b_o of GRU(1, 6
 // for its completion before the step's registers were reused: a store round trip inside the recurrence, every step.  The
 // flush's stores are waited for the same way, in the first step after the flush: one round trip per SC steps.)
 constexpr int SC = 32;                   // steps per LDS stage of the saves (divides the tile, 40 KB)
-
-__global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__restrict__ ws)
+//
+// REP (the replica entry points): the streams are stacked replica-major, stream s belongs to replica s / bper, and the six
+// parameter pointers are the [R, ...] stacks -- the workgroup moves them to its replica's slice before the weight load (a scalar
+// division and six scalar adds, once); everything behind that is the same code.  REP = false reads no bper.
+template <bool REP>
+__global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__restrict__ ws, const unsigned bper)
 {
 #pragma clang fp contract(off)
+    if constexpr (REP) {
+        const size_t rep = blockIdx.x / bper;
+        a.w_ih += rep * (3 * kH); a.w_hh += rep * (3 * kH * kH); a.b_ih += rep * (3 * kH); a.b_hh += rep * (3 * kH);
+        a.w_o += rep * kH;
+        if (a.b_o) a.b_o += rep;
+    }
     __shared__ __attribute__((aligned(16))) float stg[SC * NSAVE * kH];   // saves of steps c0 .. c0 + SC - 1: [step][j][u]
     __shared__ __attribute__((aligned(16))) float hb[2][kH];
     __shared__ float xt[2][LT];
@@ -123,14 +133,20 @@ __global__ __launch_bounds__(320) void gru_train_fwd_kernel(GruArgs a, float *__
 // The saved values of step t - PF are loaded while step t runs (a register ring, PF steps deep), so the global latency sits
 // behind the recurrence; the barrier orders LDS only and does not drain them.
 constexpr int PF = 4;
-
+// REP: as in the forward -- w_hh and w_o are the [R, ...] stacks and the workgroup of stream s reads replica s / bper's.
+template <bool REP>
 __global__ __launch_bounds__(256) void gru_train_bwd_kernel(const float *__restrict__ w_hh, const float *__restrict__ w_o,
                                                              const float *__restrict__ x, int64_t xs, const float *__restrict__ ws,
                                                              const float *__restrict__ dy, int64_t dys,
                                                              const float *__restrict__ dh_T, int64_t T, float *__restrict__ dh0,
-                                                             float *__restrict__ part)
+                                                             float *__restrict__ part, const unsigned bper)
 {
 #pragma clang fp contract(off)
+    if constexpr (REP) {
+        const size_t rep = blockIdx.x / bper;
+        w_hh += rep * (3 * kH * kH);
+        w_o += rep * kH;
+    }
     __shared__ __attribute__((aligned(16))) float ab[2][3][kH];       // a_r, a_z, a_nh of the step, by step parity
 
     const int tid = threadIdx.x, l = tid & 63;
@@ -236,6 +252,20 @@ __global__ __launch_bounds__(256) void gru_train_reduce_kernel(const float *__re
     grad[e] = (float)acc;
 }
 
+// The same for R replicas of bper streams each (grid row = replica): every entry adds its replica's bper rows in stream
+// order, so grad[r] has the bits gru_train_reduce_kernel gives on that replica's rows alone.
+__global__ __launch_bounds__(256) void gru_train_reduce_replicas_kernel(const float *__restrict__ part, int64_t bper,
+                                                                        float *__restrict__ grad)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= NGRAD) return;
+    const int64_t r = blockIdx.y;
+    const float *p = part + r * bper * NGRAD;
+    double acc = 0.0;
+    for (int64_t b = 0; b < bper; ++b) acc += (double)p[b * NGRAD + e];
+    grad[r * NGRAD + e] = (float)acc;
+}
+
 // (d) Loss adjoints.  ESR (code/train.py:176): L = (S_e / n) / (S_t / n + eps) with whole-batch sums S (sums2 = [S_e, S_t],
 // fp64, from ntm_esr_sums) -> dL/dy = 2 (y - t) / (n (S_t / n + eps)), times the upstream gradient gout[0].
 __global__ __launch_bounds__(256) void esr_grad_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t N,
@@ -248,16 +278,40 @@ __global__ __launch_bounds__(256) void esr_grad_kernel(const float *__restrict__
         dy[i] = (float)(c * ((double)y[i] - (double)t[i]));
 }
 
+// R losses at once (grid row = replica): replica r's N = bper * T elements with ITS sums, upstream gradient and n -- per
+// element the arithmetic of esr_grad_kernel on that slice.
+__global__ __launch_bounds__(256) void esr_grad_replicas_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t N,
+                                                                const double *__restrict__ sums2, const float *__restrict__ gout,
+                                                                double eps, float *__restrict__ dy)
+{
+    const int64_t r = blockIdx.y;
+    const double n = (double)N;
+    const double c = (double)gout[r] * 2.0 / (n * (sums2[2 * r + 1] / n + eps));
+    const float *yr = y + r * N, *tr = t + r * N;
+    float *dr = dy + r * N;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
+        dr[i] = (float)(c * ((double)yr[i] - (double)tr[i]));
+}
+
 // DCPreESR (code/train.py:174): the same on the DC-blocked signals, f = (1 - z^-1)/(1 - R z^-1) from zero state.  With
 // e_f = f(y - t) and v = 2 e_f / (n (S_tf / n + eps)), dL/dy = f^T v: the anti-causal one-pole q[t] = v[t] + R q[t+1] followed
 // by the adjoint first difference dy[t] = q[t] - q[t+1].  One thread per stream, fp64 recursions; e_f is parked in dy between
 // the causal and the anti-causal pass.
+// REP: B = R replicas of bper streams; stream b takes sums2 [R,2], gout [R] and n = bper * T of replica b / bper.
+template <bool REP>
 __global__ __launch_bounds__(64) void esr_dcpre_grad_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t B,
                                                             int64_t T, float R, const double *__restrict__ sums2,
-                                                            const float *__restrict__ gout, double eps, float *__restrict__ dy)
+                                                            const float *__restrict__ gout, double eps, float *__restrict__ dy,
+                                                            const int64_t bper)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
+    if constexpr (REP) {
+        const int64_t rep = b / bper;
+        sums2 += 2 * rep;
+        gout += rep;
+        B = bper;
+    }
     const float *yb = y + b * T, *tb = t + b * T;
     float *db = dy + b * T;
     const double Rd = (double)R;
@@ -278,6 +332,66 @@ __global__ __launch_bounds__(64) void esr_dcpre_grad_kernel(const float *__restr
         db[i] = (float)(q - q1);
         q1 = q;
     }
+}
+
+// (d') The whole-batch sums of R losses from the per-stream rows of esr_sums_kernel / esr_dcpre_kernel: rows [R][bper][splits][2]
+// fp64 -> out [R][2].  The single-model losses add these rows with torch's sum() (model.py: the `splits` partial rows of a
+// stream, then the streams), and a loss of this path must have THEIR bits, so this kernel adds in the order torch's reduction
+// takes for a column of n < 256 values -- four accumulators, value i into accumulator i mod 4, then ((a0 + a1) + a2) + a3 (for
+// n <= 4 that is index order) -- and for n >= 256: thread y of 256 that way over values y, y + 256, ..., then the LDS tree
+// 128, 64, .., 1.  Fixed, free of atomics; tests/test_gpu_train_replicas.py holds it to the single-model losses bit for bit.
+__device__ __forceinline__ double sum4_strided(const double *p, const int64_t n, const int64_t stride)
+{
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    int64_t i = 0;
+    for (; i + 3 < n; i += 4) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] += p[(i + k) * stride];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (i + k < n) a[k] += p[(i + k) * stride];
+    return ((a[0] + a[1]) + a[2]) + a[3];
+}
+
+constexpr int LS_T = 256;
+
+__global__ __launch_bounds__(LS_T) void loss_sums_replicas_kernel(const double *__restrict__ rows, int64_t bper, int splits,
+                                                                  double *__restrict__ out)
+{
+    __shared__ double red[2][LS_T];
+    const int y = threadIdx.x;
+    const double *rr = rows + (int64_t)blockIdx.x * bper * splits * 2;
+    // the sum of stream b's partial rows, column c
+    auto stream = [&](const int64_t b, const int c) { return splits == 1 ? rr[2 * b + c] : sum4_strided(rr + b * splits * 2 + c, splits, 2); };
+    const int bh = bper < LS_T ? 1 : LS_T;
+    double v[2] = {0.0, 0.0};
+    if (y < bh) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            double a[4] = {0.0, 0.0, 0.0, 0.0};
+            int64_t i = y;
+            for (; i + 3 * bh < bper; i += 4 * bh) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) a[k] += stream(i + (int64_t)k * bh, c);
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (i + (int64_t)k * bh < bper) a[k] += stream(i + (int64_t)k * bh, c);
+            v[c] = ((a[0] + a[1]) + a[2]) + a[3];
+        }
+    }
+    if (bh == 1) {
+        if (y == 0) { out[2 * blockIdx.x] = v[0]; out[2 * blockIdx.x + 1] = v[1]; }
+        return;
+    }
+    red[0][y] = v[0]; red[1][y] = v[1];
+    __syncthreads();
+    for (int off = LS_T / 2; off > 0; off >>= 1) {
+        if (y < off) { red[0][y] += red[0][y + off]; red[1][y] += red[1][y + off]; }
+        __syncthreads();
+    }
+    if (y == 0) { out[2 * blockIdx.x] = red[0][0]; out[2 * blockIdx.x + 1] = red[1][0]; }
 }
 
 // (e) Adjoint of the time-varying fractional delay line (TimeVaryingDelayLine.forward, code/model.py:269-320) over one call.
@@ -396,24 +510,39 @@ hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newb
     return hipGetLastError();
 }
 
-hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, hipStream_t stream)
+// bper = 0: one model (a's parameters as they are); else a.B = R * bper streams of R stacked replicas
+hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, int64_t bper, hipStream_t stream)
 {
     if (a.B == 0) return hipSuccess;
-    hipLaunchKernelGGL(gru_train_fwd_kernel, dim3((unsigned)a.B), dim3(320), 0, stream, a, ws);
+    if (bper == 0) hipLaunchKernelGGL(gru_train_fwd_kernel<false>, dim3((unsigned)a.B), dim3(320), 0, stream, a, ws, 0u);
+    else hipLaunchKernelGGL(gru_train_fwd_kernel<true>, dim3((unsigned)a.B), dim3(320), 0, stream, a, ws, (unsigned)bper);
     return hipGetLastError();
 }
 
 hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float *x, int64_t xs, const float *ws, const float *dy,
-                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, hipStream_t stream)
+                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, int64_t bper,
+                                hipStream_t stream)
 {
     if (B == 0) return hipSuccess;
-    hipLaunchKernelGGL(gru_train_bwd_kernel, dim3((unsigned)B), dim3(256), 0, stream, w_hh, w_o, x, xs, ws, dy, dys, dh_T, T, dh0, part);
+    if (bper == 0)
+        hipLaunchKernelGGL(gru_train_bwd_kernel<false>, dim3((unsigned)B), dim3(256), 0, stream, w_hh, w_o, x, xs, ws, dy, dys, dh_T, T,
+                           dh0, part, 0u);
+    else
+        hipLaunchKernelGGL(gru_train_bwd_kernel<true>, dim3((unsigned)B), dim3(256), 0, stream, w_hh, w_o, x, xs, ws, dy, dys, dh_T, T,
+                           dh0, part, (unsigned)bper);
     return hipGetLastError();
 }
 
 hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream)
 {
     hipLaunchKernelGGL(gru_train_reduce_kernel, dim3((NGRAD + 255) / 256), dim3(256), 0, stream, part, B, grad);
+    return hipGetLastError();
+}
+
+hipError_t launch_gru_train_reduce_replicas(const float *part, int64_t R, int64_t bper, float *grad, hipStream_t stream)
+{
+    if (R == 0) return hipSuccess;
+    hipLaunchKernelGGL(gru_train_reduce_replicas_kernel, dim3((NGRAD + 255) / 256, (unsigned)R), dim3(256), 0, stream, part, bper, grad);
     return hipGetLastError();
 }
 
@@ -430,7 +559,36 @@ hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int6
                                  const float *gout, double eps, float *dy, hipStream_t stream)
 {
     if (B == 0 || T == 0) return hipSuccess;
-    hipLaunchKernelGGL(esr_dcpre_grad_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, y, t, B, T, R, sums2, gout, eps, dy);
+    hipLaunchKernelGGL(esr_dcpre_grad_kernel<false>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, y, t, B, T, R, sums2, gout,
+                       eps, dy, (int64_t)0);
+    return hipGetLastError();
+}
+
+// N = bper * T elements per replica
+hipError_t launch_esr_grad_replicas(const float *y, const float *t, int64_t R, int64_t N, const double *sums2, const float *gout,
+                                    double eps, float *dy, hipStream_t stream)
+{
+    if (R == 0 || N == 0) return hipSuccess;
+    const int64_t want = (N + 255) / 256, cap = (4096 + R - 1) / R;
+    hipLaunchKernelGGL(esr_grad_replicas_kernel, dim3((unsigned)(want < cap ? want : cap), (unsigned)R), dim3(256), 0, stream, y, t, N,
+                       sums2, gout, eps, dy);
+    return hipGetLastError();
+}
+
+hipError_t launch_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t bper, int64_t T, float pole,
+                                          const double *sums2, const float *gout, double eps, float *dy, hipStream_t stream)
+{
+    const int64_t B = R * bper;
+    if (B == 0 || T == 0) return hipSuccess;
+    hipLaunchKernelGGL(esr_dcpre_grad_kernel<true>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, y, t, B, T, pole, sums2, gout,
+                       eps, dy, bper);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_sums_replicas(const double *rows, int64_t R, int64_t bper, int splits, double *out, hipStream_t stream)
+{
+    if (R == 0) return hipSuccess;
+    hipLaunchKernelGGL(loss_sums_replicas_kernel, dim3((unsigned)R), dim3(LS_T), 0, stream, rows, bper, splits, out);
     return hipGetLastError();
 }
 

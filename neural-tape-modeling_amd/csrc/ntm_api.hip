@@ -630,7 +630,7 @@ int ntm_gru_train_forward(const float *w_ih, const float *w_hh, const float *b_i
     if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_gru_train_forward: at most 2^31 - 1 streams per call");
     if (x == y) return fail(NTM_EINVAL, "ntm_gru_train_forward: y must not alias x");
     ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, B, T, x_stride_b, y_stride_b, nullptr, 0, 0};
-    hipError_t e = ntm::launch_gru_train_fwd(a, ws, (hipStream_t)stream);
+    hipError_t e = ntm::launch_gru_train_fwd(a, ws, 0, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_forward");
 }
 
@@ -645,7 +645,7 @@ int ntm_gru_train_backward(const float *w_hh, const float *w_o, const float *x, 
     if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_gru_train_backward: at most 2^31 - 1 streams per call");
     static_assert(NTM_TRAIN_GRAD_FLOATS == 12929, "parameter count of GRU(1, 64) + Linear(64, 1)");
     if (ntm::train_grad_floats() != NTM_TRAIN_GRAD_FLOATS) return fail(NTM_EINVAL, "ntm_gru_train_backward: layout mismatch");
-    hipError_t e = ntm::launch_gru_train_bwd(w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, B, T, dh0, part, (hipStream_t)stream);
+    hipError_t e = ntm::launch_gru_train_bwd(w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, B, T, dh0, part, 0, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_backward");
 }
 
@@ -677,6 +677,86 @@ int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, flo
     if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: at most 2^31 - 1 streams per call");
     hipError_t e = ntm::launch_esr_dcpre_grad(y, t, B, T, R, sums2, gout, eps, dy, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_dcpre_grad");
+}
+
+// ---- R replicas of the training configuration in one launch each (stream s of R * Bper belongs to replica s / Bper)
+static int bad_replicas(const char *who, int64_t R, int64_t Bper)
+{
+    const std::string w(who);
+    if (R <= 0 || Bper <= 0) return fail(NTM_EINVAL, w + ": R and Bper must be positive");
+    if (R > 65535) return fail(NTM_EINVAL, w + ": at most 65535 replicas per call");
+    if (Bper > 0x7fffffff / R) return fail(NTM_EINVAL, w + ": at most 2^31 - 1 streams per call");
+    return NTM_OK;
+}
+
+int ntm_gru_train_forward_replicas(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                                   const float *b_o, const float *x, float *y, int64_t R, int64_t Bper, int64_t T,
+                                   int64_t x_stride_b, int64_t y_stride_b, float *h_state, float *ws, void *stream)
+{
+    if (int rc = bad_replicas("ntm_gru_train_forward_replicas", R, Bper)) return rc;
+    if (T < 0) return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: negative T");
+    if (T == 0) return NTM_OK;
+    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y || !ws)
+        return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: null pointer");
+    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: row stride below T");
+    if (x == y) return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: y must not alias x");
+    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, R * Bper, T, x_stride_b, y_stride_b, nullptr, 0, 0};
+    hipError_t e = ntm::launch_gru_train_fwd(a, ws, Bper, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_forward_replicas");
+}
+
+int ntm_gru_train_backward_replicas(const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b, const float *ws,
+                                    const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t R, int64_t Bper, int64_t T,
+                                    float *dh0, float *part, void *stream)
+{
+    if (int rc = bad_replicas("ntm_gru_train_backward_replicas", R, Bper)) return rc;
+    if (T < 0) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: negative T");
+    if (!w_hh || !w_o || !part || (T > 0 && (!x || !ws))) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: null pointer");
+    if (x_stride_b < T || (dy && dy_stride_b < T)) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: row stride below T");
+    if (ntm::train_grad_floats() != NTM_TRAIN_GRAD_FLOATS) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: layout mismatch");
+    hipError_t e = ntm::launch_gru_train_bwd(w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, R * Bper, T, dh0, part, Bper,
+                                             (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_backward_replicas");
+}
+
+int ntm_gru_train_reduce_replicas(const float *part, int64_t R, int64_t Bper, float *grad, void *stream)
+{
+    if (int rc = bad_replicas("ntm_gru_train_reduce_replicas", R, Bper)) return rc;
+    if (!grad || !part) return fail(NTM_EINVAL, "ntm_gru_train_reduce_replicas: null pointer");
+    hipError_t e = ntm::launch_gru_train_reduce_replicas(part, R, Bper, grad, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_reduce_replicas");
+}
+
+int ntm_loss_sums_replicas(const double *rows, int64_t R, int64_t Bper, int splits, double *sums2, void *stream)
+{
+    if (int rc = bad_replicas("ntm_loss_sums_replicas", R, Bper)) return rc;
+    if (splits < 1 || splits > 255) return fail(NTM_EINVAL, "ntm_loss_sums_replicas: splits must be in [1, 255]");
+    if (!rows || !sums2) return fail(NTM_EINVAL, "ntm_loss_sums_replicas: null pointer");
+    hipError_t e = ntm::launch_loss_sums_replicas(rows, R, Bper, splits, sums2, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_loss_sums_replicas");
+}
+
+int ntm_esr_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, const double *sums2, const float *gout,
+                          double eps, float *dy, void *stream)
+{
+    if (int rc = bad_replicas("ntm_esr_grad_replicas", R, Bper)) return rc;
+    if (T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_grad_replicas: bad size or eps");
+    if (T == 0) return NTM_OK;
+    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_grad_replicas: null pointer");
+    hipError_t e = ntm::launch_esr_grad_replicas(y, t, R, Bper * T, sums2, gout, eps, dy, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_grad_replicas");
+}
+
+int ntm_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, float pole, const double *sums2,
+                                const float *gout, double eps, float *dy, void *stream)
+{
+    if (int rc = bad_replicas("ntm_esr_dcpre_grad_replicas", R, Bper)) return rc;
+    if (T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad_replicas: bad size or eps");
+    if (!(pole >= 0.0f && pole < 1.0f)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad_replicas: R must be in [0,1)");
+    if (T == 0) return NTM_OK;
+    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad_replicas: null pointer");
+    hipError_t e = ntm::launch_esr_dcpre_grad_replicas(y, t, R, Bper, T, pole, sums2, gout, eps, dy, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_dcpre_grad_replicas");
 }
 
 int ntm_delay_backward(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,

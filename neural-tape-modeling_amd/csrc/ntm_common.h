@@ -73,9 +73,17 @@ hipError_t launch_gru_io(const GruArgs &a, int H, int I, int O, hipStream_t stre
 hipError_t launch_debug_transpose(const float *in, float *out, hipStream_t stream);
 // training (gru_train.hip)
 int64_t train_grad_floats();
-hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, hipStream_t stream);
+// bper = 0: one model; bper > 0: R stacked replicas of bper streams each, stream s reads the parameters of replica s / bper
+hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, int64_t bper, hipStream_t stream);
 hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float *x, int64_t xs, const float *ws, const float *dy,
-                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, hipStream_t stream);
+                                int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, int64_t bper,
+                                hipStream_t stream);
+hipError_t launch_gru_train_reduce_replicas(const float *part, int64_t R, int64_t bper, float *grad, hipStream_t stream);
+hipError_t launch_esr_grad_replicas(const float *y, const float *t, int64_t R, int64_t N, const double *sums2, const float *gout,
+                                    double eps, float *dy, hipStream_t stream);
+hipError_t launch_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t bper, int64_t T, float pole,
+                                          const double *sums2, const float *gout, double eps, float *dy, hipStream_t stream);
+hipError_t launch_loss_sums_replicas(const double *rows, int64_t R, int64_t bper, int splits, double *out, hipStream_t stream);
 hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream);
 hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const double *sums2, const float *gout, double eps, float *dy,
                            hipStream_t stream);

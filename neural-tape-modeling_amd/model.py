@@ -868,6 +868,263 @@ class DiffDelRNN(_GRUHead):
         return val_loss, examples
 
 
+class Replicas:
+    """R independent models of one supported training configuration -- R `RNN(1, 64, 1)` or R `DiffDelRNN(1, 64, 1)`, no skip
+    connection, all on the same HIP device -- trained side by side: what the reference runs as an array of jobs
+    (scripts/sbatch-train-exp1a.sh:7-15, --array=0-2, each at code/train.py:94's batch of 32, i.e. 32 of 256 CUs).  Per TBPTT
+    window there is ONE forward launch, ONE BPTT launch, ONE gradient reduction and ONE launch per loss kernel for all R; the
+    streams are stacked replica-major (training.GRUReplicaTrainStep).  Every replica ends up bit-identical to the same model
+    trained alone by its own train_epoch: everything on the path is per stream and free of atomics.
+    The models stay ordinary modules with their own parameters (the [R, ...] stacks are built inside the graph by torch.stack, so
+    autograd hands each model its own .grad): each state_dict() is the reference's checkpoint format, and each can validate()
+    or predict() on its own afterwards.  After every window each model's `hidden` (and delay buffer) is its slice of the group's.
+    Out of scope: replicas of different architectures, per-replica batch sizes, skip=True and hidden sizes other than 64 (the
+    single models refuse to train there too), several devices."""
+
+    def __init__(self, models):
+        models = list(models)
+        if not models:
+            raise ValueError("Replicas: at least one model")
+        kinds = {type(m) for m in models}
+        if kinds != {RNN} and kinds != {DiffDelRNN}:
+            raise TypeError("Replicas: all models must be RNN or all DiffDelRNN, got " + ", ".join(sorted(k.__name__ for k in kinds)))
+        if len({id(m) for m in models}) != len(models):
+            raise ValueError("Replicas: the same module appears twice; every replica needs a model of its own")
+        ps = [p for m in models for p in m.parameters()]
+        if len({id(p) for p in ps}) != len(ps):
+            raise ValueError("Replicas: the same parameter appears twice; every replica needs parameters of its own")
+        for m in models:
+            m._check_trainable("Replicas")
+        devs = {m.GRU.weight_hh_l0.device for m in models}
+        if len(devs) != 1:
+            raise ValueError(f"Replicas: all models must be on one device, got {sorted(map(str, devs))}")
+        self.models = models
+        self.diffdel = kinds == {DiffDelRNN}
+        self.device = devs.pop()
+        self.hidden = None                               # (1, R*Bper, 64) replica-major, in the graph between detach_hidden() calls
+        self._dl = TimeVaryingDelayLine(max_delay=models[0].max_delay) if self.diffdel else None
+
+    def __len__(self):
+        return len(self.models)
+
+    def _stacks(self):
+        """The six parameters as [R, ...] stacks, nodes of the graph (the bias-free head: b_o None)."""
+        ms = self.models
+        return (torch.stack([m.GRU.weight_ih_l0 for m in ms]), torch.stack([m.GRU.weight_hh_l0 for m in ms]),
+                torch.stack([m.GRU.bias_ih_l0 for m in ms]), torch.stack([m.GRU.bias_hh_l0 for m in ms]),
+                torch.stack([m.output.weight for m in ms]), None if self.diffdel else torch.stack([m.output.bias for m in ms]))
+
+    def initialize_hidden(self, Bper=None):
+        """Every replica's initialize_hidden: hidden <- None, for DiffDelRNN also a zero delay buffer of max_delay + 1 samples for
+        `Bper` streams per replica."""
+        self.hidden = None
+        for m in self.models:
+            m.hidden = None
+        if self.diffdel:
+            D = {int(m.max_delay) for m in self.models}
+            if len(D) != 1:
+                raise ValueError(f"Replicas: the models' max_delay differ ({sorted(D)}); one delay-buffer length is needed")
+            self._dl.init_buffer(len(self.models) * int(Bper), D.pop() + 1)
+            self._share()
+
+    def _share(self):
+        """Each model's state <- its slice of the group's (views)."""
+        R = len(self.models)
+        h = self.hidden
+        for r, m in enumerate(self.models):
+            if h is not None:
+                n = h.shape[1] // R
+                m.hidden = h[:, r * n:(r + 1) * n]
+            if self.diffdel:
+                n = self._dl.buffer.shape[0] // R
+                m.diffdel.max_delay = self._dl.max_delay
+                m.diffdel.buffer = self._dl.buffer[r * n:(r + 1) * n]
+                m.diffdel._fresh = False
+
+    def detach_hidden(self):
+        """Every replica's detach_hidden (one clone for all)."""
+        self.hidden = self.hidden.clone().detach()
+        if self.diffdel:
+            self._dl.detach_buffer()
+        self._share()
+
+    def zero_grad(self):
+        for m in self.models:
+            m.zero_grad()
+
+    def forward(self, x, del_traj=None, warmup=False, _share=True):
+        """One stateful training forward of all replicas: x (and del_traj, in samples) (R*Bper, 1, T) replica-major -> y for RNN,
+        (y, pre_d) for DiffDelRNN, as the models' own forward() gives on their slices (same bits), as graph nodes.  A delay above
+        the buffer in ANY replica raises AssertionError with every replica's delay buffer as it was."""
+        R = len(self.models)
+        xbt = _as_bt(x, "Replicas.forward")
+        B, T = xbt.shape
+        if B % R:
+            raise ValueError(f"Replicas.forward: {B} streams do not divide into {R} replicas")
+        if x.requires_grad or (del_traj is not None and del_traj.requires_grad):
+            raise RuntimeError("Replicas.forward: the input requires grad; the training kernels give gradients for the parameters, "
+                               "the hidden state and the delay buffer only")
+        if self.hidden is None:
+            h0 = torch.zeros(B, training.HIDDEN, device=xbt.device, dtype=torch.float32)
+        elif tuple(self.hidden.shape) != (1, B, training.HIDDEN):
+            raise RuntimeError(f"Expected hidden size (1, {B}, {training.HIDDEN}), got {list(self.hidden.shape)}")
+        else:
+            h0 = self.hidden.to(device=xbt.device, dtype=torch.float32).reshape(B, training.HIDDEN)
+        if self.diffdel:
+            if del_traj is None:
+                raise RuntimeError("Replicas.forward: DiffDelRNN replicas need a delay trajectory")
+            dbt = _as_bt(del_traj, "Replicas.forward")
+            if dbt.shape != xbt.shape:
+                raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+            self._dl._prepare(B, xbt.device)
+        pre, h = training.GRUReplicaTrainStep.apply(xbt, h0, *self._stacks(), R)
+        self.hidden = h.view(1, B, training.HIDDEN)
+        if not self.diffdel:
+            if _share:
+                self._share()
+            return pre.view(B, 1, T)
+        dl = self._dl
+        y, buf = training.DelayLineStep.apply(pre, dl.buffer, dbt, bool(warmup), dl._err)
+        dl._launched()               # raises BEFORE any buffer moves on
+        dl.buffer = buf
+        if _share:
+            self._share()
+        return y.view(B, 1, T), pre.view(B, 1, T)
+
+    __call__ = forward
+
+    def _losses(self, loss_fcn, pred, target):
+        """[R] losses: ESRLoss / DCPreESR grouped (one launch per kernel); any other callable per replica slice."""
+        R = len(self.models)
+        if isinstance(loss_fcn, (ESRLoss, DCPreESR)):
+            return loss_fcn.replicas(pred, target, R)
+        n = pred.shape[0] // R
+        return torch.stack([loss_fcn(pred[r * n:(r + 1) * n], target[r * n:(r + 1) * n]).reshape(()) for r in range(R)])
+
+    @staticmethod
+    def _is_batch(b):
+        return isinstance(b, (tuple, list)) and len(b) >= 2 and torch.is_tensor(b[0])
+
+    def _per_replica(self, arg, what):
+        """-> (list of R, shared): `arg` is a list / tuple of R loaders (none of whose items is itself a batch), or ONE loader
+        (which may itself be a list of batches) shared by all replicas."""
+        R = len(self.models)
+        if isinstance(arg, (list, tuple)) and arg and not any(self._is_batch(b) for b in arg):
+            if len(arg) != R:
+                raise ValueError(f"Replicas.train_epoch: {len(arg)} {what} for {R} replicas")
+            return list(arg), False
+        return [arg] * R, True
+
+    def _gather(self, batches, prepare):
+        """The R batches of one iteration, each prepared as its model's train_epoch prepares it, stacked replica-major.  All R
+        must have one shape: ValueError naming both shapes otherwise, before anything is launched for the iteration."""
+        for r, batch in enumerate(batches):
+            for a, b in zip(batches[0][:2], batch[:2]):
+                if a.shape != b.shape:
+                    raise ValueError(f"Replicas.train_epoch: the batch of replica {r} has shape {tuple(b.shape)}, that of replica 0 "
+                                     f"{tuple(a.shape)}; all replicas need batches of one shape")
+        per = [prepare(r, b) for r, b in enumerate(batches)]
+        if all(b is batches[0] for b in batches):
+            R = len(batches)
+            return [t.repeat(R, 1, 1) for t in per[0]]
+        return [torch.cat(ts, dim=0) for ts in zip(*per)]
+
+    def train_epoch(self, dataloaders, loss_fcn, optimizers, dataset=None, losses_hook=None):
+        """One epoch of every replica's train_epoch (RNN: code/model.py:90-161, TBPTT_INIT = TBPTT_LEN = 1024; DiffDelRNN:
+        code/model.py:426-511, the analyser's nextpow2 warm-up, windows of 2048, the fp32 d * fs product, the `//` window count)
+        in lock step; -> the list of R epoch losses.  Per replica the loop is statement for statement that of its own
+        train_epoch: warm-up forward in the graph, zero_grad, then per window forward, loss, backward (of the sum of the R losses:
+        they share no node, so each model receives its own gradient), every optimizer's step(), detach_hidden, zero_grad.
+        `dataloaders`: a list / tuple of R loaders (zipped; the epoch ends with the shortest), or ONE loader whose batches every
+        replica sees.  In every iteration the R batches must have the same shape (ValueError otherwise).
+        `optimizers`: a list / tuple of optimizers (e.g. one per replica), or one optimizer over every replica's parameters;
+        only step() is called on each.
+        `loss_fcn`: an ESRLoss or DCPreESR instance is evaluated for all replicas at once (one launch per kernel, one host
+        synchronisation per window); any other callable of (pred, target) is applied to each replica's slice in turn.
+        `dataset` (DiffDelRNN; one or a list of R; default each loader's .dataset): as DiffDelRNN.train_epoch's; all must give
+        the same warm-up length, and the models the same max_delay.
+        `losses_hook(list of R floats)` is called once per window with the window's losses, in replica order."""
+        R = len(self.models)
+        loaders, shared = self._per_replica(dataloaders, "loaders")
+        opts = list(optimizers) if isinstance(optimizers, (list, tuple)) else [optimizers]
+        for m in self.models:
+            m._check_trainable("Replicas.train_epoch")
+            for p in m.parameters():
+                p.requires_grad_(True)
+            m.train()
+        device = self.device
+        if self.diffdel:
+            from .utilities import nextpow2
+            datasets = ([ld.dataset for ld in loaders] if dataset is None else
+                        list(dataset) if isinstance(dataset, (list, tuple)) else [dataset] * R)
+            if len(datasets) != R:
+                raise ValueError(f"Replicas.train_epoch: {len(datasets)} datasets for {R} replicas")
+            fss = [ds.fs for ds in datasets]
+            inits = [nextpow2(int((ds.delay_analyzer.max_delay if hasattr(ds, "delay_analyzer") else ds.max_delay) * ds.fs))
+                     for ds in datasets]
+            if len(set(inits)) != 1:
+                raise ValueError(f"Replicas.train_epoch: the datasets give different warm-up lengths {inits}; one is needed")
+            TBPTT_INIT, TBPTT_LEN = inits[0], 2**11
+        else:
+            TBPTT_INIT, TBPTT_LEN = 2**10, 2**10
+
+        def prepare(r, batch):
+            input, target = batch[0], batch[1]
+            if input.shape[1] > 1:  # only the audio channel counts for training
+                input, target = input[:, :1, :], target[:, :1, :]
+            if not self.diffdel:
+                return input.to(device), target.to(device)
+            if isinstance(batch[2], dict):
+                d_traj = batch[2]["delay_trajectory"].float()
+                d_traj = d_traj.unsqueeze(1) * fss[r]
+            elif batch[2] is not None:
+                d_traj = batch[2][:, :1, :].float() * fss[r]
+            else:
+                raise RuntimeError("Replicas.train_epoch: the batch carries no delay trajectory")
+            return input.to(device), target.to(device), d_traj.to(device)
+
+        num_batches = 0
+        epoch_loss = [0] * R
+        for batches in (((b,) * R for b in loaders[0]) if shared else zip(*loaders)):
+            stacked = self._gather(batches, prepare)
+            input, target = stacked[0], stacked[1]
+            d_traj = stacked[2] if self.diffdel else None
+            sl = slice(0, TBPTT_INIT)
+            if self.diffdel:
+                num_minibatches = int(np.ceil((input.shape[-1] - TBPTT_INIT) // TBPTT_LEN))
+                self.initialize_hidden(input.shape[0] // R)
+                self.forward(input[:, :, sl], d_traj[:, :, sl], warmup=True, _share=False)          # graph nodes
+            else:
+                num_minibatches = (input.shape[2] - TBPTT_INIT) // TBPTT_LEN
+                self.initialize_hidden()
+                self.forward(input[:, :, sl], _share=False)
+            self.zero_grad()
+
+            minibatch_loss = [0] * R
+            sample_offset = TBPTT_INIT
+            for _ in range(num_minibatches):
+                sl = slice(sample_offset, sample_offset + TBPTT_LEN)
+                if self.diffdel:
+                    pred_mini, _ = self.forward(input[:, :, sl], d_traj[:, :, sl], _share=False)
+                else:
+                    pred_mini = self.forward(input[:, :, sl], _share=False)
+                losses = self._losses(loss_fcn, pred_mini, target[:, :, sl])
+                losses.sum().backward()
+                for opt in opts:
+                    opt.step()
+                self.detach_hidden()
+                self.zero_grad()
+                values = losses.tolist()                 # one host synchronisation for the R losses
+                if losses_hook is not None:
+                    losses_hook(values)
+                minibatch_loss = [a + v for a, v in zip(minibatch_loss, values)]
+                sample_offset += TBPTT_LEN
+            minibatch_loss = [a / num_minibatches for a in minibatch_loss]      # ZeroDivisionError as in the single models
+            epoch_loss = [a + b for a, b in zip(epoch_loss, minibatch_loss)]
+            num_batches += 1
+        return [a / num_batches for a in epoch_loss]
+
+
 # ------------------------------------------------------------------------------------------
 # ESR (the loss that follows the path in code/test-model.py:250-254,386-388)
 # ------------------------------------------------------------------------------------------
@@ -902,6 +1159,36 @@ def _esr_value(output, target):
     return ((s[0] / n) / (s[1] / n + ESR_EPS)).float(), s
 
 
+def _replica_sums(rows, R, Bper, splits):
+    """[R,2] fp64 whole-batch sums of R replicas from the per-stream rows [R*Bper, splits, 2] (ntm_loss_sums_replicas: one
+    launch, the fixed order in which the single-model losses add the rows of one batch)."""
+    s = torch.empty(R, 2, device=rows.device, dtype=torch.float64)
+    _lib.check(_lib.lib().ntm_loss_sums_replicas(ptr(rows), R, Bper, splits, ptr(s), _lib.current_stream()), "ntm_loss_sums_replicas")
+    return s
+
+
+def _replica_split(output, R, what):
+    B = output.shape[0]
+    if R < 1 or B % R:
+        raise ValueError(f"{what}: {B} streams do not divide into {R} replicas")
+    return B // R
+
+
+@torch.no_grad()
+def _esr_value_replicas(output, target, R):
+    y = _as_bt(output, "esr_sums")
+    t = _as_bt(target, "esr_sums")
+    B, T = y.shape
+    Bper = _replica_split(output, R, "ESRLoss.replicas")
+    L = _lib.lib()
+    splits = L.ntm_esr_splits(Bper, T, 0)          # of ONE replica's batch: the partial rows esr_sums forms for it alone
+    rows = torch.empty(B, splits, 2, device=y.device, dtype=torch.float64)
+    _lib.check(L.ntm_esr_sums(ptr(y), ptr(t), B, T, 0, splits, ptr(rows), _lib.current_stream()), "ntm_esr_sums")
+    s = _replica_sums(rows, R, Bper, splits)
+    n = output.numel() // R
+    return ((s[:, 0] / n) / (s[:, 1] / n + ESR_EPS)).float(), s
+
+
 class ESRLoss(torch.nn.Module):
     """ESR of a whole (B,1,T) tensor, as `loss_fcn(output, target)` in code/test-model.py:386-388.  With an output that
     requires grad (RNN.train_epoch, code/train.py:176) the same value as a differentiable scalar (adjoint: ntm_esr_grad)."""
@@ -910,6 +1197,13 @@ class ESRLoss(torch.nn.Module):
         if output.requires_grad and torch.is_grad_enabled():
             return training.loss_with_grad(output, target, _esr_value, None)
         return _esr_value(output, target)[0]
+
+    def replicas(self, output, target, R):
+        """[R] losses of a replica-major (R*Bper,1,T) tensor (Replicas.train_epoch): entry r is forward() on slice r, value and
+        adjoint bit for bit, from one launch per kernel for all R."""
+        if output.requires_grad and torch.is_grad_enabled():
+            return training.replica_losses_with_grad(output, target, _esr_value_replicas, None, R)
+        return _esr_value_replicas(output, target, R)[0]
 
 
 DC_PRE_R = 0.995
@@ -946,6 +1240,21 @@ class DCPreESR(torch.nn.Module):
         if output.requires_grad and torch.is_grad_enabled():
             return training.loss_with_grad(output, target, self._value, self.R if self.dc_pre else None)
         return self._value(output, target)[0]
+
+    @torch.no_grad()
+    def _value_replicas(self, output, target, R):
+        if not self.dc_pre:
+            return _esr_value_replicas(output, target, R)
+        Bper = _replica_split(output, R, "DCPreESR.replicas")
+        s = _replica_sums(esr_dcpre_sums(output, target, 0, self.R), R, Bper, 1)
+        n = output.numel() // R
+        return ((s[:, 0] / n) / (s[:, 1] / n + ESR_EPS)).float(), s
+
+    def replicas(self, output, target, R):
+        """[R] losses of a replica-major (R*Bper,1,T) tensor: entry r is forward() on slice r, value and adjoint bit for bit."""
+        if output.requires_grad and torch.is_grad_enabled():
+            return training.replica_losses_with_grad(output, target, self._value_replicas, self.R if self.dc_pre else None, R)
+        return self._value_replicas(output, target, R)[0]
 
 
 MRSTFT_FFT_SIZES, MRSTFT_HOP_SIZES, MRSTFT_WIN_LENGTHS = (1024, 2048, 512), (120, 240, 50), (600, 1200, 240)

@@ -13,6 +13,9 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
     backward = ntm_delay_backward, the deterministic adjoint (gradients for pre and, where it is in the graph, the old buffer).
   * ESRLossFn / DCPreESRLossFn: the loss value exactly as the no-grad path computes it, and its adjoint on the device
     (ntm_esr_grad / ntm_esr_dcpre_grad).
+  * GRUReplicaTrainStep / replica_losses_with_grad: the same nodes for R independent models stacked replica-major
+    (model.Replicas): one forward, one BPTT, one reduction and one loss launch for all of them, each replica's bits those of
+    the single-model node on its slice.
 """
 import torch
 
@@ -61,6 +64,52 @@ class GRUTrainStep(torch.autograd.Function):
         g_wih, g_whh, g_bih, g_bhh, g_wo, g_bo = torch.split(grad, sizes)
         return (None, dh0.view(ctx.h0_shape), g_wih.view(w_ih.shape), g_whh.view(w_hh.shape), g_bih.view(b_ih.shape),
                 g_bhh.view(b_hh.shape), g_wo.view(w_o.shape), None if b_o is None else g_bo.view(b_o.shape))
+
+
+class GRUReplicaTrainStep(torch.autograd.Function):
+    """GRUTrainStep for R independent models in one launch each way (model.Replicas): x [R*Bper,T] and h0 [R*Bper,64] stacked
+    replica-major, the six parameters as contiguous [R, ...] stacks (b_o None for the bias-free head) -> (y [R*Bper,T],
+    h_T [R*Bper,64]), both fresh.  Every replica's slice has the bits GRUTrainStep gives on it alone; the gradients come back as
+    [R, ...] stacks (the caller builds the stacks with torch.stack inside the graph, so each model gets its own .grad)."""
+
+    @staticmethod
+    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, w_o, b_o, R):
+        B, T = x.shape
+        if R < 1 or B % R:
+            raise RuntimeError(f"GRUReplicaTrainStep: {B} streams do not divide into {R} replicas")
+        for w in (w_ih, w_hh, b_ih, b_hh, w_o, b_o):
+            if w is not None and (w.shape[0] != R or not w.is_contiguous() or w.dtype != torch.float32):
+                raise RuntimeError("GRUReplicaTrainStep: the parameters must be contiguous float32 [R, ...] stacks")
+        L = _lib.lib()
+        h = h0.detach().to(torch.float32).reshape(B, HIDDEN).clone(memory_format=torch.contiguous_format)
+        y = torch.empty(B, T, device=x.device, dtype=torch.float32)
+        ws = torch.empty(max(int(L.ntm_gru_train_workspace_floats(B, T)), 1), device=x.device, dtype=torch.float32)
+        _lib.check(L.ntm_gru_train_forward_replicas(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(x), ptr(y), R,
+                                                    B // R, T, T, T, ptr(h), ptr(ws), _lib.current_stream()),
+                   "ntm_gru_train_forward_replicas")
+        ctx.save_for_backward(x, ws, w_ih, w_hh, b_ih, b_hh, w_o, b_o)
+        ctx.h0_shape, ctx.R = h0.shape, R
+        ctx.set_materialize_grads(False)
+        return y, h
+
+    @staticmethod
+    def backward(ctx, dy, dh):
+        x, ws, w_ih, w_hh, b_ih, b_hh, w_o, b_o = ctx.saved_tensors
+        B, T = x.shape
+        R, dev = ctx.R, x.device
+        dy = None if dy is None else dy.to(torch.float32).contiguous()
+        dh = None if dh is None else dh.to(torch.float32).reshape(B, HIDDEN).contiguous()
+        dh0 = torch.empty(B, HIDDEN, device=dev, dtype=torch.float32)
+        part = torch.empty(B, _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
+        grad = torch.empty(R, _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
+        L, s = _lib.lib(), _lib.current_stream()
+        _lib.check(L.ntm_gru_train_backward_replicas(ptr(w_hh), ptr(w_o), ptr(x), T, ptr(ws), ptr(dy), T, ptr(dh), R, B // R, T,
+                                                     ptr(dh0), ptr(part), s), "ntm_gru_train_backward_replicas")
+        _lib.check(L.ntm_gru_train_reduce_replicas(ptr(part), R, B // R, ptr(grad), s), "ntm_gru_train_reduce_replicas")
+        H3 = 3 * HIDDEN
+        g_wih, g_whh, g_bih, g_bhh, g_wo, g_bo = torch.split(grad, [H3, H3 * HIDDEN, H3, H3, HIDDEN, 1], dim=1)
+        return (None, dh0.view(ctx.h0_shape), g_wih.reshape(w_ih.shape), g_whh.reshape(w_hh.shape), g_bih.reshape(b_ih.shape),
+                g_bhh.reshape(b_hh.shape), g_wo.reshape(w_o.shape), None if b_o is None else g_bo.reshape(b_o.shape), None)
 
 
 class DelayLineStep(torch.autograd.Function):
@@ -128,3 +177,40 @@ def loss_with_grad(output, target, value, R):
     if target.requires_grad:
         raise RuntimeError("ESRLoss / DCPreESR: gradients flow to the prediction only; the target must not require grad")
     return _LossFn.apply(output, target, value, R)
+
+
+class _ReplicaLossFn(torch.autograd.Function):
+    """_LossFn for R losses at once: `value(output, target, R)` -> (losses [R], the replicas' whole-batch sums [R,2] fp64)."""
+
+    @staticmethod
+    def forward(ctx, output, target, value, pole, R):
+        loss, sums = value(output, target, R)
+        ctx.save_for_backward(output, target, sums)
+        ctx.pole, ctx.R = pole, R
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from .model import ESR_EPS, _as_bt
+        output, target, sums = ctx.saved_tensors
+        y = _as_bt(output, "loss backward")
+        t = _as_bt(target, "loss backward")
+        B, T = y.shape
+        R = ctx.R
+        g = gout.detach().to(device=y.device, dtype=torch.float32).reshape(R).contiguous()
+        dy = torch.empty(B, T, device=y.device, dtype=torch.float32)
+        L, s = _lib.lib(), _lib.current_stream()
+        if ctx.pole is None:
+            _lib.check(L.ntm_esr_grad_replicas(ptr(y), ptr(t), R, B // R, T, ptr(sums), ptr(g), ESR_EPS, ptr(dy), s),
+                       "ntm_esr_grad_replicas")
+        else:
+            _lib.check(L.ntm_esr_dcpre_grad_replicas(ptr(y), ptr(t), R, B // R, T, float(ctx.pole), ptr(sums), ptr(g), ESR_EPS,
+                                                     ptr(dy), s), "ntm_esr_dcpre_grad_replicas")
+        return dy.view(output.shape).to(output.dtype), None, None, None, None
+
+
+def replica_losses_with_grad(output, target, value, pole, R):
+    """The grouped loss node: [R] losses of the replica-major (R*Bper,1,T) output; pole None = ESR, else DCPreESR's R."""
+    if target.requires_grad:
+        raise RuntimeError("ESRLoss / DCPreESR: gradients flow to the prediction only; the target must not require grad")
+    return _ReplicaLossFn.apply(output, target, value, pole, R)

@@ -6,7 +6,11 @@ in a child under `rocprofv3 --kernel-trace --stats` and the per-kernel times are
 With --model diffdel: one TBPTT window of DiffDelRNN.train_epoch (code/model.py:464-497) for DiffDelGRU-HS[64] at L = 2048, D = 11 001
 (forward: GRU + delay line, loss, backward: delay adjoint + BPTT + reduce, Adam), and the backward of a 16 384-sample warm-up
 (TBPTT_INIT at that D) reached through the first window; its GRU workspace is B * 16 384 * 1280 B (0.67 GB at B = 32).
-usage: python tools/train_probe.py [--model gru|diffdel] [--iters N] [--rocprof]"""
+With --replicas R[,R...]: one TBPTT window of ntm_amd.Replicas (R models at B = 32 each, one launch per kernel for all of them)
+beside R sequential windows of the single-model path in the same process -- whole window, window without the optimizer steps, and
+the optimizer steps alone, with one optimizer per replica and with one optimizer over all parameters; median and range over
+--reps repetitions of --iters windows.  GRU: L = 1024; --model diffdel: L = 2048, D = 11 001.
+usage: python tools/train_probe.py [--model gru|diffdel] [--iters N] [--rocprof] [--replicas 1,2,4,8 [--reps N]]"""
 import argparse
 import glob
 import json
@@ -105,6 +109,93 @@ def engine_diffdel(B, iters):
     return _time(window, iters), _time(first_window, max(iters // 4, 2)), _time(adjoint, iters)
 
 
+def replicas(R, iters, reps, model="gru", B=32):
+    """-> {name: [median, min, max] ms per window}: the group window (one optimizer per replica / one over all), R sequential
+    single-model windows, both without the optimizer steps, and the optimizer steps alone."""
+    import statistics
+    import torch
+    import ntm_amd
+    torch.manual_seed(0)
+    dd = model == "diffdel"
+    T = DD_L if dd else L
+    loss_fcn = ntm_amd.ESRLoss()
+
+    def make():
+        m = (ntm_amd.DiffDelRNN(1, 64, 1, max_delay=DD_D - 1) if dd else ntm_amd.RNN(1, 64, 1)).cuda()
+        for p in m.parameters():
+            p.requires_grad_(True)
+        return m
+    x = torch.rand(R * B, 1, T, device="cuda") - 0.5
+    t = 0.5 * x
+    n = torch.arange(T, device="cuda", dtype=torch.float32)
+    d = (5500.0 + 4000.0 * torch.sin(n / 7000.0) + 20.0 * torch.sin(n / 300.0)).expand(R * B, 1, -1).contiguous()
+
+    def group(opts_of):
+        ms = [make() for _ in range(R)]
+        g = ntm_amd.Replicas(ms)
+        opts = opts_of(ms)
+        g.initialize_hidden(B)
+        g.hidden = torch.zeros(1, R * B, 64, device="cuda")
+
+        def window(step=True):
+            y = g(x, d, _share=False)[0] if dd else g(x, _share=False)
+            losses = loss_fcn.replicas(y, t, R)
+            losses.sum().backward()
+            if step:
+                for o in opts:
+                    o.step()
+            g.detach_hidden()
+            g.zero_grad()
+            return losses.tolist()
+        window()                       # leaves gradients' shapes and the optimizer state in place
+        return window, opts, ms
+
+    def single():
+        ms = [make() for _ in range(R)]
+        opts = [torch.optim.Adam(m.parameters(), 1e-3) for m in ms]
+        for m in ms:
+            if dd:
+                m.initialize_hidden(B, m.max_delay)
+            m.hidden = torch.zeros(1, B, 64, device="cuda")
+
+        def window(step=True):
+            for r, (m, o) in enumerate(zip(ms, opts)):
+                sl = slice(r * B, (r + 1) * B)
+                y = m(x[sl], d[sl])[0] if dd else m(x[sl])
+                loss = loss_fcn(y, t[sl])
+                loss.backward()
+                if step:
+                    o.step()
+                m.detach_hidden()
+                m.zero_grad()
+                loss.item()
+        window()
+        return window
+
+    def steps_only(opts, ms):
+        for m in ms:
+            for p in m.parameters():
+                p.grad = torch.zeros_like(p)
+
+        def run():
+            for o in opts:
+                o.step()
+        return run
+    each = lambda ms: [torch.optim.Adam(m.parameters(), 1e-3) for m in ms]                       # noqa: E731
+    one = lambda ms: [torch.optim.Adam([p for m in ms for p in m.parameters()], 1e-3)]          # noqa: E731
+    w_each, o_each, m_each = group(each)
+    w_one, o_one, m_one = group(one)
+    w_single = single()
+    runs = {"group": w_each, "group, one optimizer": w_one, f"{R} x single": w_single,
+            "group, no step": lambda: w_each(False), f"{R} x single, no step": lambda: w_single(False),
+            "steps alone": steps_only(o_each, m_each), "step alone, one optimizer": steps_only(o_one, m_one)}
+    times = {name: [] for name in runs}
+    for _ in range(reps):               # the forms alternate within a repetition, so that drift of the machine hits all alike
+        for name, fn in runs.items():
+            times[name].append(_time(fn, iters))
+    return {name: [statistics.median(v), min(v), max(v)] for name, v in times.items()}
+
+
 def miopen(B, iters, native=False):
     """torch.nn.GRU + Linear training; `native`: with torch's own GRU cell kernels instead of MIOpen (cudnn backend off)."""
     import torch
@@ -132,13 +223,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rocprof", action="store_true")
-    ap.add_argument("--child", choices=["engine", "miopen", "native", "diffdel"])
+    ap.add_argument("--child", choices=["engine", "miopen", "native", "diffdel", "replicas"])
+    ap.add_argument("--replicas", default=None, help="comma-separated replica counts, e.g. 1,2,4,8")
+    ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="32,4096")
     ap.add_argument("--model", choices=["gru", "diffdel"], default="gru")
     a = ap.parse_args()
     sizes = [int(b) for b in a.sizes.split(",")]
     if a.child == "diffdel":
         print(json.dumps({str(B): engine_diffdel(B, a.iters) for B in sizes}))
+        return
+    if a.child == "replicas":
+        print(json.dumps({str(R): replicas(R, a.iters, a.reps, a.model) for R in map(int, a.replicas.split(","))}))
         return
     if a.child:
         out = {}
@@ -165,6 +261,21 @@ def main():
         if r.returncode != 0:
             raise SystemExit(f"{what} exited with status {r.returncode}; nothing more is started\n{r.stderr[-2000:]}")
         return r
+
+    if a.replicas:
+        r = child([sys.executable, __file__, "--child", "replicas", "--replicas", a.replicas, "--iters", str(a.iters), "--reps",
+                   str(a.reps), "--model", a.model], "replicas child")
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        what = f"DiffDelGRU-HS[64], L = {DD_L}, D = {DD_D}" if a.model == "diffdel" else f"GRU-HS[64], L = {L}"
+        print(f"{what}, B = 32 per replica; ms per window, median [min .. max] of {a.reps} x {a.iters} windows:")
+        for R, rows in res.items():
+            print(f"R = {R}")
+            for name, (med, lo, hi) in rows.items():
+                print(f"  {name:<28} {med:8.3f}  [{lo:.3f} .. {hi:.3f}]")
+        if a.rocprof:
+            for R in a.replicas.split(","):
+                _rocprof(child, a, [R], "replicas", ["--replicas", R, "--reps", "1", "--model", a.model])
+        return
 
     if a.model == "diffdel":
         r = child([sys.executable, __file__, "--child", "diffdel", "--iters", str(a.iters), "--sizes", a.sizes], "diffdel child")
@@ -195,19 +306,19 @@ def main():
         _rocprof(child, a, sizes, "engine")
 
 
-def _rocprof(child, a, sizes, kind):
+def _rocprof(child, a, sizes, kind, extra=()):
     """The per-kernel split of the `kind` child under rocprofv3 --kernel-trace --stats, one child per batch size."""
     import csv
     for B in sizes:
         with tempfile.TemporaryDirectory() as d:
             child(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "probe", "--output-format", "csv", "--", sys.executable,
-                   __file__, "--child", kind, "--iters", str(a.iters), "--sizes", str(B)], f"rocprofv3 {kind} child B={B}")
+                   __file__, "--child", kind, "--iters", str(a.iters), "--sizes", str(B), *extra], f"rocprofv3 {kind} child B={B}")
             stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
             if not stats:
                 raise SystemExit("rocprofv3 wrote no kernel stats")
             krows = list(csv.DictReader(open(stats[0])))
         total = sum(float(x["TotalDurationNs"]) for x in krows)
-        print(f"\nper-kernel time of the engine at B = {B} ({a.iters} + 3 warm-up windows):")
+        print(f"\nper-kernel time of the {kind} child at {'R' if kind == 'replicas' else 'B'} = {B} (all of its windows):")
         for x in sorted(krows, key=lambda x: -float(x["TotalDurationNs"]))[:12]:
             print(f"{float(x['TotalDurationNs']) / total * 100:6.1f}%  {int(x['Calls']):6d} calls  "
                   f"{float(x['AverageNs']) / 1e3:10.1f} us avg  {x['Name'][:90]}")
