@@ -444,6 +444,19 @@ int ntm_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64
                                 const float *gout, double eps, float *dy, void *stream);
 
 /*
+ * Inference for R replicas (the `validate` / `predict` half of the epoch loop, code/train.py:238-267, for models trained side by
+ * side): ntm_gru_forward_ex with NTM_GRU_LAT for H = 64, input / output size 1, on R * Bper streams stacked replica-major with
+ * the parameter stacks described above -- y [R*Bper, T] (row strides in elements, >= T) and h_state [R*Bper, 64] (in / out; null:
+ * zero initial state, final state not written) of replica r are bit-identical to that call on r's slice with r's parameters,
+ * and R = 1 IS that call.  b_o may be null.  One launch; always the low-latency kernel (a workgroup per stream), for any
+ * R * Bper: NTM_GRU_AUTO's hand-over to the matrix-pipe kernel above NTM_GRU_LAT_MAX_B streams does not happen here.
+ * NTM_EINVAL before anything is enqueued: R < 1, Bper < 1, T < 0, a null required pointer, a stride below T, y == x.
+ */
+int ntm_gru_forward_replicas(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                             const float *b_o, const float *x, float *y, int64_t R, int64_t Bper, int64_t T, int64_t x_stride_b,
+                             int64_t y_stride_b, float *h_state, void *stream);
+
+/*
  * Adjoint of the time-varying fractional delay line (ntm_delay_forward) over one call of B streams of L samples with a buffer of
  * D samples (the backward of DiffDelRNN.train_epoch's delay step, code/model.py:269-320,456-496).  With z = [buffer, x] the
  * forward is y[n] = sum_m w_m(n) z[D + n - m] over the taps m in {k+1, k}, k = floor(d[n]), that it counts, and the new buffer

@@ -16,10 +16,21 @@ using namespace lat;
 
 // HEADW: a fifth wave does the head (B <= the number of CUs: a workgroup has a CU to itself); without it the head is a duty
 // that rotates among the four compute waves (more streams than CUs: a fifth wave per workgroup costs occupancy)
-template <bool HEADW>
+//
+// REP (ntm_gru_forward_replicas): R models in one launch.  The streams are stacked replica-major, stream s belongs to replica
+// s / a.bper, and the six parameter pointers are the [R, ...] stacks gru_train_fwd_kernel<true> takes -- the workgroup moves them
+// to its replica's slice before the weight load (a scalar division and six scalar adds, once); everything behind that is the
+// same code, so every replica's y and h_state are the bits of the REP = false kernel on its slice.  REP = false reads no bper.
+template <bool HEADW, bool REP = false>
 __global__ __launch_bounds__(HEADW ? 320 : 256) void gru_lat_kernel(GruArgs a)
 {
 #pragma clang fp contract(off)
+    if constexpr (REP) {
+        const size_t rep = blockIdx.x / a.bper;
+        a.w_ih += rep * (3 * kH); a.w_hh += rep * (3 * kH * kH); a.b_ih += rep * (3 * kH); a.b_hh += rep * (3 * kH);
+        a.w_o += rep * kH;
+        if (a.b_o) a.b_o += rep;
+    }
     __shared__ __attribute__((aligned(16))) float hb[2][kH];            // h by step parity
     __shared__ float xt[2][LT];
     __shared__ float yt[2][LT];
@@ -94,6 +105,17 @@ hipError_t launch_gru_lat(const GruArgs &a, hipStream_t stream)
     if (a.B == 0) return hipSuccess;
     if (a.B <= device_cus()) hipLaunchKernelGGL(gru_lat_kernel<true>, dim3((unsigned)a.B), dim3(320), 0, stream, a);
     else hipLaunchKernelGGL(gru_lat_kernel<false>, dim3((unsigned)a.B), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+// R * bper streams of R stacked replicas: HEADW by the TOTAL stream count, as above (a workgroup has a CU to itself or not
+// whichever replica it belongs to)
+hipError_t launch_gru_lat_replicas(const GruArgs &a, hipStream_t stream)
+{
+    if (a.B == 0) return hipSuccess;
+    if (a.bper == 0) return hipErrorInvalidValue;
+    if (a.B <= device_cus()) hipLaunchKernelGGL((gru_lat_kernel<true, true>), dim3((unsigned)a.B), dim3(320), 0, stream, a);
+    else hipLaunchKernelGGL((gru_lat_kernel<false, true>), dim3((unsigned)a.B), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

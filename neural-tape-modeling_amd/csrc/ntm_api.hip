@@ -759,6 +759,24 @@ int ntm_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_dcpre_grad_replicas");
 }
 
+// inference of R stacked replicas: ALWAYS the low-latency kernel (NTM_GRU_LAT), whatever R * Bper is -- NTM_GRU_AUTO's hand-over
+// to the matrix-pipe kernel above NTM_GRU_LAT_MAX_B streams (mfma2_streams) has no counterpart here
+int ntm_gru_forward_replicas(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                             const float *b_o, const float *x, float *y, int64_t R, int64_t Bper, int64_t T, int64_t x_stride_b,
+                             int64_t y_stride_b, float *h_state, void *stream)
+{
+    if (int rc = bad_replicas("ntm_gru_forward_replicas", R, Bper)) return rc;
+    if (T < 0) return fail(NTM_EINVAL, "ntm_gru_forward_replicas: negative T");
+    if (T == 0) return NTM_OK;
+    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y) return fail(NTM_EINVAL, "ntm_gru_forward_replicas: null pointer");
+    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, "ntm_gru_forward_replicas: row stride below T");
+    if (x == y) return fail(NTM_EINVAL, "ntm_gru_forward_replicas: y must not alias x");
+    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, R * Bper, T, x_stride_b, y_stride_b, nullptr, 0, 0};
+    a.bper = (unsigned)Bper;
+    hipError_t e = ntm::launch_gru_lat_replicas(a, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_forward_replicas");
+}
+
 int ntm_delay_backward(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
                        int D, int warmup, int flags, void *stream)
 {

@@ -49,6 +49,9 @@ struct GruArgs {
     float dcp_R = 0.995f;           // pole of the DC blocker
     int H = 64;                     // hidden size as the caller's tensors have it (gru_small.hip: any size but 64; the
                                     // matrix-pipe / low-latency kernels are compiled for kH)
+    // R stacked replicas in one low-latency launch (gru_lat_kernel<HEADW, REP>, launch_gru_lat_replicas): streams per replica;
+    // B = R * bper, stream s reads the parameters of replica s / bper from the [R, ...] stacks.  0: one model (nobody reads it)
+    unsigned bper = 0;
 };
 
 }  // namespace ntm
@@ -68,6 +71,7 @@ hipError_t launch_gru_mfma(const GruArgs &a, hipStream_t stream);
 hipError_t launch_gru_valu(const GruArgs &a, hipStream_t stream);
 hipError_t launch_gru_mfma2(const GruArgs &a, hipStream_t stream);   // a.dd set: GRU + head + delay line in one launch
 hipError_t launch_gru_lat(const GruArgs &a, hipStream_t stream);
+hipError_t launch_gru_lat_replicas(const GruArgs &a, hipStream_t stream);   // a.bper > 0, a.B = R * a.bper, the parameters are stacks
 hipError_t launch_gru_small(const GruArgs &a, int H, hipStream_t stream);   // any H in [1, 1024] but 64
 hipError_t launch_gru_io(const GruArgs &a, int H, int I, int O, hipStream_t stream);   // any input_size / output_size (gru_small.hip)
 hipError_t launch_debug_transpose(const float *in, float *out, hipStream_t stream);

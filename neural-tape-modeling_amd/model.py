@@ -878,6 +878,9 @@ class Replicas:
     The models stay ordinary modules with their own parameters (the [R, ...] stacks are built inside the graph by torch.stack, so
     autograd hands each model its own .grad): each state_dict() is the reference's checkpoint format, and each can validate()
     or predict() on its own afterwards.  After every window each model's `hidden` (and delay buffer) is its slice of the group's.
+    The other half of the epoch loop (code/train.py:238-267) is grouped as well: infer() / validate() / predict() run all R models
+    in one launch of the low-latency kernel (ntm_gru_forward_replicas) and give every replica the bits of its own
+    validate() / predict().
     Out of scope: replicas of different architectures, per-replica batch sizes, skip=True and hidden sizes other than 64 (the
     single models refuse to train there too), several devices."""
 
@@ -1005,29 +1008,32 @@ class Replicas:
     def _is_batch(b):
         return isinstance(b, (tuple, list)) and len(b) >= 2 and torch.is_tensor(b[0])
 
-    def _per_replica(self, arg, what):
+    def _per_replica(self, arg, what, who="Replicas.train_epoch"):
         """-> (list of R, shared): `arg` is a list / tuple of R loaders (none of whose items is itself a batch), or ONE loader
         (which may itself be a list of batches) shared by all replicas."""
         R = len(self.models)
         if isinstance(arg, (list, tuple)) and arg and not any(self._is_batch(b) for b in arg):
             if len(arg) != R:
-                raise ValueError(f"Replicas.train_epoch: {len(arg)} {what} for {R} replicas")
+                raise ValueError(f"{who}: {len(arg)} {what} for {R} replicas")
             return list(arg), False
         return [arg] * R, True
 
-    def _gather(self, batches, prepare):
+    def _gather(self, batches, prepare, who="Replicas.train_epoch", keep=False):
         """The R batches of one iteration, each prepared as its model's train_epoch prepares it, stacked replica-major.  All R
-        must have one shape: ValueError naming both shapes otherwise, before anything is launched for the iteration."""
+        must have one shape: ValueError naming both shapes otherwise, before anything is launched for the iteration.
+        `keep`: -> (stacked, the R prepared batches as they were before stacking)."""
         for r, batch in enumerate(batches):
             for a, b in zip(batches[0][:2], batch[:2]):
                 if a.shape != b.shape:
-                    raise ValueError(f"Replicas.train_epoch: the batch of replica {r} has shape {tuple(b.shape)}, that of replica 0 "
+                    raise ValueError(f"{who}: the batch of replica {r} has shape {tuple(b.shape)}, that of replica 0 "
                                      f"{tuple(a.shape)}; all replicas need batches of one shape")
         per = [prepare(r, b) for r, b in enumerate(batches)]
         if all(b is batches[0] for b in batches):
             R = len(batches)
-            return [t.repeat(R, 1, 1) for t in per[0]]
-        return [torch.cat(ts, dim=0) for ts in zip(*per)]
+            stacked = [t.repeat(R, 1, 1) for t in per[0]]
+        else:
+            stacked = [torch.cat(ts, dim=0) for ts in zip(*per)]
+        return (stacked, per) if keep else stacked
 
     def train_epoch(self, dataloaders, loss_fcn, optimizers, dataset=None, losses_hook=None):
         """One epoch of every replica's train_epoch (RNN: code/model.py:90-161, TBPTT_INIT = TBPTT_LEN = 1024; DiffDelRNN:
@@ -1123,6 +1129,227 @@ class Replicas:
             epoch_loss = [a + b for a, b in zip(epoch_loss, minibatch_loss)]
             num_batches += 1
         return [a / num_batches for a in epoch_loss]
+
+    # ---- inference of the group: one launch of the low-latency kernel for all R models
+
+    @staticmethod
+    def _streams_per_replica(B, R, what):
+        """Bper of B replica-major streams, or the ValueError that names both numbers."""
+        if R < 1 or B % R:
+            raise ValueError(f"{what}: {B} streams do not divide into {R} replicas")
+        return B // R
+
+    @torch.no_grad()
+    def _infer_stacks(self):
+        """The six [R, ...] parameter stacks as plain tensors (no graph, whatever requires_grad says)."""
+        return tuple(None if t is None else t.detach().contiguous() for t in self._stacks())
+
+    @torch.no_grad()
+    def infer(self, x, del_traj=None, warmup=False, _stacks=None):
+        """The stateful inference forward of all replicas in ONE GRU launch: x (and del_traj, in samples) (R*Bper, 1, T)
+        replica-major -> y for RNN replicas, (y, pre_d) for DiffDelRNN replicas; carries the group's `hidden` (and delay buffer)
+        and refreshes each model's views of them.  Nothing is recorded, whatever requires_grad says (it works straight after
+        train_epoch), and the outputs do not require grad.
+        Grouped inference ALWAYS runs the low-latency kernel (ntm_gru_forward_replicas: a workgroup per stream, each reading its
+        replica's slice of the parameter stacks), for any R * Bper; DiffDelRNN replicas follow it with the streaming delay pass on
+        all R * Bper streams (the delay line has no parameters).  Every replica's result is bit-identical to the same model's own
+        forward() on its slice with `kernel_variant = "lat"` (and `delay_mode = "two_pass"`) -- which is what the default "auto"
+        runs up to NTM_GRU_LAT_MAX_B = 1024 streams per model (csrc/ntm_api.hip, mfma2_streams); above that a single model's
+        "auto" hands over to the matrix-pipe kernel (another summation order) and this entry does not.
+        A delay above the buffer in ANY replica raises AssertionError with every replica's delay buffer as it was (one range
+        flag for the group; the hidden state has moved on by then, as in the single model)."""
+        R = len(self.models)
+        H = training.HIDDEN
+        xbt = _as_bt(x, "Replicas.infer")
+        B, T = xbt.shape
+        Bper = self._streams_per_replica(B, R, "Replicas.infer")
+        _require_hip(self.models[0].GRU.weight_hh_l0, "model parameters (call .to('cuda'))")
+        if self.hidden is None:
+            h = torch.zeros(B, H, device=xbt.device, dtype=torch.float32)
+        elif tuple(self.hidden.shape) != (1, B, H):
+            raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
+        else:           # a tensor of its own: the kernel updates it in place
+            h = self.hidden.detach().to(device=xbt.device, dtype=torch.float32).reshape(B, H).clone()
+        if self.diffdel:
+            if del_traj is None:
+                raise RuntimeError("Replicas.infer: DiffDelRNN replicas need a delay trajectory")
+            dbt = _as_bt(del_traj, "Replicas.infer")
+            if dbt.shape != xbt.shape:
+                raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        w_ih, w_hh, b_ih, b_hh, w_o, b_o = self._infer_stacks() if _stacks is None else _stacks
+        pre = torch.empty_like(xbt)
+        rc = _lib.lib().ntm_gru_forward_replicas(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(xbt), ptr(pre),
+                                                 R, Bper, T, max(xbt.stride(0), T), max(pre.stride(0), T), ptr(h), _lib.current_stream())
+        _lib.check(rc, "ntm_gru_forward_replicas")
+        self.hidden = h.view(1, B, H)
+        if not self.diffdel:
+            self._share()
+            return pre.view(B, 1, T)
+        try:
+            y = self._dl._run(pre, dbt, warmup)          # raises BEFORE any buffer moves on (or defers, as predict() asks)
+        finally:
+            self._share()
+        return y.view(B, 1, T), pre.view(B, 1, T)
+
+    @staticmethod
+    def _host_rows(rows):
+        """The losses of one batch, rows [pieces][R], as Python floats -- the values `.item()` gives the single model's validate,
+        brought over in ONE .tolist() of a [pieces, R] tensor wherever they are tensors of one kind on one device."""
+        if all(torch.is_tensor(r) for r in rows):
+            return torch.stack(rows).tolist() if rows else []
+        flat = [v for r in rows for v in r]
+        if flat and all(torch.is_tensor(v) and v.dtype == flat[0].dtype and v.device == flat[0].device for v in flat):
+            return torch.stack([v.reshape(()) for v in flat]).view(len(rows), -1).tolist()
+        return [[v.item() if hasattr(v, "item") else float(v) for v in r] for r in rows]
+
+    @torch.no_grad()
+    def validate(self, dataloaders, loss_fcn, store_examples=True):
+        """Every replica's validate() (RNN: code/model.py:163-216, INIT_LEN = 1024, one loss per batch; DiffDelRNN:
+        code/model.py:513-616, INIT_LEN = the analyser's nextpow2 warm-up run with `warmup=True`, the loss on 2048-sample pieces,
+        the mean over pieces, ZeroDivisionError for T <= INIT_LEN) in lock step, with ONE GRU launch per forward for all R;
+        -> the list of R (val_loss, examples), each the bits of that model's own validate() on its own loader (see infer()).
+        `dataloaders`: a list / tuple of R loaders of equal length (zipped), or ONE loader whose batches every replica sees
+        (train_epoch's rule); in every iteration the R batches must have one shape (ValueError otherwise).  DiffDelRNN: every
+        loader needs `.dataset.fs` and `.dataset.delay_analyzer.max_delay`, all giving one warm-up length.
+        `loss_fcn`: an ESRLoss or DCPreESR instance is evaluated for all replicas at once (one launch per kernel); any other
+        callable of (pred, target) is applied to each replica in turn, on tensors laid out as that model's own validate() lays
+        them out (a fresh prediction tensor, the replica's own target), so that a torch reduction takes the same path.  The losses
+        of a batch reach the host in one .tolist() and are added in Python in the order the single validate adds its .item()s.
+        The examples of replica r are the first stream of its slice, with the single model's keys."""
+        who = "Replicas.validate"
+        R = len(self.models)
+        loaders, shared = self._per_replica(dataloaders, "loaders", who)
+        counts = [len(ld) for ld in loaders]
+        if len(set(counts)) != 1:
+            raise ValueError(f"{who}: the loaders have different lengths {counts}; every replica needs as many batches")
+        device = self.device
+        for m in self.models:
+            m.eval()
+        grouped = isinstance(loss_fcn, (ESRLoss, DCPreESR))
+        if self.diffdel:
+            from .utilities import nextpow2
+            fss = [ld.dataset.fs for ld in loaders]
+            inits = [nextpow2(int(ld.dataset.delay_analyzer.max_delay * ld.dataset.fs)) for ld in loaders]
+            if len(set(inits)) != 1:
+                raise ValueError(f"{who}: the datasets give different warm-up lengths {inits}; one is needed")
+            INIT_LEN, TBPTT_LEN = inits[0], 2**11
+        else:
+            INIT_LEN = 2**10
+
+        def prepare(r, batch):
+            input, target, meta = batch
+            if input.shape[1] > 1:            # only the audio channel counts for the loss
+                input, target = input[:, :1, :], target[:, :1, :]
+            if not self.diffdel:
+                return input.to(device), target.to(device)
+            d_traj = meta["delay_trajectory"].float()
+            d_traj = d_traj.unsqueeze(1) * fss[r]
+            return input.to(device), target.to(device), d_traj.to(device)
+
+        stacks = self._infer_stacks()           # once per call, not once per batch
+        val_loss = [0] * R
+        examples = [[] for _ in range(R)]
+        for batches in (((b,) * R for b in loaders[0]) if shared else zip(*loaders)):
+            stacked, per = self._gather(batches, prepare, who, keep=True)
+            input, target = stacked[0], stacked[1]
+            n = self._streams_per_replica(input.shape[0], R, who)
+            T = input.shape[-1]
+            if self.diffdel:
+                d_traj = stacked[2]
+                num_minibatches = int(np.ceil((T - INIT_LEN) / TBPTT_LEN))
+                self.initialize_hidden(n)
+                self.infer(input[:, :, :INIT_LEN], d_traj[:, :, :INIT_LEN], warmup=True, _stacks=stacks)
+                if num_minibatches > 0:
+                    pred, pre_d = self.infer(input[:, :, INIT_LEN:], d_traj[:, :, INIT_LEN:], _stacks=stacks)
+                else:
+                    pred = pre_d = torch.empty(input.shape[0], 1, max(T - INIT_LEN, 0), device=device, dtype=torch.float32)
+                pieces = [slice(k * TBPTT_LEN, (k + 1) * TBPTT_LEN) for k in range(num_minibatches)]
+            else:
+                self.initialize_hidden()
+                self.infer(input[:, :, :INIT_LEN], _stacks=stacks)
+                pred = self.infer(input[:, :, INIT_LEN:], _stacks=stacks)
+                num_minibatches, pieces = None, [slice(None)]
+            input, target = input[:, :, INIT_LEN:], target[:, :, INIT_LEN:]
+            if grouped:
+                rows = [loss_fcn.replicas(pred[:, :, sl], target[:, :, sl], R) for sl in pieces]
+            else:
+                rows = [[] for _ in pieces]
+                for r in range(R):
+                    own_t = per[r][1]
+                    if self.diffdel:        # the single model scores slices of a whole-length prediction buffer
+                        own_p = torch.empty(own_t.shape, device=device, dtype=torch.float32)
+                        own_p[:, :, INIT_LEN:] = pred[r * n:(r + 1) * n]
+                        own_p, own_t = own_p[:, :, INIT_LEN:], own_t[:, :, INIT_LEN:]
+                    else:
+                        own_p, own_t = pred[r * n:(r + 1) * n].clone(), own_t[:, :, INIT_LEN:]
+                    for k, sl in enumerate(pieces):
+                        rows[k].append(loss_fcn(own_p[:, :, sl], own_t[:, :, sl]))
+            batch_loss = [0] * R
+            for values in self._host_rows(rows):                        # in piece order, as the single loop adds them
+                batch_loss = [a + v for a, v in zip(batch_loss, values)]
+            if num_minibatches is not None:
+                batch_loss = [a / num_minibatches for a in batch_loss]  # ZeroDivisionError for T <= INIT_LEN, as in the single model
+            val_loss = [a + b for a, b in zip(val_loss, batch_loss)]
+            if store_examples:
+                for r in range(R):
+                    ex = {"input": input[r * n, 0, :], "target": target[r * n, 0, :], "prediction": pred[r * n, 0, :]}
+                    if self.diffdel:
+                        ex["prediction_pre_d"] = pre_d[r * n, 0, :]
+                    examples[r].append(ex)
+        return [(v / c, ex) for v, c, ex in zip(val_loss, counts, examples)]
+
+    @torch.no_grad()
+    def predict(self, input, d_traj=None, segment_length=None):
+        """Every replica's predict() (code/model.py:218-246, :618-653) on input (and d_traj, in samples) (R*Bper, 1, T)
+        replica-major: initialize_hidden, the warm start of all R models -- ONE grouped launch of R x 1 stream over 1024 zeros --
+        each warm state (hidden, and delay buffer) broadcast to its Bper streams, then the sequence whole or in `segment_length`
+        pieces; -> y for RNN replicas, (y, pre_d) for DiffDelRNN replicas, the bits of each model's own predict() on its slice
+        (see infer()).  The warm start is recomputed on every call (the models' `warm_cache` is neither read nor written: what it
+        would hold is what the launch computes, and a stale key cannot arise).  As in DiffDelRNN.predict the delay-range assert
+        is evaluated once, after the last piece has been enqueued."""
+        START_LEN = 2**10
+        R = len(self.models)
+        if input.dim() != 3:
+            raise RuntimeError(f"Replicas.predict: expected (N_BATCHES, N_CHANNELS, N_SAMPLES), got {tuple(input.shape)}")
+        B, T = input.shape[0], input.shape[-1]
+        Bper = self._streams_per_replica(B, R, "Replicas.predict")
+        if self.diffdel and d_traj is None:
+            raise RuntimeError("Replicas.predict: DiffDelRNN replicas need a delay trajectory")
+        stacks = self._infer_stacks()
+        self.initialize_hidden(1)
+        zeros = torch.zeros((R, 1, START_LEN), device=self.device)
+        if self.diffdel:
+            deferred, self._dl.defer_check = self._dl.defer_check, True
+        try:
+            if self.diffdel:
+                self.infer(zeros, zeros, _stacks=stacks)
+                self._dl.buffer = self._dl.buffer.repeat_interleave(Bper, dim=0) if Bper != 1 else self._dl.buffer
+            else:
+                self.infer(zeros, _stacks=stacks)
+            if Bper != 1:
+                self.hidden = self.hidden.repeat_interleave(Bper, dim=1)
+            self._share()
+
+            def run(sl):
+                if self.diffdel:
+                    return self.infer(input[:, :, sl], d_traj[:, :, sl], _stacks=stacks)
+                return (self.infer(input[:, :, sl], _stacks=stacks),)
+            if segment_length is None:
+                outs = run(slice(None))
+            else:
+                outs = tuple(torch.empty(input.shape, device=input.device, dtype=torch.float32) for _ in range(2 if self.diffdel else 1))
+                for i in range(int(np.ceil(T / segment_length))):
+                    sl = slice(i * segment_length, (i + 1) * segment_length)
+                    for o, v in zip(outs, run(sl)):
+                        o[:, :, sl] = v
+        finally:
+            if self.diffdel:
+                self._dl.defer_check = deferred
+        if self.diffdel:
+            if not deferred:
+                self._dl.raise_if_violated()
+            return outs
+        return outs[0]
 
 
 # ------------------------------------------------------------------------------------------

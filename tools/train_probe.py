@@ -10,7 +10,11 @@ With --replicas R[,R...]: one TBPTT window of ntm_amd.Replicas (R models at B = 
 beside R sequential windows of the single-model path in the same process -- whole window, window without the optimizer steps, and
 the optimizer steps alone, with one optimizer per replica and with one optimizer over all parameters; median and range over
 --reps repetitions of --iters windows.  GRU: L = 1024; --model diffdel: L = 2048, D = 11 001.
-usage: python tools/train_probe.py [--model gru|diffdel] [--iters N] [--rocprof] [--replicas 1,2,4,8 [--reps N]]"""
+With --validate --replicas R[,R...]: one validation batch of the reference's shape (code/train.py:148: 6 segments of 441 000
+samples) through Replicas.validate (one launch of the low-latency kernel for all R models) beside R sequential single-model
+validate() calls on the same data, host time from call to return (validate ends with the losses on the host); the forms alternate
+within a repetition, median and range over --reps repetitions.  --model diffdel: D = 11 001, warm-up 16 384.
+usage: python tools/train_probe.py [--model gru|diffdel] [--iters N] [--rocprof] [--replicas 1,2,4,8 [--reps N] [--validate]]"""
 import argparse
 import glob
 import json
@@ -196,6 +200,60 @@ def replicas(R, iters, reps, model="gru", B=32):
     return {name: [statistics.median(v), min(v), max(v)] for name, v in times.items()}
 
 
+VAL_B, VAL_T = 6, 441000
+
+
+class _ValLoader(list):
+    """What validate() needs of a DataLoader: len(), (x, t, meta) batches, .dataset.fs / .dataset.delay_analyzer.max_delay."""
+
+    def __init__(self, batches, fs, max_delay_s):
+        super().__init__(batches)
+        self.dataset = type("DS", (), {"fs": fs, "delay_analyzer": type("DA", (), {"max_delay": max_delay_s})})
+
+
+def validate_probe(R, reps, model="gru", B=VAL_B, T=VAL_T):
+    """-> {name: [median, min, max] ms per validation batch}: Replicas.validate of R models against R sequential validate()
+    calls of the same models on the same batch (and that the two gave the same losses)."""
+    import statistics
+    import time
+    import torch
+    import ntm_amd
+    torch.manual_seed(0)
+    dd = model == "diffdel"
+    fs = 44100
+    ms = [(ntm_amd.DiffDelRNN(1, 64, 1, max_delay=DD_D - 1) if dd else ntm_amd.RNN(1, 64, 1)).cuda() for _ in range(R)]
+    x = torch.rand(B, 1, T, device="cuda") - 0.5
+    n = torch.arange(T, dtype=torch.float32)
+    meta = {"delay_trajectory": ((5500.0 + 4000.0 * torch.sin(n / 7000.0) + 20.0 * torch.sin(n / 300.0)) / fs).expand(B, -1).contiguous().cuda()}
+    loader = _ValLoader([(x, 0.5 * x, meta)], fs, (DD_D - 1) / fs)
+    loss_fcn = ntm_amd.ESRLoss()
+    g = ntm_amd.Replicas(ms)
+    out = {}
+
+    def group():
+        out["group"] = [v for v, _ in g.validate(loader, loss_fcn, store_examples=False)]
+
+    def single():
+        out["single"] = [m.validate(loader, loss_fcn, store_examples=False)[0] for m in ms]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    runs = {"group": group, f"{R} x single": single}
+    for fn in runs.values():
+        fn()                            # warm-up: allocations, the first launch of every kernel
+    times = {name: [] for name in runs}
+    for _ in range(reps):               # the forms alternate within a repetition, so that drift of the machine hits all alike
+        for name, fn in runs.items():
+            times[name].append(wall(fn))
+    res = {name: [statistics.median(v), min(v), max(v)] for name, v in times.items()}
+    res["same losses"] = out["group"] == out["single"]
+    return res
+
+
 def miopen(B, iters, native=False):
     """torch.nn.GRU + Linear training; `native`: with torch's own GRU cell kernels instead of MIOpen (cudnn backend off)."""
     import torch
@@ -223,15 +281,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rocprof", action="store_true")
-    ap.add_argument("--child", choices=["engine", "miopen", "native", "diffdel", "replicas"])
+    ap.add_argument("--child", choices=["engine", "miopen", "native", "diffdel", "replicas", "validate"])
     ap.add_argument("--replicas", default=None, help="comma-separated replica counts, e.g. 1,2,4,8")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="32,4096")
     ap.add_argument("--model", choices=["gru", "diffdel"], default="gru")
+    ap.add_argument("--validate", action="store_true", help="with --replicas: one grouped validation batch against R single ones")
     a = ap.parse_args()
     sizes = [int(b) for b in a.sizes.split(",")]
     if a.child == "diffdel":
         print(json.dumps({str(B): engine_diffdel(B, a.iters) for B in sizes}))
+        return
+    if a.child == "validate":
+        print(json.dumps({str(R): validate_probe(R, a.reps, a.model) for R in map(int, a.replicas.split(","))}))
         return
     if a.child == "replicas":
         print(json.dumps({str(R): replicas(R, a.iters, a.reps, a.model) for R in map(int, a.replicas.split(","))}))
@@ -261,6 +323,23 @@ def main():
         if r.returncode != 0:
             raise SystemExit(f"{what} exited with status {r.returncode}; nothing more is started\n{r.stderr[-2000:]}")
         return r
+
+    if a.replicas and a.validate:
+        r = child([sys.executable, __file__, "--child", "validate", "--replicas", a.replicas, "--reps", str(a.reps), "--model", a.model],
+                  "validate child")
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        what = f"DiffDelGRU-HS[64], D = {DD_D}" if a.model == "diffdel" else "GRU-HS[64]"
+        print(f"{what}, one validation batch of {VAL_B} x {VAL_T} per replica (ESRLoss); ms from call to return, median [min .. max] "
+              f"of {a.reps} repetitions:")
+        for R, rows in res.items():
+            same = rows.pop("same losses")
+            print(f"R = {R}   (grouped losses == single losses: {same})")
+            for name, (med, lo, hi) in rows.items():
+                print(f"  {name:<28} {med:9.2f}  [{lo:.2f} .. {hi:.2f}]")
+        if a.rocprof:
+            for R in a.replicas.split(","):
+                _rocprof(child, a, [R], "validate", ["--replicas", R, "--reps", "1", "--model", a.model])
+        return
 
     if a.replicas:
         r = child([sys.executable, __file__, "--child", "replicas", "--replicas", a.replicas, "--iters", str(a.iters), "--reps",
@@ -318,7 +397,7 @@ def _rocprof(child, a, sizes, kind, extra=()):
                 raise SystemExit("rocprofv3 wrote no kernel stats")
             krows = list(csv.DictReader(open(stats[0])))
         total = sum(float(x["TotalDurationNs"]) for x in krows)
-        print(f"\nper-kernel time of the {kind} child at {'R' if kind == 'replicas' else 'B'} = {B} (all of its windows):")
+        print(f"\nper-kernel time of the {kind} child at {'R' if kind in ('replicas', 'validate') else 'B'} = {B} (all of its windows):")
         for x in sorted(krows, key=lambda x: -float(x["TotalDurationNs"]))[:12]:
             print(f"{float(x['TotalDurationNs']) / total * 100:6.1f}%  {int(x['Calls']):6d} calls  "
                   f"{float(x['AverageNs']) / 1e3:10.1f} us avg  {x['Name'][:90]}")
