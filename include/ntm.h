@@ -413,6 +413,8 @@ int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, flo
  * stacks: w_ih [R,192,1], w_hh [R,192,64], b_ih, b_hh [R,192], w_o [R,1,64], b_o [R,1] (may be null).  Everything is per
  * stream and free of atomics, so every replica's outputs are bit-identical to those of the single-model entry point above
  * called on that replica's slice with that replica's parameters.  R and Bper must be positive (R <= 65535).
+ * The reduction and the two loss adjoints are the same kernels either way: ntm_gru_train_reduce, ntm_esr_grad and
+ * ntm_esr_dcpre_grad run them with R = 1, Bper = B (and, unlike the calls below, accept B = 0).
  */
 
 /* ntm_gru_train_forward for R replicas: x, y, h_state [R*Bper, .], ws = ntm_gru_train_workspace_floats(R * Bper, T). */

@@ -1,6 +1,7 @@
 // Training kernels for GRU-HS[64] (input_size = output_size = 1, no skip, exact fp32): what RNN.train_epoch needs
 // (code/model.py:90-161) -- the forward with its activations saved, the backward through time (BPTT), the deterministic
-// reduction of the per-stream gradients, and the adjoints of the ESR / DCPreESR losses (code/train.py:173-176).
+// reduction of the per-stream gradients, and the adjoints of the ESR / DCPreESR losses (code/train.py:173-176).  The reduction
+// and the loss adjoints exist once, for R stacked replicas; one model is their R = 1 (one grid row, bper = B).
 //
 // GRU as torch defines it, with gh_n = W_hn h_{t-1} + b_hn:
 //   r, z = sigma(.),  n = tanh(W_in x + b_in + r o gh_n),  h_t = n + z o (h_{t-1} - n),  y_t = w_o . h_t + b_o.
@@ -242,18 +243,8 @@ __global__ __launch_bounds__(256) void gru_train_bwd_kernel(const float *__restr
     if (tid == 0) ps[OFF_BO] = (float)dbo;
 }
 
-// (c) The parameter gradients: the B per-stream partials of every entry added in stream order, in fp64 (no atomics).
-__global__ __launch_bounds__(256) void gru_train_reduce_kernel(const float *__restrict__ part, int64_t B, float *__restrict__ grad)
-{
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= NGRAD) return;
-    double acc = 0.0;
-    for (int64_t b = 0; b < B; ++b) acc += (double)part[b * NGRAD + e];
-    grad[e] = (float)acc;
-}
-
-// The same for R replicas of bper streams each (grid row = replica): every entry adds its replica's bper rows in stream
-// order, so grad[r] has the bits gru_train_reduce_kernel gives on that replica's rows alone.
+// (c) The parameter gradients of R models of bper streams each (grid row = model; the single model is R = 1, bper = B): every
+// entry adds its model's bper per-stream partials in stream order, in fp64 (no atomics).  bper = 0 writes zeros.
 __global__ __launch_bounds__(256) void gru_train_reduce_replicas_kernel(const float *__restrict__ part, int64_t bper,
                                                                         float *__restrict__ grad)
 {
@@ -266,20 +257,9 @@ __global__ __launch_bounds__(256) void gru_train_reduce_replicas_kernel(const fl
     grad[r * NGRAD + e] = (float)acc;
 }
 
-// (d) Loss adjoints.  ESR (code/train.py:176): L = (S_e / n) / (S_t / n + eps) with whole-batch sums S (sums2 = [S_e, S_t],
-// fp64, from ntm_esr_sums) -> dL/dy = 2 (y - t) / (n (S_t / n + eps)), times the upstream gradient gout[0].
-__global__ __launch_bounds__(256) void esr_grad_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t N,
-                                                       const double *__restrict__ sums2, const float *__restrict__ gout, double eps,
-                                                       float *__restrict__ dy)
-{
-    const double n = (double)N;
-    const double c = (double)gout[0] * 2.0 / (n * (sums2[1] / n + eps));
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
-        dy[i] = (float)(c * ((double)y[i] - (double)t[i]));
-}
-
-// R losses at once (grid row = replica): replica r's N = bper * T elements with ITS sums, upstream gradient and n -- per
-// element the arithmetic of esr_grad_kernel on that slice.
+// (d) Loss adjoints, for R losses at once (the single loss is R = 1, bper = B).  ESR (code/train.py:176): L = (S_e / n) /
+// (S_t / n + eps) with whole-batch sums S (sums2 = [S_e, S_t], fp64, from ntm_esr_sums) -> dL/dy = 2 (y - t) / (n (S_t / n + eps)),
+// times the upstream gradient.  Grid row = replica r: its N = bper * T elements with ITS sums2[r], gout[r] and n.
 __global__ __launch_bounds__(256) void esr_grad_replicas_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t N,
                                                                 const double *__restrict__ sums2, const float *__restrict__ gout,
                                                                 double eps, float *__restrict__ dy)
@@ -293,28 +273,24 @@ __global__ __launch_bounds__(256) void esr_grad_replicas_kernel(const float *__r
         dr[i] = (float)(c * ((double)yr[i] - (double)tr[i]));
 }
 
-// DCPreESR (code/train.py:174): the same on the DC-blocked signals, f = (1 - z^-1)/(1 - R z^-1) from zero state.  With
+// DCPreESR (code/train.py:174): the same on the DC-blocked signals, f = (1 - z^-1)/(1 - R z^-1), R = pole, from zero state.  With
 // e_f = f(y - t) and v = 2 e_f / (n (S_tf / n + eps)), dL/dy = f^T v: the anti-causal one-pole q[t] = v[t] + R q[t+1] followed
 // by the adjoint first difference dy[t] = q[t] - q[t+1].  One thread per stream, fp64 recursions; e_f is parked in dy between
-// the causal and the anti-causal pass.
-// REP: B = R replicas of bper streams; stream b takes sums2 [R,2], gout [R] and n = bper * T of replica b / bper.
-template <bool REP>
+// the causal and the anti-causal pass.  The B streams are replicas of bper each: stream b takes sums2 [.,2], gout [.] and
+// n = bper * T of replica b / bper (the single loss: bper = B, replica 0).
 __global__ __launch_bounds__(64) void esr_dcpre_grad_kernel(const float *__restrict__ y, const float *__restrict__ t, int64_t B,
-                                                            int64_t T, float R, const double *__restrict__ sums2,
+                                                            int64_t T, float pole, const double *__restrict__ sums2,
                                                             const float *__restrict__ gout, double eps, float *__restrict__ dy,
                                                             const int64_t bper)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    if constexpr (REP) {
-        const int64_t rep = b / bper;
-        sums2 += 2 * rep;
-        gout += rep;
-        B = bper;
-    }
+    const int64_t rep = b / bper;
+    sums2 += 2 * rep;
+    gout += rep;
     const float *yb = y + b * T, *tb = t + b * T;
     float *db = dy + b * T;
-    const double Rd = (double)R;
+    const double Rd = (double)pole;
     double prev = 0.0, ef = 0.0;
 #pragma unroll 8
     for (int64_t i = 0; i < T; ++i) {
@@ -323,7 +299,7 @@ __global__ __launch_bounds__(64) void esr_dcpre_grad_kernel(const float *__restr
         prev = wv;
         db[i] = (float)ef;
     }
-    const double n = (double)(B * T);
+    const double n = (double)(bper * T);
     const double c = (double)gout[0] * 2.0 / (n * (sums2[1] / n + eps));
     double q1 = 0.0;                               // q[t + 1]
 #pragma unroll 8
@@ -533,34 +509,11 @@ hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float
     return hipGetLastError();
 }
 
-hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream)
-{
-    hipLaunchKernelGGL(gru_train_reduce_kernel, dim3((NGRAD + 255) / 256), dim3(256), 0, stream, part, B, grad);
-    return hipGetLastError();
-}
-
+// the launchers of (c) and (d): R models / losses of bper streams each; the single-model entry points pass R = 1, bper = B
 hipError_t launch_gru_train_reduce_replicas(const float *part, int64_t R, int64_t bper, float *grad, hipStream_t stream)
 {
-    if (R == 0) return hipSuccess;
+    if (R == 0) return hipSuccess;      // bper = 0 is launched: grad <- 0
     hipLaunchKernelGGL(gru_train_reduce_replicas_kernel, dim3((NGRAD + 255) / 256, (unsigned)R), dim3(256), 0, stream, part, bper, grad);
-    return hipGetLastError();
-}
-
-hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const double *sums2, const float *gout, double eps, float *dy,
-                           hipStream_t stream)
-{
-    if (N == 0) return hipSuccess;
-    const int64_t blocks = (N + 255) / 256 < 4096 ? (N + 255) / 256 : 4096;
-    hipLaunchKernelGGL(esr_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, y, t, N, sums2, gout, eps, dy);
-    return hipGetLastError();
-}
-
-hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2,
-                                 const float *gout, double eps, float *dy, hipStream_t stream)
-{
-    if (B == 0 || T == 0) return hipSuccess;
-    hipLaunchKernelGGL(esr_dcpre_grad_kernel<false>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, y, t, B, T, R, sums2, gout,
-                       eps, dy, (int64_t)0);
     return hipGetLastError();
 }
 
@@ -580,8 +533,8 @@ hipError_t launch_esr_dcpre_grad_replicas(const float *y, const float *t, int64_
 {
     const int64_t B = R * bper;
     if (B == 0 || T == 0) return hipSuccess;
-    hipLaunchKernelGGL(esr_dcpre_grad_kernel<true>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, y, t, B, T, pole, sums2, gout,
-                       eps, dy, bper);
+    hipLaunchKernelGGL(esr_dcpre_grad_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, y, t, B, T, pole, sums2, gout, eps,
+                       dy, bper);
     return hipGetLastError();
 }
 

@@ -618,68 +618,7 @@ int64_t ntm_gru_train_workspace_floats(int64_t B, int64_t T)
     return (B < 0 || T < 0) ? 0 : B * T * NTM_TRAIN_SAVED * NTM_HIDDEN;
 }
 
-int ntm_gru_train_forward(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
-                          const float *b_o, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
-                          int64_t y_stride_b, float *h_state, float *ws, void *stream)
-{
-    static_assert(NTM_TRAIN_SAVED * NTM_HIDDEN == 5 * ntm::kH, "workspace layout");
-    if (B < 0 || T < 0) return fail(NTM_EINVAL, "ntm_gru_train_forward: negative B or T");
-    if (B == 0 || T == 0) return NTM_OK;
-    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y || !ws) return fail(NTM_EINVAL, "ntm_gru_train_forward: null pointer");
-    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, "ntm_gru_train_forward: row stride below T");
-    if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_gru_train_forward: at most 2^31 - 1 streams per call");
-    if (x == y) return fail(NTM_EINVAL, "ntm_gru_train_forward: y must not alias x");
-    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, B, T, x_stride_b, y_stride_b, nullptr, 0, 0};
-    hipError_t e = ntm::launch_gru_train_fwd(a, ws, 0, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_forward");
-}
-
-int ntm_gru_train_backward(const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b, const float *ws,
-                           const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t B, int64_t T, float *dh0,
-                           float *part, void *stream)
-{
-    if (B < 0 || T < 0) return fail(NTM_EINVAL, "ntm_gru_train_backward: negative B or T");
-    if (B == 0) return NTM_OK;
-    if (!w_hh || !w_o || !part || (T > 0 && (!x || !ws))) return fail(NTM_EINVAL, "ntm_gru_train_backward: null pointer");
-    if (x_stride_b < T || (dy && dy_stride_b < T)) return fail(NTM_EINVAL, "ntm_gru_train_backward: row stride below T");
-    if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_gru_train_backward: at most 2^31 - 1 streams per call");
-    static_assert(NTM_TRAIN_GRAD_FLOATS == 12929, "parameter count of GRU(1, 64) + Linear(64, 1)");
-    if (ntm::train_grad_floats() != NTM_TRAIN_GRAD_FLOATS) return fail(NTM_EINVAL, "ntm_gru_train_backward: layout mismatch");
-    hipError_t e = ntm::launch_gru_train_bwd(w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, B, T, dh0, part, 0, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_backward");
-}
-
-int ntm_gru_train_reduce(const float *part, int64_t B, float *grad, void *stream)
-{
-    if (B < 0) return fail(NTM_EINVAL, "ntm_gru_train_reduce: negative B");
-    if (!grad || (B > 0 && !part)) return fail(NTM_EINVAL, "ntm_gru_train_reduce: null pointer");
-    hipError_t e = ntm::launch_gru_train_reduce(part, B, grad, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_reduce");
-}
-
-int ntm_esr_grad(const float *y, const float *t, int64_t B, int64_t T, const double *sums2, const float *gout, double eps,
-                 float *dy, void *stream)
-{
-    if (B < 0 || T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_grad: bad size or eps");
-    if (B == 0 || T == 0) return NTM_OK;
-    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_grad: null pointer");
-    hipError_t e = ntm::launch_esr_grad(y, t, B * T, sums2, gout, eps, dy, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_grad");
-}
-
-int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2, const float *gout,
-                       double eps, float *dy, void *stream)
-{
-    if (B < 0 || T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: bad size or eps");
-    if (!(R >= 0.0f && R < 1.0f)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: R must be in [0,1)");
-    if (B == 0 || T == 0) return NTM_OK;
-    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: null pointer");
-    if (B > 0x7fffffff) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad: at most 2^31 - 1 streams per call");
-    hipError_t e = ntm::launch_esr_dcpre_grad(y, t, B, T, R, sums2, gout, eps, dy, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_dcpre_grad");
-}
-
-// ---- R replicas of the training configuration in one launch each (stream s of R * Bper belongs to replica s / Bper)
+// R replicas in one launch each (stream s of R * Bper belongs to replica s / Bper): what every `_replicas` entry refuses first
 static int bad_replicas(const char *who, int64_t R, int64_t Bper)
 {
     const std::string w(who);
@@ -689,42 +628,142 @@ static int bad_replicas(const char *who, int64_t R, int64_t Bper)
     return NTM_OK;
 }
 
+// Each single-model entry point and its `_replicas` form share one body: `rep` says which of the two `who` is.  The single form
+// passes R = 1, Bper = B and keeps its own refusals and its B == 0 / T == 0 early returns (a replica call has Bper > 0).
+static int bad_train_sizes(const char *who, bool rep, int64_t R, int64_t Bper, int64_t T)
+{
+    if (!rep) return (Bper < 0 || T < 0) ? fail(NTM_EINVAL, std::string(who) + ": negative B or T") : NTM_OK;
+    if (int rc = bad_replicas(who, R, Bper)) return rc;
+    return T < 0 ? fail(NTM_EINVAL, std::string(who) + ": negative T") : NTM_OK;
+}
+
+static int train_forward_impl(const char *who, bool rep, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                              const float *w_o, const float *b_o, const float *x, float *y, int64_t R, int64_t Bper, int64_t T,
+                              int64_t x_stride_b, int64_t y_stride_b, float *h_state, float *ws, void *stream)
+{
+    static_assert(NTM_TRAIN_SAVED * NTM_HIDDEN == 5 * ntm::kH, "workspace layout");
+    const std::string w(who);
+    if (int rc = bad_train_sizes(who, rep, R, Bper, T)) return rc;
+    if (Bper == 0 || T == 0) return NTM_OK;
+    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y || !ws) return fail(NTM_EINVAL, w + ": null pointer");
+    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, w + ": row stride below T");
+    if (!rep && Bper > 0x7fffffff) return fail(NTM_EINVAL, w + ": at most 2^31 - 1 streams per call");
+    if (x == y) return fail(NTM_EINVAL, w + ": y must not alias x");
+    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, R * Bper, T, x_stride_b, y_stride_b, nullptr, 0, 0};
+    hipError_t e = ntm::launch_gru_train_fwd(a, ws, rep ? Bper : 0, (hipStream_t)stream);      // 0: the plain kernel
+    return e == hipSuccess ? NTM_OK : hip_fail(e, who);
+}
+
+static int train_backward_impl(const char *who, bool rep, const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b,
+                               const float *ws, const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t R, int64_t Bper,
+                               int64_t T, float *dh0, float *part, void *stream)
+{
+    const std::string w(who);
+    if (int rc = bad_train_sizes(who, rep, R, Bper, T)) return rc;
+    if (Bper == 0) return NTM_OK;
+    if (!w_hh || !w_o || !part || (T > 0 && (!x || !ws))) return fail(NTM_EINVAL, w + ": null pointer");
+    if (x_stride_b < T || (dy && dy_stride_b < T)) return fail(NTM_EINVAL, w + ": row stride below T");
+    if (!rep && Bper > 0x7fffffff) return fail(NTM_EINVAL, w + ": at most 2^31 - 1 streams per call");
+    static_assert(NTM_TRAIN_GRAD_FLOATS == 12929, "parameter count of GRU(1, 64) + Linear(64, 1)");
+    if (ntm::train_grad_floats() != NTM_TRAIN_GRAD_FLOATS) return fail(NTM_EINVAL, w + ": layout mismatch");
+    hipError_t e = ntm::launch_gru_train_bwd(w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, R * Bper, T, dh0, part,
+                                             rep ? Bper : 0, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, who);
+}
+
+// one model with B = 0: launched all the same, grad <- 0
+static int train_reduce_impl(const char *who, bool rep, const float *part, int64_t R, int64_t Bper, float *grad, void *stream)
+{
+    const std::string w(who);
+    if (rep) {
+        if (int rc = bad_replicas(who, R, Bper)) return rc;
+    } else if (Bper < 0) return fail(NTM_EINVAL, w + ": negative B");
+    if (!grad || (Bper > 0 && !part)) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_gru_train_reduce_replicas(part, R, Bper, grad, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, who);
+}
+
+// the adjoint of ESR (pole null) or of DCPreESR with that pole
+static int loss_grad_impl(const char *who, bool rep, const float *y, const float *t, int64_t R, int64_t Bper, int64_t T,
+                          const float *pole, const double *sums2, const float *gout, double eps, float *dy, void *stream)
+{
+    const std::string w(who);
+    if (rep)
+        if (int rc = bad_replicas(who, R, Bper)) return rc;
+    if (Bper < 0 || T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, w + ": bad size or eps");
+    if (pole && !(*pole >= 0.0f && *pole < 1.0f)) return fail(NTM_EINVAL, w + ": R must be in [0,1)");
+    if (Bper == 0 || T == 0) return NTM_OK;
+    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, w + ": null pointer");
+    if (pole && !rep && Bper > 0x7fffffff) return fail(NTM_EINVAL, w + ": at most 2^31 - 1 streams per call");
+    hipError_t e = pole ? ntm::launch_esr_dcpre_grad_replicas(y, t, R, Bper, T, *pole, sums2, gout, eps, dy, (hipStream_t)stream)
+                        : ntm::launch_esr_grad_replicas(y, t, R, Bper * T, sums2, gout, eps, dy, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, who);
+}
+
+int ntm_gru_train_forward(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                          const float *b_o, const float *x, float *y, int64_t B, int64_t T, int64_t x_stride_b,
+                          int64_t y_stride_b, float *h_state, float *ws, void *stream)
+{
+    return train_forward_impl("ntm_gru_train_forward", false, w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, 1, B, T, x_stride_b, y_stride_b,
+                              h_state, ws, stream);
+}
+
 int ntm_gru_train_forward_replicas(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
                                    const float *b_o, const float *x, float *y, int64_t R, int64_t Bper, int64_t T,
                                    int64_t x_stride_b, int64_t y_stride_b, float *h_state, float *ws, void *stream)
 {
-    if (int rc = bad_replicas("ntm_gru_train_forward_replicas", R, Bper)) return rc;
-    if (T < 0) return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: negative T");
-    if (T == 0) return NTM_OK;
-    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !y || !ws)
-        return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: null pointer");
-    if (x_stride_b < T || y_stride_b < T) return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: row stride below T");
-    if (x == y) return fail(NTM_EINVAL, "ntm_gru_train_forward_replicas: y must not alias x");
-    ntm::GruArgs a{w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, h_state, R * Bper, T, x_stride_b, y_stride_b, nullptr, 0, 0};
-    hipError_t e = ntm::launch_gru_train_fwd(a, ws, Bper, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_forward_replicas");
+    return train_forward_impl("ntm_gru_train_forward_replicas", true, w_ih, w_hh, b_ih, b_hh, w_o, b_o, x, y, R, Bper, T, x_stride_b,
+                              y_stride_b, h_state, ws, stream);
+}
+
+int ntm_gru_train_backward(const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b, const float *ws,
+                           const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t B, int64_t T, float *dh0,
+                           float *part, void *stream)
+{
+    return train_backward_impl("ntm_gru_train_backward", false, w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, 1, B, T, dh0, part,
+                               stream);
 }
 
 int ntm_gru_train_backward_replicas(const float *w_hh, const float *w_o, const float *x, int64_t x_stride_b, const float *ws,
                                     const float *dy, int64_t dy_stride_b, const float *dh_T, int64_t R, int64_t Bper, int64_t T,
                                     float *dh0, float *part, void *stream)
 {
-    if (int rc = bad_replicas("ntm_gru_train_backward_replicas", R, Bper)) return rc;
-    if (T < 0) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: negative T");
-    if (!w_hh || !w_o || !part || (T > 0 && (!x || !ws))) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: null pointer");
-    if (x_stride_b < T || (dy && dy_stride_b < T)) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: row stride below T");
-    if (ntm::train_grad_floats() != NTM_TRAIN_GRAD_FLOATS) return fail(NTM_EINVAL, "ntm_gru_train_backward_replicas: layout mismatch");
-    hipError_t e = ntm::launch_gru_train_bwd(w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, R * Bper, T, dh0, part, Bper,
-                                             (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_backward_replicas");
+    return train_backward_impl("ntm_gru_train_backward_replicas", true, w_hh, w_o, x, x_stride_b, ws, dy, dy_stride_b, dh_T, R, Bper, T,
+                               dh0, part, stream);
+}
+
+int ntm_gru_train_reduce(const float *part, int64_t B, float *grad, void *stream)
+{
+    return train_reduce_impl("ntm_gru_train_reduce", false, part, 1, B, grad, stream);
 }
 
 int ntm_gru_train_reduce_replicas(const float *part, int64_t R, int64_t Bper, float *grad, void *stream)
 {
-    if (int rc = bad_replicas("ntm_gru_train_reduce_replicas", R, Bper)) return rc;
-    if (!grad || !part) return fail(NTM_EINVAL, "ntm_gru_train_reduce_replicas: null pointer");
-    hipError_t e = ntm::launch_gru_train_reduce_replicas(part, R, Bper, grad, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_gru_train_reduce_replicas");
+    return train_reduce_impl("ntm_gru_train_reduce_replicas", true, part, R, Bper, grad, stream);
+}
+
+int ntm_esr_grad(const float *y, const float *t, int64_t B, int64_t T, const double *sums2, const float *gout, double eps,
+                 float *dy, void *stream)
+{
+    return loss_grad_impl("ntm_esr_grad", false, y, t, 1, B, T, nullptr, sums2, gout, eps, dy, stream);
+}
+
+int ntm_esr_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, const double *sums2, const float *gout,
+                          double eps, float *dy, void *stream)
+{
+    return loss_grad_impl("ntm_esr_grad_replicas", true, y, t, R, Bper, T, nullptr, sums2, gout, eps, dy, stream);
+}
+
+int ntm_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2, const float *gout,
+                       double eps, float *dy, void *stream)
+{
+    return loss_grad_impl("ntm_esr_dcpre_grad", false, y, t, 1, B, T, &R, sums2, gout, eps, dy, stream);
+}
+
+int ntm_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, float pole, const double *sums2,
+                                const float *gout, double eps, float *dy, void *stream)
+{
+    return loss_grad_impl("ntm_esr_dcpre_grad_replicas", true, y, t, R, Bper, T, &pole, sums2, gout, eps, dy, stream);
 }
 
 int ntm_loss_sums_replicas(const double *rows, int64_t R, int64_t Bper, int splits, double *sums2, void *stream)
@@ -734,29 +773,6 @@ int ntm_loss_sums_replicas(const double *rows, int64_t R, int64_t Bper, int spli
     if (!rows || !sums2) return fail(NTM_EINVAL, "ntm_loss_sums_replicas: null pointer");
     hipError_t e = ntm::launch_loss_sums_replicas(rows, R, Bper, splits, sums2, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_loss_sums_replicas");
-}
-
-int ntm_esr_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, const double *sums2, const float *gout,
-                          double eps, float *dy, void *stream)
-{
-    if (int rc = bad_replicas("ntm_esr_grad_replicas", R, Bper)) return rc;
-    if (T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_grad_replicas: bad size or eps");
-    if (T == 0) return NTM_OK;
-    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_grad_replicas: null pointer");
-    hipError_t e = ntm::launch_esr_grad_replicas(y, t, R, Bper * T, sums2, gout, eps, dy, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_grad_replicas");
-}
-
-int ntm_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t Bper, int64_t T, float pole, const double *sums2,
-                                const float *gout, double eps, float *dy, void *stream)
-{
-    if (int rc = bad_replicas("ntm_esr_dcpre_grad_replicas", R, Bper)) return rc;
-    if (T < 0 || !(eps >= 0.0)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad_replicas: bad size or eps");
-    if (!(pole >= 0.0f && pole < 1.0f)) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad_replicas: R must be in [0,1)");
-    if (T == 0) return NTM_OK;
-    if (!y || !t || !sums2 || !gout || !dy) return fail(NTM_EINVAL, "ntm_esr_dcpre_grad_replicas: null pointer");
-    hipError_t e = ntm::launch_esr_dcpre_grad_replicas(y, t, R, Bper, T, pole, sums2, gout, eps, dy, (hipStream_t)stream);
-    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_esr_dcpre_grad_replicas");
 }
 
 // inference of R stacked replicas: ALWAYS the low-latency kernel (NTM_GRU_LAT), whatever R * Bper is -- NTM_GRU_AUTO's hand-over

@@ -82,17 +82,13 @@ hipError_t launch_gru_train_fwd(const GruArgs &a, float *ws, int64_t bper, hipSt
 hipError_t launch_gru_train_bwd(const float *w_hh, const float *w_o, const float *x, int64_t xs, const float *ws, const float *dy,
                                 int64_t dys, const float *dh_T, int64_t B, int64_t T, float *dh0, float *part, int64_t bper,
                                 hipStream_t stream);
+// the reduction and the loss adjoints: R models of bper streams each (one model: R = 1, bper = B)
 hipError_t launch_gru_train_reduce_replicas(const float *part, int64_t R, int64_t bper, float *grad, hipStream_t stream);
 hipError_t launch_esr_grad_replicas(const float *y, const float *t, int64_t R, int64_t N, const double *sums2, const float *gout,
                                     double eps, float *dy, hipStream_t stream);
 hipError_t launch_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t bper, int64_t T, float pole,
                                           const double *sums2, const float *gout, double eps, float *dy, hipStream_t stream);
 hipError_t launch_loss_sums_replicas(const double *rows, int64_t R, int64_t bper, int splits, double *out, hipStream_t stream);
-hipError_t launch_gru_train_reduce(const float *part, int64_t B, float *grad, hipStream_t stream);
-hipError_t launch_esr_grad(const float *y, const float *t, int64_t N, const double *sums2, const float *gout, double eps, float *dy,
-                           hipStream_t stream);
-hipError_t launch_esr_dcpre_grad(const float *y, const float *t, int64_t B, int64_t T, float R, const double *sums2,
-                                 const float *gout, double eps, float *dy, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
                             int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm

@@ -181,6 +181,33 @@ class _GRUHead(torch.nn.Module):
             y2d += x2d
 
 
+# ---- what every train_epoch / validate does to a batch before its loop (the single models and Replicas alike)
+def _audio_channel(input, target, device):
+    """(input, target) (B,C,T) -> channel 0 of both on `device`: only the audio channel counts for training and for the loss."""
+    if input.shape[1] > 1:
+        input, target = input[:, :1, :], target[:, :1, :]
+    return input.to(device), target.to(device)
+
+
+def _delay_samples(extra, fs, who):
+    """The delay trajectory (B,1,T) in samples -- the fp32 product d_seconds * fs, as the reference forms it -- from the third item
+    of a batch: the reference's meta dict with 'delay_trajectory' (B,T) in seconds, or SegmentFeeder.batches' d_seconds (B,C,T)."""
+    if isinstance(extra, dict):
+        d_traj = extra["delay_trajectory"].float()
+        return d_traj.unsqueeze(1) * fs
+    if extra is not None:
+        return extra[:, :1, :].float() * fs
+    raise RuntimeError(f"{who}: the batch carries no delay trajectory")
+
+
+def _diffdel_warmup(dataset):
+    """Warm-up length of a DiffDel dataset in samples: nextpow2(int(max_delay * fs)), max_delay in seconds from
+    `delay_analyzer.max_delay` (the reference's dataset) or `max_delay` (SegmentFeeder)."""
+    from .utilities import nextpow2
+    max_delay = dataset.delay_analyzer.max_delay if hasattr(dataset, "delay_analyzer") else dataset.max_delay
+    return nextpow2(int(max_delay * dataset.fs))
+
+
 class RNN(_GRUHead):
     """GRU + fully connected output layer (reference: code/model.py:20-246)."""
 
@@ -374,10 +401,7 @@ class RNN(_GRUHead):
         num_batches = 0             # counted, so that a generator (SegmentFeeder.batches) serves as well as a DataLoader
         epoch_loss = 0
         for _, batch in enumerate(dataloader):
-            input, target = batch[0], batch[1]
-            if input.shape[1] > 1:  # only the audio channel counts for training
-                input, target = input[:, :1, :], target[:, :1, :]
-            input, target = input.to(device), target.to(device)
+            input, target = _audio_channel(batch[0], batch[1], device)
 
             self.initialize_hidden()
             num_minibatches = (input.shape[2] - TBPTT_INIT) // TBPTT_LEN
@@ -417,9 +441,7 @@ class RNN(_GRUHead):
         examples = []
         for _, batch in enumerate(dataloader):
             input, target, _ = batch
-            if input.shape[1] > 1:            # only the audio channel counts for the loss
-                input, target = input[:, :1, :], target[:, :1, :]
-            input, target = input.to(device), target.to(device)
+            input, target = _audio_channel(input, target, device)
             self.initialize_hidden()
             _ = self.forward(input[:, :, :INIT_LEN])
             input = input[:, :, INIT_LEN:]
@@ -772,12 +794,10 @@ class DiffDelRNN(_GRUHead):
         the fp32 product d_seconds * fs, as the reference forms them.
         Supported: DiffDelRNN(1, 64, 1, skip=False) on a HIP device (RuntimeError otherwise).  On entry it sets requires_grad on
         the GRU and head parameters."""
-        from .utilities import nextpow2
         self._check_trainable("DiffDelRNN.train_epoch")
         dataset = dataloader.dataset if dataset is None else dataset
         fs = dataset.fs
-        max_delay = dataset.delay_analyzer.max_delay if hasattr(dataset, "delay_analyzer") else dataset.max_delay
-        TBPTT_INIT = nextpow2(int(max_delay * fs))
+        TBPTT_INIT = _diffdel_warmup(dataset)
         TBPTT_LEN = 2**11
         for p in self.parameters():
             p.requires_grad_(True)
@@ -787,17 +807,8 @@ class DiffDelRNN(_GRUHead):
         num_batches = 0             # counted, so that a generator (SegmentFeeder.batches) serves as well as a DataLoader
         epoch_loss = 0
         for _, batch in enumerate(dataloader):
-            input, target = batch[0], batch[1]
-            if input.shape[1] > 1:  # only the audio channel counts for training
-                input, target = input[:, :1, :], target[:, :1, :]
-            if isinstance(batch[2], dict):
-                d_traj = batch[2]["delay_trajectory"].float()
-                d_traj = d_traj.unsqueeze(1) * fs
-            elif batch[2] is not None:
-                d_traj = batch[2][:, :1, :].float() * fs
-            else:
-                raise RuntimeError("DiffDelRNN.train_epoch: the batch carries no delay trajectory")
-            input, target, d_traj = input.to(device), target.to(device), d_traj.to(device)
+            input, target = _audio_channel(batch[0], batch[1], device)
+            d_traj = _delay_samples(batch[2], fs, "DiffDelRNN.train_epoch").to(device)
 
             num_minibatches = int(np.ceil((input.shape[-1] - TBPTT_INIT) // TBPTT_LEN))
             self.initialize_hidden(input.shape[0], self.max_delay)
@@ -831,9 +842,8 @@ class DiffDelRNN(_GRUHead):
         bit for bit, state carried either way) and only the loss loop runs per piece.  Needs of the dataloader what the
         reference needs: len(), (input, target, meta) batches with meta['delay_trajectory'] (B, T) in seconds,
         `.dataset.delay_analyzer.max_delay` (seconds) and `.dataset.fs`."""
-        from .utilities import nextpow2
         fs = dataloader.dataset.fs
-        INIT_LEN = nextpow2(int(dataloader.dataset.delay_analyzer.max_delay * fs))
+        INIT_LEN = _diffdel_warmup(dataloader.dataset)
         TBPTT_LEN = 2**11
         device = self.GRU.weight_hh_l0.device
         self.eval()
@@ -842,11 +852,8 @@ class DiffDelRNN(_GRUHead):
         examples = []
         for _, batch in enumerate(dataloader):
             input, target, meta = batch
-            if input.shape[1] > 1:
-                input, target = input[:, :1, :], target[:, :1, :]
-            d_traj = meta["delay_trajectory"].float()
-            d_traj = d_traj.unsqueeze(1) * fs
-            input, target, d_traj = input.to(device), target.to(device), d_traj.to(device)
+            input, target = _audio_channel(input, target, device)
+            d_traj = _delay_samples(meta, fs, "DiffDelRNN.validate").to(device)
             num_minibatches = int(np.ceil((input.shape[-1] - INIT_LEN) / TBPTT_LEN))
             self.initialize_hidden(input.shape[0], self.max_delay)
             _, __ = self.forward(input[:, :, :INIT_LEN], d_traj[:, :, :INIT_LEN], warmup=True)
@@ -873,7 +880,7 @@ class Replicas:
     connection, all on the same HIP device -- trained side by side: what the reference runs as an array of jobs
     (scripts/sbatch-train-exp1a.sh:7-15, --array=0-2, each at code/train.py:94's batch of 32, i.e. 32 of 256 CUs).  Per TBPTT
     window there is ONE forward launch, ONE BPTT launch, ONE gradient reduction and ONE launch per loss kernel for all R; the
-    streams are stacked replica-major (training.GRUReplicaTrainStep).  Every replica ends up bit-identical to the same model
+    streams are stacked replica-major (training.GRUTrainStep with R).  Every replica ends up bit-identical to the same model
     trained alone by its own train_epoch: everything on the path is per stream and free of atomics.
     The models stay ordinary modules with their own parameters (the [R, ...] stacks are built inside the graph by torch.stack, so
     autograd hands each model its own .grad): each state_dict() is the reference's checkpoint format, and each can validate()
@@ -955,6 +962,28 @@ class Replicas:
         for m in self.models:
             m.zero_grad()
 
+    def _stage(self, who, x, xbt, del_traj, own=False):
+        """What forward() and infer() need beside x [B,T]: the group's state as h0 [B,64] (zeros from a fresh state; `own`: a
+        detached tensor of its own, which the inference kernel updates in place) and, for DiffDelRNN replicas, del_traj as
+        [B,T] of x's shape (else None)."""
+        B, H = xbt.shape[0], training.HIDDEN
+        if self.hidden is None:
+            h0 = torch.zeros(B, H, device=xbt.device, dtype=torch.float32)
+        elif tuple(self.hidden.shape) != (1, B, H):
+            raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
+        elif own:
+            h0 = self.hidden.detach().to(device=xbt.device, dtype=torch.float32).reshape(B, H).clone()
+        else:
+            h0 = self.hidden.to(device=xbt.device, dtype=torch.float32).reshape(B, H)
+        if not self.diffdel:
+            return h0, None
+        if del_traj is None:
+            raise RuntimeError(f"{who}: DiffDelRNN replicas need a delay trajectory")
+        dbt = _as_bt(del_traj, who)
+        if dbt.shape != xbt.shape:
+            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        return h0, dbt
+
     def forward(self, x, del_traj=None, warmup=False, _share=True):
         """One stateful training forward of all replicas: x (and del_traj, in samples) (R*Bper, 1, T) replica-major -> y for RNN,
         (y, pre_d) for DiffDelRNN, as the models' own forward() gives on their slices (same bits), as graph nodes.  A delay above
@@ -967,20 +996,10 @@ class Replicas:
         if x.requires_grad or (del_traj is not None and del_traj.requires_grad):
             raise RuntimeError("Replicas.forward: the input requires grad; the training kernels give gradients for the parameters, "
                                "the hidden state and the delay buffer only")
-        if self.hidden is None:
-            h0 = torch.zeros(B, training.HIDDEN, device=xbt.device, dtype=torch.float32)
-        elif tuple(self.hidden.shape) != (1, B, training.HIDDEN):
-            raise RuntimeError(f"Expected hidden size (1, {B}, {training.HIDDEN}), got {list(self.hidden.shape)}")
-        else:
-            h0 = self.hidden.to(device=xbt.device, dtype=torch.float32).reshape(B, training.HIDDEN)
+        h0, dbt = self._stage("Replicas.forward", x, xbt, del_traj)
         if self.diffdel:
-            if del_traj is None:
-                raise RuntimeError("Replicas.forward: DiffDelRNN replicas need a delay trajectory")
-            dbt = _as_bt(del_traj, "Replicas.forward")
-            if dbt.shape != xbt.shape:
-                raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
             self._dl._prepare(B, xbt.device)
-        pre, h = training.GRUReplicaTrainStep.apply(xbt, h0, *self._stacks(), R)
+        pre, h = training.GRUTrainStep.apply(xbt, h0, *self._stacks(), R)
         self.hidden = h.view(1, B, training.HIDDEN)
         if not self.diffdel:
             if _share:
@@ -1060,14 +1079,12 @@ class Replicas:
             m.train()
         device = self.device
         if self.diffdel:
-            from .utilities import nextpow2
             datasets = ([ld.dataset for ld in loaders] if dataset is None else
                         list(dataset) if isinstance(dataset, (list, tuple)) else [dataset] * R)
             if len(datasets) != R:
                 raise ValueError(f"Replicas.train_epoch: {len(datasets)} datasets for {R} replicas")
             fss = [ds.fs for ds in datasets]
-            inits = [nextpow2(int((ds.delay_analyzer.max_delay if hasattr(ds, "delay_analyzer") else ds.max_delay) * ds.fs))
-                     for ds in datasets]
+            inits = [_diffdel_warmup(ds) for ds in datasets]
             if len(set(inits)) != 1:
                 raise ValueError(f"Replicas.train_epoch: the datasets give different warm-up lengths {inits}; one is needed")
             TBPTT_INIT, TBPTT_LEN = inits[0], 2**11
@@ -1075,19 +1092,10 @@ class Replicas:
             TBPTT_INIT, TBPTT_LEN = 2**10, 2**10
 
         def prepare(r, batch):
-            input, target = batch[0], batch[1]
-            if input.shape[1] > 1:  # only the audio channel counts for training
-                input, target = input[:, :1, :], target[:, :1, :]
+            pair = _audio_channel(batch[0], batch[1], device)
             if not self.diffdel:
-                return input.to(device), target.to(device)
-            if isinstance(batch[2], dict):
-                d_traj = batch[2]["delay_trajectory"].float()
-                d_traj = d_traj.unsqueeze(1) * fss[r]
-            elif batch[2] is not None:
-                d_traj = batch[2][:, :1, :].float() * fss[r]
-            else:
-                raise RuntimeError("Replicas.train_epoch: the batch carries no delay trajectory")
-            return input.to(device), target.to(device), d_traj.to(device)
+                return pair
+            return pair + (_delay_samples(batch[2], fss[r], "Replicas.train_epoch").to(device),)
 
         num_batches = 0
         epoch_loss = [0] * R
@@ -1164,18 +1172,7 @@ class Replicas:
         B, T = xbt.shape
         Bper = self._streams_per_replica(B, R, "Replicas.infer")
         _require_hip(self.models[0].GRU.weight_hh_l0, "model parameters (call .to('cuda'))")
-        if self.hidden is None:
-            h = torch.zeros(B, H, device=xbt.device, dtype=torch.float32)
-        elif tuple(self.hidden.shape) != (1, B, H):
-            raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
-        else:           # a tensor of its own: the kernel updates it in place
-            h = self.hidden.detach().to(device=xbt.device, dtype=torch.float32).reshape(B, H).clone()
-        if self.diffdel:
-            if del_traj is None:
-                raise RuntimeError("Replicas.infer: DiffDelRNN replicas need a delay trajectory")
-            dbt = _as_bt(del_traj, "Replicas.infer")
-            if dbt.shape != xbt.shape:
-                raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        h, dbt = self._stage("Replicas.infer", x, xbt, del_traj, own=True)
         w_ih, w_hh, b_ih, b_hh, w_o, b_o = self._infer_stacks() if _stacks is None else _stacks
         pre = torch.empty_like(xbt)
         rc = _lib.lib().ntm_gru_forward_replicas(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(xbt), ptr(pre),
@@ -1227,9 +1224,8 @@ class Replicas:
             m.eval()
         grouped = isinstance(loss_fcn, (ESRLoss, DCPreESR))
         if self.diffdel:
-            from .utilities import nextpow2
             fss = [ld.dataset.fs for ld in loaders]
-            inits = [nextpow2(int(ld.dataset.delay_analyzer.max_delay * ld.dataset.fs)) for ld in loaders]
+            inits = [_diffdel_warmup(ld.dataset) for ld in loaders]
             if len(set(inits)) != 1:
                 raise ValueError(f"{who}: the datasets give different warm-up lengths {inits}; one is needed")
             INIT_LEN, TBPTT_LEN = inits[0], 2**11
@@ -1238,13 +1234,10 @@ class Replicas:
 
         def prepare(r, batch):
             input, target, meta = batch
-            if input.shape[1] > 1:            # only the audio channel counts for the loss
-                input, target = input[:, :1, :], target[:, :1, :]
+            pair = _audio_channel(input, target, device)
             if not self.diffdel:
-                return input.to(device), target.to(device)
-            d_traj = meta["delay_trajectory"].float()
-            d_traj = d_traj.unsqueeze(1) * fss[r]
-            return input.to(device), target.to(device), d_traj.to(device)
+                return pair
+            return pair + (_delay_samples(meta, fss[r], who).to(device),)
 
         stacks = self._infer_stacks()           # once per call, not once per batch
         val_loss = [0] * R
@@ -1380,12 +1373,6 @@ def esr_per_segment(output, target, skip=0):
     return (s[:, 0] / n) / (s[:, 1] / n + ESR_EPS)
 
 
-def _esr_value(output, target):
-    s = esr_sums(output, target).sum(dim=0)
-    n = output.numel()
-    return ((s[0] / n) / (s[1] / n + ESR_EPS)).float(), s
-
-
 def _replica_sums(rows, R, Bper, splits):
     """[R,2] fp64 whole-batch sums of R replicas from the per-stream rows [R*Bper, splits, 2] (ntm_loss_sums_replicas: one
     launch, the fixed order in which the single-model losses add the rows of one batch)."""
@@ -1401,8 +1388,16 @@ def _replica_split(output, R, what):
     return B // R
 
 
+def _esr_ratio(s, n):
+    """(loss, s) from whole-batch sums s [..., 2] fp64 over n elements."""
+    return ((s[..., 0] / n) / (s[..., 1] / n + ESR_EPS)).float(), s
+
+
 @torch.no_grad()
-def _esr_value_replicas(output, target, R):
+def _esr_value(output, target, R=None):
+    """(ESR of the whole tensor, its sums [2] fp64); with R the [R] losses of the replica-major slices and their sums [R,2]."""
+    if R is None:
+        return _esr_ratio(esr_sums(output, target).sum(dim=0), output.numel())
     y = _as_bt(output, "esr_sums")
     t = _as_bt(target, "esr_sums")
     B, T = y.shape
@@ -1411,9 +1406,14 @@ def _esr_value_replicas(output, target, R):
     splits = L.ntm_esr_splits(Bper, T, 0)          # of ONE replica's batch: the partial rows esr_sums forms for it alone
     rows = torch.empty(B, splits, 2, device=y.device, dtype=torch.float64)
     _lib.check(L.ntm_esr_sums(ptr(y), ptr(t), B, T, 0, splits, ptr(rows), _lib.current_stream()), "ntm_esr_sums")
-    s = _replica_sums(rows, R, Bper, splits)
-    n = output.numel() // R
-    return ((s[:, 0] / n) / (s[:, 1] / n + ESR_EPS)).float(), s
+    return _esr_ratio(_replica_sums(rows, R, Bper, splits), output.numel() // R)
+
+
+def _loss(value, pole, output, target, R=None):
+    """`value(output, target, R)`'s loss: a node of the graph where the output requires grad (training.loss_with_grad)."""
+    if output.requires_grad and torch.is_grad_enabled():
+        return training.loss_with_grad(output, target, value, pole, R)
+    return value(output, target, R)[0]
 
 
 class ESRLoss(torch.nn.Module):
@@ -1421,16 +1421,12 @@ class ESRLoss(torch.nn.Module):
     requires grad (RNN.train_epoch, code/train.py:176) the same value as a differentiable scalar (adjoint: ntm_esr_grad)."""
 
     def forward(self, output, target):
-        if output.requires_grad and torch.is_grad_enabled():
-            return training.loss_with_grad(output, target, _esr_value, None)
-        return _esr_value(output, target)[0]
+        return _loss(_esr_value, None, output, target)
 
     def replicas(self, output, target, R):
         """[R] losses of a replica-major (R*Bper,1,T) tensor (Replicas.train_epoch): entry r is forward() on slice r, value and
         adjoint bit for bit, from one launch per kernel for all R."""
-        if output.requires_grad and torch.is_grad_enabled():
-            return training.replica_losses_with_grad(output, target, _esr_value_replicas, None, R)
-        return _esr_value_replicas(output, target, R)[0]
+        return _loss(_esr_value, None, output, target, R)
 
 
 DC_PRE_R = 0.995
@@ -1456,32 +1452,29 @@ class DCPreESR(torch.nn.Module):
         super().__init__()
         self.dc_pre, self.R = dc_pre, R
 
-    def _value(self, output, target):
-        s = (esr_dcpre_sums(output, target, 0, self.R) if self.dc_pre else esr_sums(output, target)).sum(dim=0)
-        n = output.numel()
-        return ((s[0] / n) / (s[1] / n + ESR_EPS)).float(), s
+    @property
+    def _pole(self):
+        return self.R if self.dc_pre else None
+
+    @torch.no_grad()
+    def _value(self, output, target, R=None):
+        """_esr_value of the DC-blocked signals (of the signals themselves with dc_pre=False)."""
+        if not self.dc_pre:
+            return _esr_value(output, target, R)
+        rows = esr_dcpre_sums(output, target, 0, self.R)
+        if R is None:
+            return _esr_ratio(rows.sum(dim=0), output.numel())
+        Bper = _replica_split(output, R, "DCPreESR.replicas")
+        return _esr_ratio(_replica_sums(rows, R, Bper, 1), output.numel() // R)
 
     def forward(self, output, target):
         """With an output that requires grad (RNN.train_epoch, code/train.py:174) the same value as a differentiable scalar
         (adjoint: ntm_esr_dcpre_grad, or ntm_esr_grad with dc_pre=False)."""
-        if output.requires_grad and torch.is_grad_enabled():
-            return training.loss_with_grad(output, target, self._value, self.R if self.dc_pre else None)
-        return self._value(output, target)[0]
-
-    @torch.no_grad()
-    def _value_replicas(self, output, target, R):
-        if not self.dc_pre:
-            return _esr_value_replicas(output, target, R)
-        Bper = _replica_split(output, R, "DCPreESR.replicas")
-        s = _replica_sums(esr_dcpre_sums(output, target, 0, self.R), R, Bper, 1)
-        n = output.numel() // R
-        return ((s[:, 0] / n) / (s[:, 1] / n + ESR_EPS)).float(), s
+        return _loss(self._value, self._pole, output, target)
 
     def replicas(self, output, target, R):
         """[R] losses of a replica-major (R*Bper,1,T) tensor: entry r is forward() on slice r, value and adjoint bit for bit."""
-        if output.requires_grad and torch.is_grad_enabled():
-            return training.replica_losses_with_grad(output, target, self._value_replicas, self.R if self.dc_pre else None, R)
-        return self._value_replicas(output, target, R)[0]
+        return _loss(self._value, self._pole, output, target, R)
 
 
 MRSTFT_FFT_SIZES, MRSTFT_HOP_SIZES, MRSTFT_WIN_LENGTHS = (1024, 2048, 512), (120, 240, 50), (600, 1200, 240)

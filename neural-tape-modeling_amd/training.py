@@ -3,19 +3,19 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
 
   * GRUTrainStep: one stateful forward call of the GRU + head as a graph node.  forward = ntm_gru_train_forward (the step of the
     low-latency kernel -- the same code, csrc/gru_lat_step.h, so the same bits as kernel_variant "lat" -- plus the activations
-    saved for BPTT); backward =
-    ntm_gru_train_backward (one workgroup per stream) + ntm_gru_train_reduce (fixed-order sum over the streams): the gradients of
-    the six parameters and of the initial state h0.  dh0 is what chains a window to the one before it (the warm-up of
+    saved for BPTT); backward = ntm_gru_train_backward (one workgroup per stream) + ntm_gru_train_reduce (fixed-order sum over
+    the streams): the gradients of the six parameters and of the initial state h0.  dh0 is what chains a window to the one before it (the warm-up of
     train_epoch is such a node: code/model.py:122 runs it with grad enabled and does not detach it).
   * DelayLineStep: one call of the time-varying fractional delay line of DiffDelRNN (code/model.py:269-320) as a graph node.
     forward = ntm_delay_forward into a FRESH new-buffer tensor (the old buffer stays as it was: an in-place update would cut
     the edge from the first window back to the warm-up, whose outputs fill the buffer the first window's taps read);
     backward = ntm_delay_backward, the deterministic adjoint (gradients for pre and, where it is in the graph, the old buffer).
-  * ESRLossFn / DCPreESRLossFn: the loss value exactly as the no-grad path computes it, and its adjoint on the device
+  * loss_with_grad: the ESR / DCPreESR loss value exactly as the no-grad path computes it, and its adjoint on the device
     (ntm_esr_grad / ntm_esr_dcpre_grad).
-  * GRUReplicaTrainStep / replica_losses_with_grad: the same nodes for R independent models stacked replica-major
-    (model.Replicas): one forward, one BPTT, one reduction and one loss launch for all of them, each replica's bits those of
-    the single-model node on its slice.
+  * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
+    replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
+    launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
+    are one kernel each either way (one model is its R = 1); the forward and the BPTT keep a plain and a replica form.
 """
 import torch
 
@@ -27,66 +27,38 @@ SUPPORTED = "RNN(input_size=1, hidden_size=64, output_size=1, skip=False) on a H
 SUPPORTED_DIFFDEL = "DiffDelRNN(input_size=1, hidden_size=64, output_size=1, skip=False) on a HIP device"
 
 
+def _entry(name, B, R):
+    """The C entry point of a node and its leading size arguments: `name`(..., B, ...) for one model (R None), else
+    `name`_replicas(..., R, Bper, ...)."""
+    if R is None:
+        return name, (B,)
+    return name + "_replicas", (R, B // R)
+
+
 class GRUTrainStep(torch.autograd.Function):
-    """(x [B,T] fp32 contiguous, h0 [B,64], w_ih, w_hh, b_ih, b_hh, w_o, b_o) -> (y [B,T], h_T [B,64]), both fresh tensors."""
-
-    @staticmethod
-    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, w_o, b_o):
-        B, T = x.shape
-        L = _lib.lib()
-        h = h0.detach().to(torch.float32).reshape(B, HIDDEN).clone(memory_format=torch.contiguous_format)
-        y = torch.empty(B, T, device=x.device, dtype=torch.float32)
-        ws = torch.empty(max(int(L.ntm_gru_train_workspace_floats(B, T)), 1), device=x.device, dtype=torch.float32)
-        _lib.check(L.ntm_gru_train_forward(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(x), ptr(y), B, T, T, T,
-                                           ptr(h), ptr(ws), _lib.current_stream()), "ntm_gru_train_forward")
-        # the weights through save_for_backward: torch's version counters then refuse a backward after an in-place update
-        ctx.save_for_backward(x, ws, w_ih, w_hh, b_ih, b_hh, w_o, b_o)
-        ctx.h0_shape = h0.shape
-        ctx.set_materialize_grads(False)
-        return y, h
-
-    @staticmethod
-    def backward(ctx, dy, dh):
-        x, ws, w_ih, w_hh, b_ih, b_hh, w_o, b_o = ctx.saved_tensors
-        B, T = x.shape
-        dev = x.device
-        dy = None if dy is None else dy.to(torch.float32).contiguous()
-        dh = None if dh is None else dh.to(torch.float32).reshape(B, HIDDEN).contiguous()
-        dh0 = torch.empty(B, HIDDEN, device=dev, dtype=torch.float32)
-        part = torch.empty(max(B, 1), _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
-        grad = torch.empty(_lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
-        L, s = _lib.lib(), _lib.current_stream()
-        _lib.check(L.ntm_gru_train_backward(ptr(w_hh), ptr(w_o), ptr(x), T, ptr(ws), ptr(dy), T, ptr(dh), B, T, ptr(dh0), ptr(part), s),
-                   "ntm_gru_train_backward")
-        _lib.check(L.ntm_gru_train_reduce(ptr(part), B, ptr(grad), s), "ntm_gru_train_reduce")
-        H3 = 3 * HIDDEN
-        sizes = [w_ih.numel(), w_hh.numel(), H3, H3, HIDDEN, 1]
-        g_wih, g_whh, g_bih, g_bhh, g_wo, g_bo = torch.split(grad, sizes)
-        return (None, dh0.view(ctx.h0_shape), g_wih.view(w_ih.shape), g_whh.view(w_hh.shape), g_bih.view(b_ih.shape),
-                g_bhh.view(b_hh.shape), g_wo.view(w_o.shape), None if b_o is None else g_bo.view(b_o.shape))
-
-
-class GRUReplicaTrainStep(torch.autograd.Function):
-    """GRUTrainStep for R independent models in one launch each way (model.Replicas): x [R*Bper,T] and h0 [R*Bper,64] stacked
-    replica-major, the six parameters as contiguous [R, ...] stacks (b_o None for the bias-free head) -> (y [R*Bper,T],
-    h_T [R*Bper,64]), both fresh.  Every replica's slice has the bits GRUTrainStep gives on it alone; the gradients come back as
+    """(x [B,T] fp32 contiguous, h0 [B,64], w_ih, w_hh, b_ih, b_hh, w_o, b_o, R=None) -> (y [B,T], h_T [B,64]), both fresh tensors.
+    R None: one model, the parameters in their own shapes (b_o None for the bias-free head).  R an integer: R independent models
+    in one launch each way (model.Replicas) -- x and h0 stacked replica-major, B = R * Bper, the parameters as contiguous
+    [R, ...] stacks; every replica's slice has the bits the R = None node gives on it alone, and the gradients come back as
     [R, ...] stacks (the caller builds the stacks with torch.stack inside the graph, so each model gets its own .grad)."""
 
     @staticmethod
-    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, w_o, b_o, R):
+    def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh, w_o, b_o, R=None):
         B, T = x.shape
-        if R < 1 or B % R:
-            raise RuntimeError(f"GRUReplicaTrainStep: {B} streams do not divide into {R} replicas")
-        for w in (w_ih, w_hh, b_ih, b_hh, w_o, b_o):
-            if w is not None and (w.shape[0] != R or not w.is_contiguous() or w.dtype != torch.float32):
-                raise RuntimeError("GRUReplicaTrainStep: the parameters must be contiguous float32 [R, ...] stacks")
+        if R is not None:
+            if R < 1 or B % R:
+                raise RuntimeError(f"GRUTrainStep: {B} streams do not divide into {R} replicas")
+            for w in (w_ih, w_hh, b_ih, b_hh, w_o, b_o):
+                if w is not None and (w.shape[0] != R or not w.is_contiguous() or w.dtype != torch.float32):
+                    raise RuntimeError("GRUTrainStep: the parameters must be contiguous float32 [R, ...] stacks")
         L = _lib.lib()
         h = h0.detach().to(torch.float32).reshape(B, HIDDEN).clone(memory_format=torch.contiguous_format)
         y = torch.empty(B, T, device=x.device, dtype=torch.float32)
         ws = torch.empty(max(int(L.ntm_gru_train_workspace_floats(B, T)), 1), device=x.device, dtype=torch.float32)
-        _lib.check(L.ntm_gru_train_forward_replicas(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(x), ptr(y), R,
-                                                    B // R, T, T, T, ptr(h), ptr(ws), _lib.current_stream()),
-                   "ntm_gru_train_forward_replicas")
+        name, sizes = _entry("ntm_gru_train_forward", B, R)
+        _lib.check(getattr(L, name)(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(x), ptr(y), *sizes, T, T, T,
+                                    ptr(h), ptr(ws), _lib.current_stream()), name)
+        # the weights through save_for_backward: torch's version counters then refuse a backward after an in-place update
         ctx.save_for_backward(x, ws, w_ih, w_hh, b_ih, b_hh, w_o, b_o)
         ctx.h0_shape, ctx.R = h0.shape, R
         ctx.set_materialize_grads(False)
@@ -100,12 +72,13 @@ class GRUReplicaTrainStep(torch.autograd.Function):
         dy = None if dy is None else dy.to(torch.float32).contiguous()
         dh = None if dh is None else dh.to(torch.float32).reshape(B, HIDDEN).contiguous()
         dh0 = torch.empty(B, HIDDEN, device=dev, dtype=torch.float32)
-        part = torch.empty(B, _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
-        grad = torch.empty(R, _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
+        part = torch.empty(max(B, 1), _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
+        grad = torch.empty(1 if R is None else R, _lib.TRAIN_GRAD_FLOATS, device=dev, dtype=torch.float32)
         L, s = _lib.lib(), _lib.current_stream()
-        _lib.check(L.ntm_gru_train_backward_replicas(ptr(w_hh), ptr(w_o), ptr(x), T, ptr(ws), ptr(dy), T, ptr(dh), R, B // R, T,
-                                                     ptr(dh0), ptr(part), s), "ntm_gru_train_backward_replicas")
-        _lib.check(L.ntm_gru_train_reduce_replicas(ptr(part), R, B // R, ptr(grad), s), "ntm_gru_train_reduce_replicas")
+        name, sizes = _entry("ntm_gru_train_backward", B, R)
+        _lib.check(getattr(L, name)(ptr(w_hh), ptr(w_o), ptr(x), T, ptr(ws), ptr(dy), T, ptr(dh), *sizes, T, ptr(dh0), ptr(part), s), name)
+        name, sizes = _entry("ntm_gru_train_reduce", B, R)
+        _lib.check(getattr(L, name)(ptr(part), *sizes, ptr(grad), s), name)
         H3 = 3 * HIDDEN
         g_wih, g_whh, g_bih, g_bhh, g_wo, g_bo = torch.split(grad, [H3, H3 * HIDDEN, H3, H3, HIDDEN, 1], dim=1)
         return (None, dh0.view(ctx.h0_shape), g_wih.reshape(w_ih.shape), g_whh.reshape(w_hh.shape), g_bih.reshape(b_ih.shape),
@@ -145,42 +118,8 @@ class DelayLineStep(torch.autograd.Function):
 
 
 class _LossFn(torch.autograd.Function):
-    """Shared body of the two loss nodes: `value(output, target)` -> (loss, whole-batch sums [2] fp64) runs under no_grad."""
-
-    @staticmethod
-    def forward(ctx, output, target, value, R):
-        loss, sums = value(output, target)
-        ctx.save_for_backward(output, target, sums)
-        ctx.R = R
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        from .model import ESR_EPS, _as_bt
-        output, target, sums = ctx.saved_tensors
-        y = _as_bt(output, "loss backward")
-        t = _as_bt(target, "loss backward")
-        B, T = y.shape
-        g = gout.detach().to(device=y.device, dtype=torch.float32).reshape(1).contiguous()
-        dy = torch.empty(B, T, device=y.device, dtype=torch.float32)
-        L, s = _lib.lib(), _lib.current_stream()
-        if ctx.R is None:
-            _lib.check(L.ntm_esr_grad(ptr(y), ptr(t), B, T, ptr(sums), ptr(g), ESR_EPS, ptr(dy), s), "ntm_esr_grad")
-        else:
-            _lib.check(L.ntm_esr_dcpre_grad(ptr(y), ptr(t), B, T, float(ctx.R), ptr(sums), ptr(g), ESR_EPS, ptr(dy), s),
-                       "ntm_esr_dcpre_grad")
-        return dy.view(output.shape).to(output.dtype), None, None, None
-
-
-def loss_with_grad(output, target, value, R):
-    """The loss node: `value` computes the no-grad path's value and the whole-batch sums; R None = ESR, else DCPreESR."""
-    if target.requires_grad:
-        raise RuntimeError("ESRLoss / DCPreESR: gradients flow to the prediction only; the target must not require grad")
-    return _LossFn.apply(output, target, value, R)
-
-
-class _ReplicaLossFn(torch.autograd.Function):
-    """_LossFn for R losses at once: `value(output, target, R)` -> (losses [R], the replicas' whole-batch sums [R,2] fp64)."""
+    """Shared body of the two loss nodes: `value(output, target, R)` -> (loss, whole-batch sums fp64) runs under no_grad.  R None:
+    one scalar loss, sums [2]; R an integer: [R] losses of the replica-major slices, sums [R,2]."""
 
     @staticmethod
     def forward(ctx, output, target, value, pole, R):
@@ -197,20 +136,21 @@ class _ReplicaLossFn(torch.autograd.Function):
         t = _as_bt(target, "loss backward")
         B, T = y.shape
         R = ctx.R
-        g = gout.detach().to(device=y.device, dtype=torch.float32).reshape(R).contiguous()
+        g = gout.detach().to(device=y.device, dtype=torch.float32).reshape(1 if R is None else R).contiguous()
         dy = torch.empty(B, T, device=y.device, dtype=torch.float32)
         L, s = _lib.lib(), _lib.current_stream()
         if ctx.pole is None:
-            _lib.check(L.ntm_esr_grad_replicas(ptr(y), ptr(t), R, B // R, T, ptr(sums), ptr(g), ESR_EPS, ptr(dy), s),
-                       "ntm_esr_grad_replicas")
+            name, sizes = _entry("ntm_esr_grad", B, R)
+            _lib.check(getattr(L, name)(ptr(y), ptr(t), *sizes, T, ptr(sums), ptr(g), ESR_EPS, ptr(dy), s), name)
         else:
-            _lib.check(L.ntm_esr_dcpre_grad_replicas(ptr(y), ptr(t), R, B // R, T, float(ctx.pole), ptr(sums), ptr(g), ESR_EPS,
-                                                     ptr(dy), s), "ntm_esr_dcpre_grad_replicas")
+            name, sizes = _entry("ntm_esr_dcpre_grad", B, R)
+            _lib.check(getattr(L, name)(ptr(y), ptr(t), *sizes, T, float(ctx.pole), ptr(sums), ptr(g), ESR_EPS, ptr(dy), s), name)
         return dy.view(output.shape).to(output.dtype), None, None, None, None
 
 
-def replica_losses_with_grad(output, target, value, pole, R):
-    """The grouped loss node: [R] losses of the replica-major (R*Bper,1,T) output; pole None = ESR, else DCPreESR's R."""
+def loss_with_grad(output, target, value, pole, R=None):
+    """The loss node: `value` computes the no-grad path's value(s) and the whole-batch sums; pole None = ESR, else DCPreESR's
+    coefficient.  R None: the scalar loss of the whole tensor; R an integer: the [R] losses of a replica-major (R*Bper,1,T) output."""
     if target.requires_grad:
         raise RuntimeError("ESRLoss / DCPreESR: gradients flow to the prediction only; the target must not require grad")
-    return _ReplicaLossFn.apply(output, target, value, pole, R)
+    return _LossFn.apply(output, target, value, pole, R)

@@ -246,3 +246,103 @@ def test_training_refusals_on_the_device(ntm):
     m32 = ntm.RNN(1, 32, 1).cuda()
     with pytest.raises(RuntimeError, match="hidden_size=64"):
         m32.train_epoch([(x, x, None)], ntm.ESRLoss(), torch.optim.Adam(m32.parameters(), 1e-3))
+
+
+# ---- the reduction and the loss adjoints through the raw ABI, against fp64 evaluated in the kernels' operation order.  The single
+# entry points launch the `_replicas` kernels with one grid row (R = 1, bper = B); these are the anchors of that code that do not
+# go through the replica path: equality, not a tolerance.
+def _raw(ntm):
+    return ntm._lib.lib(), ntm._lib.ptr, ntm._lib.current_stream()
+
+
+@pytest.mark.gpu
+def test_reduce_of_an_empty_batch_writes_zeros(ntm):
+    L, ptr, s = _raw(ntm)
+    grad = torch.full((ntm._lib.TRAIN_GRAD_FLOATS,), float("nan"), device="cuda")
+    assert L.ntm_gru_train_reduce(None, 0, ptr(grad), s) == 0
+    assert torch.equal(grad, torch.zeros_like(grad))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 3])
+def test_reduce_adds_the_partials_in_stream_order_in_fp64(ntm, B):
+    L, ptr, s = _raw(ntm)
+    n = ntm._lib.TRAIN_GRAD_FLOATS
+    part = (torch.randn(B, n, generator=torch.Generator().manual_seed(B)) * 10.0 ** torch.randint(-3, 4, (B, n), generator=torch.Generator().manual_seed(7))).float().cuda()
+    grad = torch.full((n,), float("nan"), device="cuda")
+    assert L.ntm_gru_train_reduce(ptr(part), B, ptr(grad), s) == 0
+    acc = torch.zeros(n, dtype=torch.float64, device="cuda")
+    for b in range(B):
+        acc = acc + part[b].double()
+    assert torch.equal(grad, acc.float())
+
+
+def _loss_inputs(B, T):
+    g = torch.Generator().manual_seed(1000 * B + T)
+    y = (torch.rand(B, T, generator=g) - 0.5).float()
+    t = (0.8 * y + 0.1 * torch.randn(B, T, generator=g) + 0.05).float()
+    sums = torch.tensor([float(((t.double() - y.double()) ** 2).sum()), float((t.double() ** 2).sum())], dtype=torch.float64)
+    gout = torch.tensor([0.7], dtype=torch.float32)
+    return y, t, sums, gout
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,T", [(1, 1), (1, 5), (3, 300)])
+def test_esr_adjoint_equals_fp64_in_the_kernels_order(ntm, B, T):
+    L, ptr, s = _raw(ntm)
+    y, t, sums, gout = _loss_inputs(B, T)
+    yc, tc, sc, gc = y.cuda(), t.cuda(), sums.cuda(), gout.cuda()
+    dy = torch.full((B, T), float("nan"), device="cuda")
+    assert L.ntm_esr_grad(ptr(yc), ptr(tc), B, T, ptr(sc), ptr(gc), 1e-5, ptr(dy), s) == 0
+    n = float(B * T)
+    c = gout.double()[0] * 2.0 / (n * (sums[1] / n + 1e-5))
+    want = (c * (y.double() - t.double())).float()
+    assert torch.equal(dy.cpu(), want)
+
+
+def _fma(a, b, c):
+    """a * b + c rounded once (float() of a Fraction rounds to nearest even), as v_fma_f64 does."""
+    from fractions import Fraction
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _dcpre_adjoint_f64(y, t, pole, sums, gout, eps):
+    """esr_dcpre_grad_kernel in Python floats (IEEE fp64), one stream after the other, in the kernel's operation order: the
+    causal pass e_f = (w - w_prev) + pole e_f parked as fp32, then q = c e_f + pole q1, dy = q - q1 downwards.  The compiler
+    contracts `+ pole * e_f` and `+ pole * q1` into fused multiply-adds (the file is built with hipcc's default contraction and
+    this kernel does not switch it off), so these two are rounded once here too."""
+    import struct
+    f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]      # noqa: E731
+    B, T = y.shape
+    Rd = float(np.float32(pole))
+    n = float(B * T)
+    c = float(gout[0]) * 2.0 / (n * (float(sums[1]) / n + eps))
+    out = torch.empty(B, T, dtype=torch.float32)
+    for b in range(B):
+        prev, ef, park = 0.0, 0.0, []
+        for i in range(T):
+            wv = float(y[b, i]) - float(t[b, i])
+            ef = _fma(Rd, ef, wv - prev)
+            prev = wv
+            park.append(f32(ef))
+        q1 = 0.0
+        for i in range(T - 1, -1, -1):
+            q = _fma(Rd, q1, c * park[i])
+            out[b, i] = f32(q - q1)
+            q1 = q
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,T", [(1, 1), (3, 5), (65, 7)])
+def test_dcpre_adjoint_equals_fp64_in_the_kernels_order(ntm, B, T):
+    L, ptr, s = _raw(ntm)
+    y, t, sums, gout = _loss_inputs(B, T)
+    pole = float(np.float32(ntm.model.DC_PRE_R))
+    yc, tc, sc, gc = y.cuda(), t.cuda(), sums.cuda(), gout.cuda()
+    dy = torch.full((B, T), float("nan"), device="cuda")
+    assert L.ntm_esr_dcpre_grad(ptr(yc), ptr(tc), B, T, pole, ptr(sc), ptr(gc), 1e-5, ptr(dy), s) == 0
+    want = _dcpre_adjoint_f64(y, t, pole, sums, gout, 1e-5)
+    got = dy.cpu()
+    print(f"dcpre adjoint ({B}, {T}): {int((got != want).sum())} of {B * T} elements differ from the fp64 evaluation")
+    assert torch.equal(got, want)

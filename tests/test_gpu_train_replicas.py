@@ -1,8 +1,11 @@
-"""GPU: R replicas trained in one launch per window (ntm_amd.Replicas, training.GRUReplicaTrainStep, the *_replicas kernels of
+"""GPU: R replicas trained in one launch per window (ntm_amd.Replicas, training.GRUTrainStep with R, the *_replicas kernels of
 csrc/gru_train.hip).  The oracle throughout is the single-model path in the same process -- GRUTrainStep, ESRLoss / DCPreESR and
 the models' own train_epoch on the replica's slice with the replica's weights -- compared bit for bit (torch.equal): that path is
 pinned to float64 autograd and to the reference by tests/test_gpu_train.py and tests/test_gpu_train_diffdel.py (goldens g23, g24),
-and replica 0 of the epoch tests is held to g23's bars directly as well."""
+and replica 0 of the epoch tests is held to g23's bars directly as well.
+For the gradient reduction and the loss adjoints there is one kernel each: the single-model entry points launch it with one grid
+row, so "single versus replica" compares R = 1 against R > 1 of the same code there.  Their independent anchors are the fp64
+tests of the raw entry points in tests/test_gpu_train.py and the goldens g23 / g24."""
 import numpy as np
 import pytest
 import torch
@@ -144,6 +147,13 @@ def test_grouped_losses_are_the_single_losses_value_and_adjoint(ntm, kind):
         assert torch.equal(v[r].detach(), va.detach()), (r, float(v[r]), float(va))
         assert torch.equal(yc.grad[sl], ya.grad), r
     assert len({float(a) for a in v.detach()}) == R
+    # R = 1: the grouped loss of one replica is the plain loss (the two share their kernels: an offset bug would show here)
+    y1 = y[Bper:].cuda().requires_grad_(True)           # 2 * Bper streams as ONE replica
+    y2 = y[Bper:].cuda().requires_grad_(True)
+    v1, v2 = fn.replicas(y1, tc[Bper:], 1), fn(y2, tc[Bper:])
+    (v1 * w[:1]).sum().backward()
+    (v2 * w[0]).backward()
+    assert v1.shape == (1,) and torch.equal(v1[0].detach(), v2.detach()) and torch.equal(y1.grad, y2.grad)
 
 
 @pytest.mark.gpu

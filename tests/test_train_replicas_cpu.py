@@ -1,4 +1,4 @@
-"""CPU: the replica training path (ntm_amd.Replicas, training.GRUReplicaTrainStep, the *_replicas entry points of
+"""CPU: the replica training path (ntm_amd.Replicas, training.GRUTrainStep with R, the *_replicas entry points of
 csrc/gru_train.hip) -- the symbols, the host-side argument checks and the refusals that need no device."""
 import os
 import re
@@ -52,7 +52,7 @@ def test_argument_checks_return_minus_one_before_anything_touches_a_device():
 
 def test_replicas_is_exported_and_the_nodes_are_autograd_functions():
     assert ntm_amd.Replicas is ntm_amd.model.Replicas and "Replicas" in ntm_amd.__all__
-    assert issubclass(ntm_amd.training.GRUReplicaTrainStep, torch.autograd.Function)
+    assert issubclass(ntm_amd.training.GRUTrainStep, torch.autograd.Function)
     for cls in (ntm_amd.ESRLoss, ntm_amd.DCPreESR):
         assert callable(getattr(cls, "replicas", None))
     assert callable(ntm_amd.Replicas.train_epoch)
