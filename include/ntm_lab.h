@@ -66,6 +66,24 @@ int ntm_lab_tcn_stamps(unsigned long long *host7);
  * inside the iteration loop), or NULL to switch the trace off */
 int ntm_lab_tcn_trace(unsigned long long *device_buf);
 
+/*
+ * TEST PROBE: the fp64 helpers of tape_hmag_kernel (csrc/tape_math.h), one per call, applied elementwise by a kernel that
+ * is compiled under the same floating-point contraction setting as the product kernel.  op:
+ *   NTM_LAB_TAPE_RCP             out[i] = rcp_nr(in[i])              in[i] != 0, finite, normal
+ *   NTM_LAB_TAPE_EXPM1_NEG       out[i] = expm1_neg(in[i])           in[i] <= 0
+ *   NTM_LAB_TAPE_COTH            out[i] = coth_gt(in[i])             |in[i]| > 1e-4
+ *   NTM_LAB_TAPE_LANGEVIN_PRIME  out[i] = langevin_prime_lt1(in[i])  |in[i]| < 1
+ *   NTM_LAB_TAPE_JA_F            out[i] = ja_f(Mn, Hn, Hp) with (Mn, Hn, Hp) = in[3i .. 3i+2]; params5 as ntm_tape_hmag
+ * in [n] (or [n][3]) and out [n]: fp64 device, distinct; params5: HOST array {Ms, A, alpha, K, c}, read for
+ * NTM_LAB_TAPE_JA_F only.  n == 0 is a no-op; a bad op, a null pointer or a negative n is NTM_EINVAL.
+ */
+#define NTM_LAB_TAPE_RCP 0
+#define NTM_LAB_TAPE_EXPM1_NEG 1
+#define NTM_LAB_TAPE_COTH 2
+#define NTM_LAB_TAPE_LANGEVIN_PRIME 3
+#define NTM_LAB_TAPE_JA_F 4
+int ntm_lab_tape_math(int op, const double *in, double *out, int64_t n, const double *params5, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,7 +80,9 @@ _LAB_SIGNATURES = {
     "ntm_lab_tcn_forward": (_int, [_vp, _int, _int, _int, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "ntm_lab_tcn_stamps": (_int, [_vp]),
     "ntm_lab_tcn_trace": (_int, [_vp]),
+    "ntm_lab_tape_math": (_int, [_int, _vp, _vp, _i64, ctypes.POINTER(ctypes.c_double), _vp]),
 }
+LAB_TAPE_OPS = {"rcp_nr": 0, "expm1_neg": 1, "coth_gt": 2, "langevin_prime_lt1": 3, "ja_f": 4}   # include/ntm_lab.h NTM_LAB_TAPE_*
 LAB_VARIANTS = ("mfma", "valu")
 
 _lib = None

@@ -4,6 +4,7 @@
 // (libntm.so, neural-tape-modeling_amd/model.py with a product kernel_variant) loads this library.
 #include "ntm_lab.h"
 #include "ntm_common.h"
+#include "tape_math.h"
 
 #include <cstdlib>
 #include <string>
@@ -16,6 +17,24 @@ int fail(int code, const std::string &msg)
     return code;
 }
 int hip_fail(hipError_t e, const char *where) { return fail(NTM_EHIP, std::string(where) + ": " + hipGetErrorString(e)); }
+
+// Elementwise probe of csrc/tape_math.h: one helper of tape_hmag_kernel per launch, compiled under the kernel's own
+// contraction setting.  ja_f reads three inputs per element (Mn, Hn, Hp).
+__global__ __launch_bounds__(256) void tape_math_probe_kernel(int op, const double *in, double *out, int64_t n, ntm::JaParams p)
+{
+#pragma clang fp contract(off)   // as in tape_hmag_kernel: only the explicit fma() calls of the helpers fuse
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double r;
+    switch (op) {
+        case NTM_LAB_TAPE_RCP: r = ntm::rcp_nr(in[i]); break;
+        case NTM_LAB_TAPE_EXPM1_NEG: r = ntm::expm1_neg(in[i]); break;
+        case NTM_LAB_TAPE_COTH: r = ntm::coth_gt(in[i]); break;
+        case NTM_LAB_TAPE_LANGEVIN_PRIME: r = ntm::langevin_prime_lt1(in[i]); break;
+        default: r = ntm::ja_f(in[3 * i], in[3 * i + 1], in[3 * i + 2], p); break;
+    }
+    out[i] = r;
+}
 }  // namespace
 
 extern "C" {
@@ -82,6 +101,21 @@ int ntm_debug_transpose4(const float *in, float *out, void *stream)
     if (!in || !out) return fail(NTM_EINVAL, "ntm_debug_transpose4: null pointer");
     hipError_t e = ntm::launch_debug_transpose(in, out, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_debug_transpose4");
+}
+
+int ntm_lab_tape_math(int op, const double *in, double *out, int64_t n, const double *params5, void *stream)
+{
+    if (op < NTM_LAB_TAPE_RCP || op > NTM_LAB_TAPE_JA_F) return fail(NTM_EINVAL, "ntm_lab_tape_math: op is not one of NTM_LAB_TAPE_*");
+    if (n < 0) return fail(NTM_EINVAL, "ntm_lab_tape_math: negative n");
+    if (n > ((int64_t)1 << 30)) return fail(NTM_EINVAL, "ntm_lab_tape_math: at most 2^30 elements per call");
+    if (n == 0) return NTM_OK;
+    if (!in || !out || in == out) return fail(NTM_EINVAL, "ntm_lab_tape_math: null or aliased pointer");
+    if (op == NTM_LAB_TAPE_JA_F && !params5) return fail(NTM_EINVAL, "ntm_lab_tape_math: NTM_LAB_TAPE_JA_F needs params5");
+    ntm::JaParams p{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (op == NTM_LAB_TAPE_JA_F) p = ntm::JaParams{params5[0], params5[1], params5[2], params5[3], params5[4], 1.0 / params5[1]};   // as launch_tape_hmag
+    hipLaunchKernelGGL(tape_math_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, op, in, out, n, p);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_lab_tape_math");
 }
 
 }  // extern "C"

@@ -450,7 +450,7 @@ int ntm_demodulate(const float *x, float *out, int C, int64_t N, const int64_t *
 int ntm_tape_record_field(const double *I, const double *bias, double *H, int64_t B, int64_t N, double gain, double gap,
                           void *stream)
 {
-    if (B < 0 || N < 0 || !(gap != 0.0)) return fail(NTM_EINVAL, "ntm_tape_record_field: bad size or gap");
+    if (B < 0 || N < 0 || !(gap < 0.0 || gap > 0.0)) return fail(NTM_EINVAL, "ntm_tape_record_field: bad size or gap");   // 0 and NaN
     if (B == 0 || N == 0) return NTM_OK;
     if (!I || !H) return fail(NTM_EINVAL, "ntm_tape_record_field: null pointer");
     hipError_t e = ntm::launch_tape_record_field(I, bias, H, B, N, gain, gap, (hipStream_t)stream);

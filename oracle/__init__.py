@@ -55,6 +55,7 @@ def lib():
         _LIB.ntmo_esr_dcpre_sums.argtypes = [_f32p, _f32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_float, _f64p]
         _LIB.ntmo_tape_hmag.argtypes = [_f64p, _f64p, ctypes.c_int64, ctypes.c_int64, _f64p, ctypes.c_double, _f64p]
+        _LIB.ntmo_tape_ja_f.argtypes = [_f64p, _f64p, ctypes.c_int64, _f64p]
         _LIB.ntmo_tcn_forward.argtypes = [_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p,
                                           _f32p, _f32p, ctypes.c_int64, ctypes.c_int64]
         _LIB.ntmo_tcn_forward_mt.argtypes = _LIB.ntmo_tcn_forward.argtypes + [ctypes.c_int]
@@ -442,6 +443,17 @@ def tape_hmag(H, state=None, Ts=1.0 / (48000 * 16), params=TAPE_PARAMS):
     d = lambda a: a.ctypes.data_as(_f64p)                                                    # noqa: E731
     assert lib().ntmo_tape_hmag(d(H), d(M), B, N, d(state), Ts, d(par)) == 0
     return M, state
+
+
+def tape_ja_f(points, params=TAPE_PARAMS):
+    """Tape._f, code/tape.py:587-635, elementwise: points [n,3] = (Mn, Hn, Hp) f64 -> f [n] (the right-hand side that
+    tape_hmag integrates, operation for operation as the reference evaluates it)."""
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    out = np.empty(len(pts))
+    par = np.asarray(params, dtype=np.float64)
+    d = lambda a: a.ctypes.data_as(_f64p)                                                    # noqa: E731
+    assert lib().ntmo_tape_ja_f(d(pts), d(out), len(pts), d(par)) == 0
+    return out
 
 
 def sinc_resample(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):

@@ -376,6 +376,13 @@ static double ja_f(double Mn, double Hn, double Hp, const double *par)
     return (t1 + t2) / t3;
 }
 
+/* ja_f applied elementwise: in [n][3] = (Mn, Hn, Hp) -> out [n] (what the tests compare the device's ja_f with) */
+int ntmo_tape_ja_f(const double *in, double *out, int64_t n, const double *par)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = ja_f(in[3 * i], in[3 * i + 1], in[3 * i + 2], par);
+    return 0;
+}
+
 int ntmo_tape_hmag(const double *H, double *M, int64_t B, int64_t N, double *state, double Ts, const double *par)
 {
     for (int64_t b = 0; b < B; ++b) {

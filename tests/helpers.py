@@ -128,6 +128,98 @@ def structural_cases(n_fft):
     return [(L, hop, wins[(j + off) % 5], skips[(j + off) % 3], Bs[(j + off) % 2]) for j, (L, hop) in enumerate(lh)]
 
 
+# ---- case tables and extended-precision references of the tape kernels (tests/test_gpu_tape.py; the tables are checked
+# and the references pinned on the CPU by tests/test_oracle_tape.py)
+TAPE_TILE = 64                                           # tape_hmag_kernel: 64 streams x 64 samples per LDS tile
+TAPE_HMAG_B = (1, 63, 64, 65, 129)
+TAPE_HMAG_N = (1, 2, 63, 64, 65, 127, 128, 129, 193)
+TAPE_SINGLE_STREAMS = (0, 63, 64, 128)                   # of a batch of 129, each also run alone
+RESAMPLE_RATIOS = ((1, 16), (16, 1), (147, 160), (160, 147), (2, 3), (3, 2))      # (orig, new)
+FIR_TAPS = (1, 2, 127, 128, 129)
+RECORD_SHAPES = ((1, 1), (3, 255), (2, 257))
+RECORD_GRID_LIMIT = 65536 * 256                          # threads of tape_record_field_kernel's largest grid
+RECORD_BIG = (3, RECORD_GRID_LIMIT // 3 + 1)             # the smallest B = 3 shape whose grid-stride loop goes round twice
+
+
+def tape_walk(seed, B, N, amp=300.0):
+    """Unsaturated H_mag input (B, N): the walk_small family of golden g25, amp * cumsum(randn) / 20."""
+    return amp * np.cumsum(np.random.default_rng(seed).standard_normal((B, N)), axis=1) / 20.0
+
+
+def tape_cut_lists(N):
+    """Chunk lengths (each list sums to N) across the 64-sample tile of tape_hmag_kernel."""
+    cuts = [c for c in ((1, N - 1), (63, N - 63), (64, 64, N - 128), (65, N - 65)) if min(c) > 0]
+    if N == 67:
+        cuts.append((1,) * 67)
+    assert all(sum(c) == N for c in cuts), N
+    return cuts
+
+
+TAPE_CUT_N = (67, 193)
+
+
+def resample_lengths(width):
+    return tuple(sorted({1, 2, width - 1, width, width + 1, 255, 256, 257, 1000}))
+
+
+def resample_out_lengths(N, up, down):
+    """M: torchaudio's ceil(up N / down), 1, one below and one above it (ntm.h defines every i * up + p < M)."""
+    full = -(-up * N // down)
+    return tuple(dict.fromkeys((full, 1, max(1, full // 2), full + up + 3)))
+
+
+def fir_lengths(taps):
+    return tuple(sorted({1, taps - 1, taps, taps + 1, 255, 256, 257, 700} - {0}))
+
+
+U53 = 2.0 ** -53
+
+
+def resample_ref_ld(x, ker, width, up, down, M):
+    """include/ntm.h's formula of ntm_resample_fir in numpy.longdouble:
+    y[b][i*up + p] = sum_k ker[p][k] xpad[b][i*down + k], xpad[j] = x[j - width] (zero outside [0, N)), i*up + p < M
+    -> (y (B, M) longdouble, s (B, M) float64 = sum_k |ker[p][k]| |xpad[i*down + k]|)."""
+    x, ker = np.asarray(x, np.longdouble), np.asarray(ker, np.longdouble)
+    B, N = x.shape
+    taps = 2 * width + down
+    assert ker.shape == (up, taps)
+    o = np.arange(M)
+    i, p = o // up, o % up
+    j = i[:, None] * down + np.arange(taps)[None, :] - width                 # (M, taps) index into x
+    ok = (j >= 0) & (j < N)
+    xg = np.where(ok[None], x[:, np.clip(j, 0, N - 1)], np.longdouble(0))    # (B, M, taps)
+    kg = ker[p]                                                              # (M, taps)
+    return (xg * kg[None]).sum(-1), np.abs(xg * kg[None]).sum(-1).astype(np.float64)
+
+
+def fir_ref_ld(x, h):
+    """include/ntm.h's formula of ntm_fir_f64 without the clamp in numpy.longdouble: y[b][n] = sum_{k < taps, k <= n}
+    h[k] x[b][n-k] -> (y (B, N) longdouble, s (B, N) float64 = sum |h[k]| |x[n-k]|)."""
+    x, h = np.asarray(x, np.longdouble), np.asarray(h, np.longdouble)
+    B, N = x.shape
+    j = np.arange(N)[:, None] - np.arange(len(h))[None, :]                   # (N, taps)
+    xg = np.where((j >= 0)[None], x[:, np.clip(j, 0, N - 1)], np.longdouble(0))
+    return (xg * h[None, None]).sum(-1), np.abs(xg * h[None, None]).sum(-1).astype(np.float64)
+
+
+def resample_input(seed, B, N):
+    return np.random.default_rng(seed).uniform(-1.0, 1.0, (B, N))
+
+
+def fir_case(taps, N, seed=0):
+    """(x (2, N), h (taps,)) with outputs exactly on +-1, just inside, and far outside: h[0] = 1 passes x[0] through
+    alone at n = 0, and the first samples of the rows are +-1 and +-(1 - 2^-53); the rest is noise of amplitude 3."""
+    rng = np.random.default_rng(1000 * taps + N + seed)
+    h = rng.uniform(-1.0, 1.0, taps) / max(1, taps) ** 0.5
+    h[0] = 1.0
+    x = 3.0 * rng.standard_normal((2, N))
+    x[0, 0], x[1, 0] = 1.0, -1.0
+    if N > taps:                      # a later sample that lands exactly on the rail: everything in its window is zero
+        x[:, -taps:] = 0.0
+        x[0, -1], x[1, -1] = -(1.0 - U53), 1.0 - U53
+    return x, h
+
+
 def bench_record(stdout, detail=True):
     """bench.py's output contract: exactly ONE JSON line on stdout, the last one, shorter than 4 KB (the driver's parser lost
     round 5's 20 KB line), naming the detail file that holds the full record.  -> (compact line dict, full record dict);

@@ -562,7 +562,8 @@ def test_saturating_inputs(ntm, variant):
 
 
 def test_g9_tape_hmag(ntm):
-    """N4: Jiles-Atherton RK4 stage against the reference's own Tape.H_mag output (fp64), state carried."""
+    """N4: Jiles-Atherton RK4 stage against the reference's own Tape.H_mag output (fp64), state carried.
+    (The random-walk input below is clamped to +-Ms almost everywhere; the unsaturated cases live in tests/test_gpu_tape.py.)"""
     g = load("g9_tape_hmag.npz")
     H, split = g["H"], int(g["split"])
     tp = ntm.TapeMagnetization(batch_size=H.shape[0])
