@@ -472,6 +472,43 @@ int ntm_gru_forward_replicas(const float *w_ih, const float *w_hh, const float *
 int ntm_delay_backward(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
                        int D, int warmup, int flags, void *stream);
 
+/*
+ * ---- DiffDelRNN block by block (additions within ABI version 9): what a real-time host needs to advance B streams of
+ * DiffDelRNN(1, 64, 1, skip=False) by `block` samples per call with ONE launch and O(block) traffic of delay state per stream.
+ * The delay line's history lives in a caller-owned ring per stream, ring [B, C] floats with C = ntm_diffdel_stream_ring_floats(D,
+ * block) (a power of two >= D + block), beside a sample counter pos [B] (int64, device) that only the kernel reads and advances:
+ * no host-side position, so the block call can be captured into a graph and replayed.  Sample i of a stream, counted from the
+ * ring's origin, is ring[b][i mod C]; the reference's buffer (dl_state of ntm_delay_forward, oldest first) is samples
+ * pos - D .. pos - 1.
+ */
+
+/* Floats per stream of the ring for a delay line of D samples advanced `block` samples per call; 0 for a negative argument. */
+int64_t ntm_diffdel_stream_ring_floats(int D, int64_t block);
+
+/* ring, pos <- the reference's buffer dl_state [B,D] (contiguous): samples 0 .. D-1, pos = D.  C as above for the block size
+ * that will follow (any power of two >= D is accepted here).  B == 0 is a successful no-op. */
+int ntm_diffdel_stream_seed(const float *dl_state, float *ring, int64_t *pos, int64_t B, int D, int64_t C, void *stream);
+
+/* dl_state [B,D] <- the reference's buffer as the ring holds it now (what DiffDelRNN's delay line would carry after the same calls). */
+int ntm_diffdel_stream_export(const float *ring, const int64_t *pos, float *dl_state, int64_t B, int D, int64_t C, void *stream);
+
+/*
+ * One block of DiffDelRNN.forward(x, del_traj, warmup) (code/model.py:393-424) in one launch, a workgroup per stream: the
+ * low-latency GRU step with the bias-free head gives pre_d, the delay line reads its taps from the ring and writes y.
+ * x [B,block] (row stride x_stride_b), d [B,block] in samples (d_stride_b), y and pre_d [B,block] (both y_stride_b; pre_d may
+ * be NULL: not returned); h_state [B,64] in / out, ring / pos as above with C >= D + block, all required.
+ * pre_d and h_state are the bits of ntm_gru_forward_ex with NTM_GRU_LAT on the same block, y the bits of ntm_delay_forward on
+ * that pre_d and the exported buffer, for every block size and any split of a signal into blocks.  warmup != 0: y = pre_d,
+ * the ring and pos move on (code/model.py:288-292).  err_flag (device int32, may be NULL) is raised to 1 by any d > D or NaN
+ * d, as in ntm_delay_forward; unlike there nothing is frozen: from the violating call on y, pre_d and the streamer's own state
+ * (h_state, ring, pos) are unspecified until the caller seeds them again -- nothing else is touched.
+ * B == 0 or block == 0 is a successful no-op.  y, pre_d must not alias x, d or each other.
+ */
+int ntm_diffdel_stream_block(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                             const float *x, const float *d, float *y, float *pre_d, int64_t B, int64_t block,
+                             int64_t x_stride_b, int64_t d_stride_b, int64_t y_stride_b, float *h_state, float *ring, int64_t C,
+                             int64_t *pos, int D, int warmup, int32_t *err_flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

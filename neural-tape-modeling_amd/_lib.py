@@ -67,6 +67,11 @@ _SIGNATURES = {
     "ntm_esr_grad_replicas": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "ntm_esr_dcpre_grad_replicas": (_int, [_vp, _vp, _i64, _i64, _i64, ctypes.c_float, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "ntm_gru_forward_replicas": (_int, [_vp] * 8 + [_i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    # DiffDelRNN block by block (additions within ABI version 9)
+    "ntm_diffdel_stream_ring_floats": (_i64, [_int, _i64]),
+    "ntm_diffdel_stream_seed": (_int, [_vp, _vp, _vp, _i64, _int, _i64, _vp]),
+    "ntm_diffdel_stream_export": (_int, [_vp, _vp, _vp, _i64, _int, _i64, _vp]),
+    "ntm_diffdel_stream_block": (_int, [_vp] * 9 + [_i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _int, _int, _vp, _vp]),
 }
 TRAIN_GRAD_FLOATS = 12929   # include/ntm.h NTM_TRAIN_GRAD_FLOATS: w_ih | w_hh | b_ih | b_hh | w_o | b_o of GRU(1, 64) + Linear(64, 1)
 

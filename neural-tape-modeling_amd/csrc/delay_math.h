@@ -1,7 +1,8 @@
 // Arithmetic of the time-varying fractional delay line (TimeVaryingDelayLine.forward, code/model.py:269-320, in closed
-// form), shared by the streaming pass (aux_kernels.hip, delay_apply_kernel) and the pass fused into the GRU kernel's
-// output flush (gru_mfma2.hip, FUSE).  Every product and sum rounds separately in the reference's order (fma
-// contraction off), so both users give the bits of the reference's O(T*D) unfold formulation.
+// form), shared by the streaming pass (aux_kernels.hip, delay_apply_kernel), the pass fused into the GRU kernel's
+// output flush (gru_mfma2.hip, FUSE) and the block streamer's ring (diffdel_stream.hip).  Every product and sum rounds
+// separately in the reference's order (fma contraction off), so all users give the bits of the reference's O(T*D) unfold
+// formulation.
 #pragma once
 #include "ntm_common.h"
 
@@ -9,8 +10,10 @@ namespace ntm {
 
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access at 4-byte alignment
 
-// one output sample: y[n] = w_b x[n-k-1] + w_a x[n-k] with the reference's tap order and rounding
-__device__ __forceinline__ float delay_sample(const float *xb, const float *bb, int D, int64_t n, float dn)
+// one output sample: y[n] = w_b z[n-k-1] + w_a z[n-k] with the reference's tap order and rounding; z(i) fetches sample i of
+// the stream, wherever the caller keeps it (i < 0: history)
+template <class Fetch>
+__device__ __forceinline__ float delay_sample_at(const Fetch &z, int D, int64_t n, float dn)
 {
 #pragma clang fp contract(off)   // products and the sum must round separately (bit-exact parity)
     const float kf = floorf(dn);
@@ -21,12 +24,23 @@ __device__ __forceinline__ float delay_sample(const float *xb, const float *bb, 
         if (mf < 0.0f || mf > (float)D) continue;
         const float w = 1.0f - fabsf(mf - dn);
         if (!(w > 0.0f)) continue;
-        const int64_t src = n - (int64_t)mf;
-        const float xv = src >= 0 ? xb[src] : bb[D + src];
+        const float xv = z(n - (int64_t)mf);
         const float prod = w * xv;
         acc = acc + prod;
     }
     return acc;
+}
+
+// the samples in x, the D before them in the carried buffer bb (oldest first)
+__device__ __forceinline__ float delay_sample(const float *xb, const float *bb, int D, int64_t n, float dn)
+{
+    return delay_sample_at([=](const int64_t src) { return src >= 0 ? xb[src] : bb[D + src]; }, D, n, dn);
+}
+
+// the samples in a ring of mask + 1 floats (a power of two, above D), sample i at ring[i & mask]: n counts from the ring's origin
+__device__ __forceinline__ float delay_sample_ring(const float *ring, int64_t mask, int D, int64_t n, float dn)
+{
+    return delay_sample_at([=](const int64_t src) { return ring[src & mask]; }, D, n, dn);
 }
 
 // the same sample when both taps are known to lie inside x and inside [0, D]: xa = x[n-k], xb1 = x[n-k-1]

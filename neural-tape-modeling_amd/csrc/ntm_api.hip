@@ -808,4 +808,75 @@ int ntm_delay_backward(const float *gy, const float *d, const float *g_newbuf, f
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_delay_backward");
 }
 
+// ---- DiffDelRNN block by block (csrc/diffdel_stream.hip)
+static int64_t stream_ring_floats(int64_t D, int64_t block)
+{
+    int64_t C = 1;
+    while (C < D + block) C <<= 1;
+    return C;
+}
+
+int64_t ntm_diffdel_stream_ring_floats(int D, int64_t block)
+{
+    return (D < 0 || block < 0 || block > ((int64_t)1 << 40)) ? 0 : stream_ring_floats(D, block);
+}
+
+// what the three calls on a ring refuse first
+static int bad_ring(const char *who, int64_t B, int D, int64_t C)
+{
+    const std::string w(who);
+    if (B < 0 || D < 0) return fail(NTM_EINVAL, w + ": negative size");
+    if (B > 0x7fffffff) return fail(NTM_EINVAL, w + ": at most 2^31 - 1 streams per call");
+    if (C < 1 || (C & (C - 1)) || C < D) return fail(NTM_EINVAL, w + ": C must be a power of two, at least D (ntm_diffdel_stream_ring_floats)");
+    return NTM_OK;
+}
+
+int ntm_diffdel_stream_seed(const float *dl_state, float *ring, int64_t *pos, int64_t B, int D, int64_t C, void *stream)
+{
+    if (int rc = bad_ring("ntm_diffdel_stream_seed", B, D, C)) return rc;
+    if (B == 0) return NTM_OK;
+    if (!ring || !pos || (D > 0 && !dl_state)) return fail(NTM_EINVAL, "ntm_diffdel_stream_seed: null pointer");
+    hipError_t e = ntm::launch_diffdel_stream_seed(dl_state, ring, pos, B, D, C, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_diffdel_stream_seed");
+}
+
+int ntm_diffdel_stream_export(const float *ring, const int64_t *pos, float *dl_state, int64_t B, int D, int64_t C, void *stream)
+{
+    if (int rc = bad_ring("ntm_diffdel_stream_export", B, D, C)) return rc;
+    if (B == 0 || D == 0) return NTM_OK;
+    if (!ring || !pos || !dl_state) return fail(NTM_EINVAL, "ntm_diffdel_stream_export: null pointer");
+    hipError_t e = ntm::launch_diffdel_stream_export(ring, pos, dl_state, B, D, C, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_diffdel_stream_export");
+}
+
+int ntm_diffdel_stream_block(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o,
+                             const float *x, const float *d, float *y, float *pre_d, int64_t B, int64_t block, int64_t x_stride_b,
+                             int64_t d_stride_b, int64_t y_stride_b, float *h_state, float *ring, int64_t C, int64_t *pos, int D,
+                             int warmup, int32_t *err_flag, void *stream)
+{
+    // every argument is checked BEFORE anything is enqueued
+    if (B < 0 || block < 0 || D < 0) return fail(NTM_EINVAL, "ntm_diffdel_stream_block: negative size");
+    if (B == 0 || block == 0) return NTM_OK;
+    if (int rc = bad_ring("ntm_diffdel_stream_block", B, D, C)) return rc;
+    if (block > C || C - block < D) return fail(NTM_EINVAL, "ntm_diffdel_stream_block: the ring must hold D + block samples (ntm_diffdel_stream_ring_floats)");
+    if (!w_ih || !w_hh || !b_ih || !b_hh || !w_o || !x || !d || !y || !h_state || !ring || !pos)
+        return fail(NTM_EINVAL, "ntm_diffdel_stream_block: null pointer");
+    if (x_stride_b < block || d_stride_b < block || y_stride_b < block) return fail(NTM_EINVAL, "ntm_diffdel_stream_block: row stride below block");
+    if (y == x || y == d || pre_d == x || pre_d == d || pre_d == y)
+        return fail(NTM_EINVAL, "ntm_diffdel_stream_block: y and pre_d must not alias x, d or each other");
+    ntm::StreamArgs sa{};
+    sa.g = ntm::GruArgs{w_ih, w_hh, b_ih, b_hh, w_o, nullptr, x, pre_d ? pre_d : y, h_state, B, block, x_stride_b, y_stride_b, nullptr, 0, 0};
+    sa.g.dd = d;
+    sa.g.yd = y;
+    sa.g.dl_flag = err_flag;
+    sa.g.D = D;
+    sa.g.warmup = warmup != 0;
+    sa.ds = d_stride_b;
+    sa.ring = ring;
+    sa.pos = pos;
+    sa.mask = C - 1;
+    hipError_t e = ntm::launch_diffdel_stream(sa, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_diffdel_stream_block");
+}
+
 }  // extern "C"

@@ -74,6 +74,19 @@ hipError_t launch_gru_lat(const GruArgs &a, hipStream_t stream);
 hipError_t launch_gru_lat_replicas(const GruArgs &a, hipStream_t stream);   // a.bper > 0, a.B = R * a.bper, the parameters are stacks
 hipError_t launch_gru_small(const GruArgs &a, int H, hipStream_t stream);   // any H in [1, 1024] but 64
 hipError_t launch_gru_io(const GruArgs &a, int H, int I, int O, hipStream_t stream);   // any input_size / output_size (gru_small.hip)
+// one block of the DiffDelRNN streamer (diffdel_stream.hip): the recurrence's arguments and the stream's ring
+struct StreamArgs {
+    GruArgs g;          // x / xs, y = the rows pre_d is written to (the caller's pre_d, else yd), ys (of y AND yd), h_state, B,
+                        // T = block; dd = d, yd = the delayed output, D, warmup, dl_flag
+    int64_t ds;         // row stride of d
+    float *ring;        // [B, mask + 1]
+    int64_t *pos;       // [B] samples written so far, counted from the ring's origin
+    int64_t mask;       // C - 1, C a power of two >= D + block
+};
+hipError_t launch_diffdel_stream(const StreamArgs &sa, hipStream_t stream);
+hipError_t launch_diffdel_stream_seed(const float *dl_state, float *ring, int64_t *pos, int64_t B, int D, int64_t C, hipStream_t stream);
+hipError_t launch_diffdel_stream_export(const float *ring, const int64_t *pos, float *dl_state, int64_t B, int D, int64_t C,
+                                        hipStream_t stream);
 hipError_t launch_debug_transpose(const float *in, float *out, hipStream_t stream);
 // training (gru_train.hip)
 int64_t train_grad_floats();

@@ -85,15 +85,41 @@ class BlockStreamer:
     was measured too and is SLOWER by 8 us per block: with a single kernel per block there is nothing for a graph to
     amortise, so it is off by default.  Same numbers as model.forward() on the concatenated blocks either way.
 
-        s = BlockStreamer(model, B=16, block=128)          # RNN only; warm-start included unless warm=False
+        s = BlockStreamer(model, B=16, block=128)          # warm-start included unless warm=False
         y = s.process(x_block)                             # (B,1,block) in -> (B,1,block) view, valid until the next call
+
+    A DiffDelRNN streams the same way, with the delay trajectory of the block beside the audio:
+
+        y = s.process(x_block, d_block)                    # d_block (B,1,block) in SAMPLES, what DiffDelRNN.forward takes
+        y = s.process(x_block, d_block, warmup=True)       # the warm-up call of DiffDelRNN.forward: y = pre_d, the state moves on
+        s.raise_if_violated()                              # the delay-range assert, one synchronisation, whenever the caller likes
+        hidden, buffer = s.export_state()                  # (1,B,H), (B,1,D): what the model would carry after the same calls
+
+    For hidden size 64 (input / output size 1, no skip connection) a block is ONE launch (csrc/diffdel_stream.hip): the
+    low-latency recurrence, and the delay line on a per-stream ring in device memory whose position lives on the device too
+    -- O(block) floats of delay state move per stream and call where DiffDelRNN.forward rewrites the whole buffer, and nothing
+    is allocated.  y, `s.pre` (pre_d) and the exported state are the bits of model.forward() block by block with
+    kernel_variant "lat" and delay_mode "two_pass" (what "auto" runs up to 1024 streams).  Every other hidden size runs
+    ntm_diffdel_gru_forward per block on preallocated buffers: the GRU launch and the delay pass with its shifted buffer, the
+    bits of model.forward().  tools/stream_probe.py measures both beside the RNN streamer.
+
+    The streamer owns its state (hidden, delay line, range flag): seeded from model.hidden / model.diffdel.buffer when both are
+    set for B streams (a model that has been running), else from initialize_hidden(B, model.max_delay) -- plus the model's
+    warm_start(), one stream broadcast to B as in predict(), unless warm=False.  process() never touches the model's state.
+    After a delay above the delay line's length (raise_if_violated() raises AssertionError, as the model does) the
+    streamer's outputs and state are unspecified: build a new one.
     """
 
     def __init__(self, model, B, block, warm=True, use_graph=False):
         from . import _lib
         from ._lib import ptr
+        self.graph = None
+        if isinstance(model, DiffDelRNN):
+            self._init_diffdel(model, B, block, warm, use_graph)
+            return
         if not isinstance(model, RNN):
-            raise TypeError("BlockStreamer drives the GRU model (RNN)")
+            raise TypeError("BlockStreamer drives the GRU models (RNN, DiffDelRNN)")
+        self.diffdel = False
         dev = model.GRU.weight_hh_l0.device
         self.model, self.B, self.block = model, B, block
         self.x = torch.zeros(B, 1, block, device=dev, dtype=torch.float32)
@@ -114,25 +140,122 @@ class BlockStreamer:
             _lib.check(rc, "ntm_gru_forward")
 
         self._launch = launch
-        self.graph = None
         if use_graph:
             h0 = self.h.clone()
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                launch()                                    # warm the code path outside the capture
-            torch.cuda.current_stream().wait_stream(side)
-            self.h.copy_(h0)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                launch()
-            self.h.copy_(h0)                                # capture does not execute, but keep the state explicit
+            self._capture(dev, launch, lambda: self.h.copy_(h0))
+
+    def _capture(self, dev, launch, restore):
+        """Capture launch() into self.graph; restore() puts back the state a launch moves on."""
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            launch()                                        # warm the code path outside the capture
+        torch.cuda.current_stream().wait_stream(side)
+        restore()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            launch()
+        restore()                                           # capture does not execute, but keep the state explicit
+
+    def _init_diffdel(self, model, B, block, warm, use_graph):
+        from . import _lib
+        from ._lib import ptr
+        if model.input_size != 1 or model.output_size != 1 or model.skip:
+            raise ValueError("BlockStreamer: DiffDelRNN streams with input_size = output_size = 1 and no skip connection")
+        dev = model.GRU.weight_hh_l0.device
+        H = model.hidden_size
+        dl = model.diffdel
+        self.model, self.B, self.block, self.diffdel = model, B, block, True
+        self.x = torch.zeros(B, 1, block, device=dev, dtype=torch.float32)
+        self.d = torch.zeros(B, 1, block, device=dev, dtype=torch.float32)
+        self.y = torch.empty(B, 1, block, device=dev, dtype=torch.float32)
+        self.pre = torch.empty(B, 1, block, device=dev, dtype=torch.float32)
+        self.err = torch.zeros(1, device=dev, dtype=torch.int32)
+        if not (model.hidden is not None and model.hidden.shape[1] == B and dl.buffer.shape[0] == B):
+            if warm:                                        # DiffDelRNN._predict_start: one stream warmed, broadcast to B
+                model.initialize_hidden(1, model.max_delay)
+                model.warm_start()
+            else:
+                model.initialize_hidden(B, model.max_delay)
+        D = self.D = int(dl.max_delay)
+        if dl.buffer.shape[2] != D:
+            raise RuntimeError(f"BlockStreamer: delay buffer {list(dl.buffer.shape)} vs max_delay {D}")
+        if model.hidden is None:
+            self.h = torch.zeros(1, B, H, device=dev, dtype=torch.float32)
+        else:
+            self.h = model.hidden.to(device=dev, dtype=torch.float32).expand(1, B, H).contiguous().clone()
+        buf = dl.buffer.to(device=dev, dtype=torch.float32).expand(B, 1, D).contiguous().clone()
+        g, lib = model.GRU, _lib.lib()
+        w = (ptr(g.weight_ih_l0), ptr(g.weight_hh_l0), ptr(g.bias_ih_l0), ptr(g.bias_hh_l0), ptr(model.output.weight))
+        self.one_launch = H == 64
+        if self.one_launch:
+            C = self.C = int(lib.ntm_diffdel_stream_ring_floats(D, block))
+            self.buf = torch.zeros(B, C, device=dev, dtype=torch.float32)      # the ring
+            self.pos = torch.zeros(B, device=dev, dtype=torch.int64)
+
+            def seed():
+                _lib.check(lib.ntm_diffdel_stream_seed(ptr(buf), ptr(self.buf), ptr(self.pos), B, D, C, _lib.current_stream()),
+                           "ntm_diffdel_stream_seed")
+
+            def launch(warmup=0):
+                rc = lib.ntm_diffdel_stream_block(*w, ptr(self.x), ptr(self.d), ptr(self.y), ptr(self.pre), B, block, block, block,
+                                                  block, ptr(self.h), ptr(self.buf), C, ptr(self.pos), D, warmup, ptr(self.err),
+                                                  _lib.current_stream())
+                _lib.check(rc, "ntm_diffdel_stream_block")
+            seed()
+        else:
+            self.buf = buf.clone()                          # the reference's shifted buffer, moved on in place
+
+            def seed():
+                self.buf.copy_(buf)
+
+            def launch(warmup=0):
+                rc = lib.ntm_diffdel_gru_forward_ex(*w, H, ptr(self.x), ptr(self.d), ptr(self.y), ptr(self.pre), B, block, ptr(self.h),
+                                                    ptr(self.buf), D, warmup, ptr(self.err), _lib.NTM_DIFFDEL_TWO_PASS,
+                                                    _lib.current_stream())
+                _lib.check(rc, "ntm_diffdel_gru_forward")
+        self._launch = launch
+        if use_graph:                                       # the normal block; a warm-up call takes the plain launch
+            h0 = self.h.clone()
+            self._capture(dev, launch, lambda: (self.h.copy_(h0), seed(), self.err.zero_()))
 
     @torch.no_grad()
-    def process(self, x_block):
+    def process(self, x_block, d_block=None, warmup=False):
+        if not self.diffdel:
+            if d_block is not None or warmup:
+                raise TypeError("BlockStreamer.process: an RNN streamer takes x_block alone")
+        else:
+            if d_block is None:
+                raise TypeError("BlockStreamer.process: a DiffDelRNN streamer needs d_block (B,1,block), the delays in samples")
+            if tuple(d_block.shape) not in ((self.B, 1, self.block), (self.B, self.block)):
+                raise ValueError(f"BlockStreamer.process: d_block {tuple(d_block.shape)}, expected {(self.B, 1, self.block)}")
+            self.d.copy_(d_block.reshape(self.B, 1, self.block), non_blocking=True)
         self.x.copy_(x_block.reshape(self.B, 1, self.block), non_blocking=True)
-        if self.graph is not None:
+        if warmup:
+            self._launch(1)
+        elif self.graph is not None:
             self.graph.replay()
         else:
             self._launch()
         return self.y
+
+    def raise_if_violated(self):
+        """The model's `assert max_delay >= max(dt)` for every block since the last check (one host synchronisation)."""
+        if self.diffdel and int(self.err.item()) != 0:
+            self.err.zero_()
+            raise AssertionError("max_delay >= max(dt) violated")
+
+    @torch.no_grad()
+    def export_state(self):
+        """-> (hidden (1,B,H), buffer (B,1,D)) in the reference's layout: what a DiffDelRNN carries after the same calls, and
+        takes back (model.hidden, model.diffdel.buffer)."""
+        from . import _lib
+        from ._lib import ptr
+        if not self.diffdel:
+            raise TypeError("BlockStreamer.export_state: a DiffDelRNN streamer's state; an RNN streamer's is `h`")
+        if not self.one_launch:
+            return self.h.clone(), self.buf.clone()
+        buf = torch.empty(self.B, 1, self.D, device=self.buf.device, dtype=torch.float32)
+        rc = _lib.lib().ntm_diffdel_stream_export(ptr(self.buf), ptr(self.pos), ptr(buf), self.B, self.D, self.C, _lib.current_stream())
+        _lib.check(rc, "ntm_diffdel_stream_export")
+        return self.h.clone(), buf

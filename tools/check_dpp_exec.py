@@ -17,7 +17,7 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "neural-tape-modeling_amd", "csrc")
-DEFAULT = [os.path.join(CSRC, f) for f in ("gru_mfma2.hip", "gru_lat.hip", "gru_small.hip")]
+DEFAULT = [os.path.join(CSRC, f) for f in ("gru_mfma2.hip", "gru_lat.hip", "diffdel_stream.hip", "gru_small.hip")]
 DPP = re.compile(r"\b(row_shr|row_shl|row_ror|row_bcast|row_newbcast|row_mirror|row_half_mirror|quad_perm|wave_shr|wave_shl|wave_ror|wave_rol)\b")
 SAVE = re.compile(r"^s_and_saveexec_b64\s+(s\[\d+:\d+\])")
 FLIP = re.compile(r"^s_(?:andn2|or|xor)_saveexec_b64\s+(s\[\d+:\d+\]),\s*(s\[\d+:\d+\])")      # the else-flip of an if / else
