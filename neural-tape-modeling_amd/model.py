@@ -1434,7 +1434,11 @@ DC_PRE_R = 0.995
 
 @torch.no_grad()
 def esr_dcpre_sums(output, target, skip=0, R=DC_PRE_R):
-    """Per-stream ESR sums of the DC-blocked signals ((1 - z^-1)/(1 - R z^-1), zero state at `skip`)."""
+    """Per-stream ESR sums of the DC-blocked signals ((1 - z^-1)/(1 - R z^-1), zero state at `skip`).
+    The filter runs in float32: against the exact recursion on the same inputs the sums are within 2e-5 relative at the
+    shipped pole 0.995 for every length tested (to 65 536 samples: 2.9e-6) and at R = 0.9999 up to 16 384 samples (1.7e-5 on a
+    DC level with small noise); at R = 0.9999 the error grows with the length, 2.6e-5 at 32 768 and 3.0e-5 at 65 536 samples
+    (measured on an MI355X, tests/test_gpu_losses.py)."""
     y = _as_bt(output, "esr_dcpre_sums")
     t = _as_bt(target, "esr_dcpre_sums")
     B, T = y.shape

@@ -237,3 +237,121 @@ def bench_record(stdout, detail=True):
         assert c[k] == d[k], k
     assert c["roofline"]["frac"] == d["roofline"]["frac"] and c["roofline"]["kernel_ms"] == d["roofline"]["kernel_ms"]
     return c, d
+
+
+# ---- time-domain losses (tests/test_gpu_losses.py; the references and the input conditions are pinned on the CPU by
+# tests/test_oracle_losses.py)
+def _loss_signals(y, t, skip):
+    """(e, t) of the window [skip, T) as longdouble (2, B, n): e = t - y formed in float32, the definition the kernels and
+    the oracle share."""
+    y, t = np.asarray(y), np.asarray(t)
+    assert y.dtype == np.float32 and t.dtype == np.float32 and y.shape == t.shape and y.ndim == 2 and 0 <= skip <= y.shape[1]
+    with np.errstate(all="ignore"):
+        e = t - y
+    assert e.dtype == np.float32
+    return np.stack([e[:, skip:], t[:, skip:]]).astype(np.longdouble)
+
+
+def esr_sums_exact(y, t, skip):
+    """include/ntm.h's ntm_esr_sums per stream, (B, 2) numpy.longdouble: sum (t - y)^2 | sum t^2 over [skip, T) with the
+    float32 difference, squares and sums in longdouble."""
+    u = _loss_signals(y, t, skip)
+    return (u * u).sum(-1).T
+
+
+def dcpre_sums_exact(y, t, skip, R, dtype=np.longdouble):
+    """include/ntm.h's ntm_esr_dcpre_sums per stream, (B, 2) `dtype`: both e = t - y (float32) and t pass
+    f[n] = (u[n] - u[n-1]) + R f[n-1] from f = 0 and u[skip-1] := 0 at sample `skip`, the pole being the float32 value of
+    `R`; recursion and sums of squares in `dtype` (longdouble: 64-bit mantissa, rounding 5e-20 per operation against the
+    6e-8 of the kernels' float32 filters).  A sequence of poles gives (len(R), B, 2)."""
+    u = _loss_signals(y, t, skip).astype(dtype)                               # (2, B, n)
+    poles = np.atleast_1d(np.asarray(R, np.float32)).astype(dtype)
+    r = poles.reshape(-1, 1, 1)
+    f = np.zeros((len(poles),) + u.shape[:2], dtype)
+    prev, s = np.zeros(u.shape[:2], dtype), np.zeros_like(f)
+    with np.errstate(all="ignore"):
+        for n in range(u.shape[2]):
+            cur = u[:, :, n]
+            f = (cur - prev) + r * f
+            s += f * f
+            prev = cur
+    s = np.moveaxis(s, 1, 2)                                                  # (poles, B, 2)
+    return s if np.ndim(R) else s[0]
+
+
+def _fam_noise_offset(rng, B, T):
+    t = (rng.standard_normal((B, T)) + 0.3).astype(np.float32)
+    return (t + 0.1 * rng.standard_normal((B, T))).astype(np.float32), t
+
+
+def _fam_dc_small_ac(rng, B, T):
+    t = (1.0 + 1e-3 * rng.standard_normal((B, T))).astype(np.float32)
+    return (0.9 + 1e-3 * rng.standard_normal((B, T))).astype(np.float32), t
+
+
+def _fam_step(rng, B, T):
+    t = np.zeros((B, T), np.float32)
+    t[:, T // 2 + 3:] = 0.7
+    return (0.9 * t + 1e-3 * rng.standard_normal((B, T))).astype(np.float32), t
+
+
+def _fam_slow_sine(rng, B, T):
+    ph = rng.uniform(0.0, 2 * np.pi, (B, 1))
+    n = np.arange(T)[None, :]
+    t = (0.5 * np.sin(2e-3 * n + ph) + 0.5).astype(np.float32)
+    return (0.45 * np.sin(2e-3 * n + ph + 0.1) + 0.48 + 1e-3 * rng.standard_normal((B, T))).astype(np.float32), t
+
+
+def _fam_const(rng, B, T):
+    lv = rng.uniform(0.2, 1.0, (B, 1))
+    return np.broadcast_to(0.4 * lv, (B, T)).astype(np.float32), np.broadcast_to(lv, (B, T)).astype(np.float32)
+
+
+def _fam_tight_fit(rng, B, T):
+    _, t = _fam_dc_small_ac(rng, B, T)
+    return (t * (1.0 + 1e-6 * rng.standard_normal((B, T)))).astype(np.float32), t
+
+
+# name -> generator(rng, B, T) -> (y, t) float32 (B, T): the output / target pairs of the time-domain loss tests
+LOSS_FAMILIES = {
+    "noise_offset": _fam_noise_offset,     # white noise on a 0.3 offset, error 0.1 noise (test_esr_dcpre_sums_vs_oracle's inputs)
+    "dc_small_ac": _fam_dc_small_ac,       # level 1.0 (output 0.9) with 1e-3 noise: the filter state stays large
+    "step": _fam_step,                     # 0 -> 0.7 three samples after the middle
+    "slow_sine": _fam_slow_sine,           # 0.5 sin(2e-3 n + phase) + 0.5, a phase per stream
+    "const": _fam_const,                   # a level per stream: the blocker's impulse response alone
+    "tight_fit": _fam_tight_fit,           # y = t (1 + 1e-6 xi) on a dc_small_ac target: t - y is a few float32 roundings
+}
+
+
+def loss_family(name, seed, B, T):
+    y, t = LOSS_FAMILIES[name](np.random.default_rng(seed), B, T)
+    return np.ascontiguousarray(y), np.ascontiguousarray(t)
+
+
+R_BELOW_ONE = float(np.nextafter(np.float32(1.0), np.float32(0.0)))          # the largest float32 pole the entry points accept
+LOSS_BAR = 2e-5                                                              # the project's bar on the DCPreESR sums
+# the streaming kernel (esr_dcpre_kernel): 4 waves x 1024-sample chunks, n = T - skip
+DCPRE_STRUCT_N = (0, 1, 2, 15, 16, 17, 1023, 1024, 1025, 2048, 2049, 3073, 4095, 4096, 4097, 5121, 8192, 8193)
+DCPRE_STRUCT_SKIP = (0, 7, 1024)
+DCPRE_STRUCT_B, DCPRE_STRUCT_SEED = 3, 41
+DCPRE_COND_N, DCPRE_COND_SKIP, DCPRE_COND_B, DCPRE_COND_SEED = (17, 1025, 4097), 5, 2, 43
+DCPRE_COND_POLES = (0.0, 0.5, 0.9, 0.995)
+DCPRE_GROWTH_N, DCPRE_GROWTH_B, DCPRE_GROWTH_SEED = 65536, 2, 47
+DCPRE_GROWTH_FAMILIES = ("slow_sine", "dc_small_ac")
+# the fused flush (gru_mfma2.hip): 64-sample tiles, skip a multiple of 4
+FLUSH_FAMILIES = ("dc_small_ac", "step", "slow_sine", "const")
+FLUSH_T = (1, 4, 63, 64, 65, 128, 129, 300)
+FLUSH_POLES = (0.995, 0.9, 0.0)
+FLUSH_SEED = 53
+
+
+def flush_skips(T):
+    return tuple(s for s in dict.fromkeys((0, 4, 64, 68, T // 4 * 4)) if s <= T)
+
+
+def rel_err(got, want):
+    """|got - want| / |want| elementwise in longdouble; 0 where both are 0, inf where only `want` is."""
+    got, want = np.asarray(got, np.longdouble), np.asarray(want, np.longdouble)
+    with np.errstate(all="ignore"):
+        r = np.abs(got - want) / np.abs(want)
+    return np.where(want == 0, np.where(got == 0, 0.0, np.inf), r).astype(np.float64)

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import oracle
-from helpers import load, oracle_weights
+from helpers import dcpre_sums_exact, load, oracle_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -500,6 +500,7 @@ def test_esr_dcpre_sums_vs_oracle(ntm):
         s = ntm.esr_dcpre_sums(dev(y).unsqueeze(1), dev(t).unsqueeze(1), skip).cpu().numpy()
         so = oracle.esr_dcpre_sums(y, t, skip)
         assert np.allclose(s, so, rtol=2e-5, atol=1e-12), (B, T, skip)
+        assert np.allclose(s, dcpre_sums_exact(y, t, skip, 0.995).astype(np.float64), rtol=2e-5, atol=1e-12), (B, T, skip)   # and the exact sums
     # the whole-tensor loss object used like `loss_fcn(output, target)` in code/test-model.py:386-388
     tot = float(ntm.DCPreESR()(dev(y).unsqueeze(1), dev(t).unsqueeze(1)))
     s0 = oracle.esr_dcpre_sums(y, t, 0).sum(0)
