@@ -275,6 +275,24 @@ int ntm_mel_sums(const float *y, const float *t, int64_t B, int64_t T, int64_t s
                  const float *mel_w, double *out, void *stream);
 
 /*
+ * Adjoint of ntm_stft_sums for ONE resolution (the backward of MRSTFTLoss): with per-stream coefficients
+ * coef[b] = (c_sc, c_log, c_lin) (device, [B,3] fp32),
+ *   dy[b] = d/dy sum_cells ( 1/2 c_sc (my - mt)^2 + c_log |ln my - ln mt| + c_lin |my - mt| )
+ * over the cells of stream b, my / mt the magnitudes of ntm_stft_sums (same frames, padding, window -- here each value
+ * correctly rounded to fp32 -- and floor: where the
+ * unclamped power of the prediction is at or below power_eps the cell contributes nothing; sgn(0) = 0).  Gradients go to
+ * the prediction y only.  dy [B,T] fp32: samples before `skip` get 0.  accumulate != 0: dy[i] = dy[i] + gradient in
+ * place of the store (samples before `skip` stay as they are) -- how the caller adds the resolutions, in its call order.
+ * ws: ntm_stft_grad_workspace_floats(B, T, skip, n_fft, hop) floats of device scratch (the windowed frame gradients,
+ * B * frames * n_fft; -1 for sizes ntm_stft_grad refuses).  No atomics: the overlap-add is a gather with a fixed order
+ * of addition (csrc/stft_kernels.hip), so equal calls give equal bits, and a stream's result does not depend on the
+ * batch it is in.  Same argument checks as ntm_stft_sums; B == 0 returns NTM_OK without looking at the pointers.
+ */
+int64_t ntm_stft_grad_workspace_floats(int64_t B, int64_t T, int64_t skip, int n_fft, int hop);
+int ntm_stft_grad(const float *y, const float *t, int64_t B, int64_t T, int64_t skip, int n_fft, int hop, int win_length,
+                  float power_eps, const float *coef, float *ws, float *dy, int accumulate, void *stream);
+
+/*
  * "Next" row N2 plumbing: pitched asynchronous copy between (pinned) host memory and the device, rows x
  * width_bytes with independent pitches -- what the segment feeder uses to send a TIME CHUNK of many segments
  * ([B, c0:c1] of a [B,T] batch) so that the copy of chunk c+1 overlaps the GRU launch on chunk c.

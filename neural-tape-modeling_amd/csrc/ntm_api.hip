@@ -23,6 +23,8 @@ hipError_t launch_esr_dcpre(const float *y, const float *t, int64_t B, int64_t T
 hipError_t launch_stft_sums(const float *y, const float *t, int64_t B, int64_t T, int64_t skip, int n_fft, int hop,
                             int win, float eps, int chunks, int mode, double *out, hipStream_t stream, int n_mels = 0,
                             const int *mel_first = nullptr, const int *mel_start = nullptr, const float *mel_w = nullptr);
+hipError_t launch_stft_grad(const float *y, const float *t, int64_t B, int64_t T, int64_t skip, int n_fft, int hop, int win,
+                            float eps, const float *coef, float *ws, float *dy, int accumulate, hipStream_t stream);
 hipError_t launch_demodulate(const float *x, float *out, int C, int64_t N, const int64_t *y_idx, int P, int64_t period,
                              int64_t shift, double *scratch, hipStream_t stream);
 hipError_t launch_tape_record_field(const double *I, const double *bias, double *H, int64_t B, int64_t N, double gain,
@@ -417,6 +419,42 @@ int ntm_mel_sums(const float *y, const float *t, int64_t B, int64_t T, int64_t s
     if (B > 0 && (!mel_first || !mel_start || !mel_w)) return fail(NTM_EINVAL, "ntm_mel_sums: null filter-bank pointer");
     return stft_common("ntm_mel_sums", y, t, B, T, skip, n_fft, hop, win_length, log_floor, chunks, 2, out, stream, n_mels,
                        mel_first, mel_start, mel_w);
+}
+
+// the argument checks of stft_common on the sizes of the adjoint (no chunk count: the launcher chooses the split)
+static int stft_grad_sizes(const std::string &w, int64_t B, int64_t T, int64_t skip, int n_fft, int hop)
+{
+    if (B < 0 || T < 0 || skip < 0 || skip > T) return fail(NTM_EINVAL, w + ": bad size");
+    if (n_fft != 64 && n_fft != 128 && n_fft != 256 && n_fft != 512 && n_fft != 1024 && n_fft != 2048)
+        return fail(NTM_EINVAL, w + ": n_fft must be a power of two from 64 to 2048");
+    if (hop <= 0) return fail(NTM_EINVAL, w + ": bad hop or win_length");
+    if (B == 0) return NTM_OK;
+    if (T - skip <= n_fft / 2) return fail(NTM_EINVAL, w + ": reflect padding needs T - skip > n_fft/2");
+    if (T - skip > 0x7fffffff - 4096) return fail(NTM_EINVAL, w + ": T - skip must be below 2^31 - 4096");
+    // one frame-kernel workgroup per (stream, chunk), at most one chunk per frame; one gather thread per sample
+    if (B * (1 + (T - skip) / hop) > 0x7fffffff || B * T > (int64_t)0x7fffffff * 256)
+        return fail(NTM_EINVAL, w + ": B * frames and B * T / 256 must be below 2^31");
+    return NTM_OK;
+}
+
+int64_t ntm_stft_grad_workspace_floats(int64_t B, int64_t T, int64_t skip, int n_fft, int hop)
+{
+    if (stft_grad_sizes("ntm_stft_grad_workspace_floats", B, T, skip, n_fft, hop) != NTM_OK) return -1;
+    return B * (1 + (T - skip) / hop) * n_fft;
+}
+
+int ntm_stft_grad(const float *y, const float *t, int64_t B, int64_t T, int64_t skip, int n_fft, int hop, int win_length,
+                  float power_eps, const float *coef, float *ws, float *dy, int accumulate, void *stream)
+{
+    const std::string w("ntm_stft_grad");
+    if (int rc = stft_grad_sizes(w, B, T, skip, n_fft, hop)) return rc;
+    if (win_length <= 0 || win_length > n_fft) return fail(NTM_EINVAL, w + ": bad hop or win_length");
+    if (!(power_eps > 0.0f)) return fail(NTM_EINVAL, w + ": the power floor must be positive");
+    if (B == 0) return NTM_OK;
+    if (!y || !t || !coef || !ws || !dy) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_stft_grad(y, t, B, T, skip, n_fft, hop, win_length, power_eps, coef, ws, dy, accumulate,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_stft_grad");
 }
 
 int ntm_copy2d_async(void *dst, int64_t dst_pitch_bytes, const void *src, int64_t src_pitch_bytes, int64_t width_bytes,

@@ -439,4 +439,230 @@ hipError_t launch_stft_sums(const float *y, const float *t, int64_t B, int64_t T
     }
 }
 
+// ---- adjoint of the mode 0 sums (ntm_stft_grad): d/dy of
+//   sum_cells ( 1/2 c_sc (my - mt)^2 + c_log |ln my - ln mt| + c_lin |my - mt| ),   (c_sc, c_log, c_lin) = coef[stream],
+// in two kernels.
+//
+// stft_grad_frames_kernel -- the mapping of stft_sums_kernel (a frame pair per wave, 64/SUB pairs for n_fft 64 / 128): the
+// pair goes through the same transform; per bin k = 0 .. N/2
+//   G = c_sc (my - mt) + sgn(my - mt) (c_log / my + c_lin)        (sgn(0) = 0: torch's abs backward; ln is monotonic)
+//   c_k = G Y_k / my   where the unclamped power is above the floor, else 0 (the clamp has zero derivative),
+// and the frame gradient g[n] = w[n] Re sum_{k=0}^{N/2} c_k e^{+2 pi i k n / N} = w[n] Re FFT(conj c)[n] -- every bin of
+// 0 .. N/2 once, no 1/N, no doubling: the adjoint of the one-sided transform -- comes out of the SAME forward passes run
+// on conj c (bins above N/2 zero).  A lane's bins k = sl + SUB i, i < P/2, are its points q < P/2 of that second
+// transform, so c never touches memory.  The spectra in the exchange buffer are 2 Y and 2 T (split_spectra): with
+// my2 = 2 my,  c_k = G Y2_k / my2,  G = c_sc/2 (my2 - mt2) + sgn (2 c_log / my2 + c_lin), floor 4 eps on the powers.
+// The windowed frame gradients go to the workspace ws[stream][frame][n] (fp32); an idle frame slot of a multi-frame wave
+// transforms a reloaded frame like the forward and stores nothing.
+//
+// stft_grad_gather_kernel -- the overlap-add back through the reflection as a gather, one thread per output sample, no
+// atomics.  ORDER OF ADDITION for sample i of [0, L), L = T - skip, in fp32 from 0:
+//   1. the direct position p = i:                        frames f ascending,  + ws[f][p + N/2 - f hop]
+//   2. the left mirror p = -i        (1 <= i <= N/2):    frames ascending
+//   3. the right mirror p = 2(L-1)-i (i < L-1, p < L + N/2): frames ascending
+// (a frame holds p when 0 <= p + N/2 - f hop < N).  With accumulate the sum is then added to dy[i]: dy[i] = dy[i] + sum.
+// Samples before `skip` get 0 (accumulate: stay as they are).
+struct StftGradArgs {
+    const float *y, *t, *coef;
+    float *ws;
+    int64_t B, T, skip;
+    int hop, win, chunks, frames_per_chunk, n_frames;
+    float eps;
+};
+
+// Periodic Hann value 0.5 - 0.5 cos(2 pi n / win) = sin^2(pi n / win), 0 <= n < win, correctly rounded to fp32: the gradient of
+// the log-magnitude term goes with 1/mag^2 at small-magnitude cells, where every absolute error of the spectrum counts, and
+// the fp32 argument 2n/win of stft_sums_kernel's window (exact for a power-of-two win only) costs 2e-7 of the window's peak --
+// twice the roundoff of the transform itself.  sin by symmetry on [0, pi/4] (m = min(n, win - n); beyond win/4 the cosine of
+// the complement), Taylor series in fp64 (truncation below 1e-12); step = pi / (2 win).
+__device__ __forceinline__ float hann_rounded(int n, int win, double step)
+{
+    const int m = min(n, win - n);
+    const bool upper = 4 * m > win;
+    const double y = step * (double)(upper ? win - 2 * m : 2 * m), y2 = y * y;
+    const double sn = y * (1.0 + y2 * (-1.0 / 6 + y2 * (1.0 / 120 + y2 * (-1.0 / 5040 + y2 * (1.0 / 362880 + y2 * (-1.0 / 39916800
+                      + y2 * (1.0 / 6227020800.0)))))));
+    const double cs = 1.0 + y2 * (-0.5 + y2 * (1.0 / 24 + y2 * (-1.0 / 720 + y2 * (1.0 / 40320 + y2 * (-1.0 / 3628800
+                      + y2 * (1.0 / 479001600 + y2 * (-1.0 / 87178291200.0)))))));
+    const double s = upper ? cs : sn;
+    return (float)(s * s);
+}
+
+template <int LOG2N>
+__global__ __launch_bounds__(256, (LOG2N <= 10 ? 2 : 1)) void stft_grad_frames_kernel(StftGradArgs a)
+{
+    constexpr int N = 1 << LOG2N;
+    using G = Geo<N>;
+    constexpr int SUB = G::SUB, P = G::P, FPW = G::FPW, NPAD = G::NPAD;
+    using PL = Plan<LOG2N>;
+    constexpr int R0 = PL::R0, R1 = PL::R1, R2 = PL::R2, R3 = PL::R3;
+    static_assert(R0 * R1 * R2 * R3 == N, "radix plan");
+    extern __shared__ f2 stft_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sl = lane & (SUB - 1), fs = lane / SUB;
+    f2 *buf = stft_smem + (wave * FPW + fs) * NPAD;
+
+    PassTw<N, R1, R0> tw1;
+    PassTw<N, R2, R0 * R1> tw2;
+    PassTw<N, (R3 > 1 ? R3 : 2), R0 * R1 * R2 / (R3 > 1 ? 1 : 2)> tw3;      // (unused when R3 == 1)
+    tw1.init(sl);
+    tw2.init(sl);
+    if constexpr (R3 > 1) tw3.init(sl);
+
+    const int left = (N - a.win) / 2;
+    const double hann_step = 1.5707963267948966 / (double)a.win;
+    float wreg[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        const int n = sl + SUB * q - left;
+        wreg[q] = (n >= 0 && n < a.win) ? hann_rounded(n, a.win, hann_step) : 0.0f;
+    }
+
+    const int64_t stream = blockIdx.x / a.chunks;
+    const int chunk = blockIdx.x % a.chunks;
+    const int L = (int)(a.T - a.skip);
+    const float *ys = a.y + stream * a.T + a.skip;
+    const float *ts = a.t + stream * a.T + a.skip;
+    float *wss = a.ws + (size_t)stream * a.n_frames * N;
+    const int f_begin = chunk * a.frames_per_chunk;
+    const int f_end = min(f_begin + a.frames_per_chunk, a.n_frames);
+    constexpr int FSTEP = 4 * FPW;
+
+    const float csc_half = 0.5f * a.coef[stream * 3], clog2 = 2.0f * a.coef[stream * 3 + 1], clin = a.coef[stream * 3 + 2];
+    const float eps4 = 4.0f * a.eps;                           // floor of the unscaled (4 x) powers, see split_spectra
+    float ry[P], rt[P];
+    auto fetch = [&](int f) {
+        if (f >= f_end) f = f_begin;                        // idle slot of a multi-frame wave: reload, nothing is stored for it
+        const int start = f * a.hop - N / 2;
+        if (FPW == 1 && start >= 0 && start + N <= L) {
+            const float *py = ys + start + sl, *pt = ts + start + sl;
+#pragma unroll
+            for (int q = 0; q < P; ++q) { ry[q] = py[SUB * q]; rt[q] = pt[SUB * q]; }
+        } else {
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                int i = start + sl + SUB * q;
+                i = i < 0 ? -i : i;
+                i = i >= L ? 2 * (L - 1) - i : i;
+                ry[q] = ys[i]; rt[q] = ts[i];
+            }
+        }
+    };
+    const int f_first = f_begin + wave * FPW;
+    if (f_first < f_end) fetch(f_first + fs);
+    for (int f0 = f_first; f0 < f_end; f0 += FSTEP) {
+        const int f = f0 + fs;
+        const bool live = f < f_end;
+        f2 v[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) v[q] = (f2){wreg[q] * ry[q], wreg[q] * rt[q]};
+        PassTw<N, R0, 1> tw0;
+        stockham_pass<N, R0, 1, true>(v, buf, tw0, sl);
+        stockham_pass<N, R1, R0, false>(v, buf, tw1, sl);
+        if (f0 + FSTEP < f_end) fetch(f + FSTEP);              // (placed as in stft_sums_kernel)
+        stockham_pass<N, R2, R0 * R1, false>(v, buf, tw2, sl);
+        if constexpr (R3 > 1) stockham_pass<N, R3, R0 * R1 * R2, false>(v, buf, tw3, sl);
+        wave_lds_fence();
+        // ---- conj c_k of this lane's bins: its points q < P/2 of the second transform (bin N/2: point P/2 of lane 0) ----
+        auto cbin = [&](int k) -> f2 {
+            const f2 zk = buf[padi(k)], zn = buf[padi((N - k) & (N - 1))];
+            f2 Y2, T2;
+            split_spectra(zk, zn, Y2, T2);
+            const f2 ysq = Y2 * Y2, tsq = T2 * T2;
+            const float py0 = ysq.x + ysq.y, pt0 = tsq.x + tsq.y;                 // 4 x the powers
+            const float my2 = __builtin_amdgcn_sqrtf(fmaxf(py0, eps4)), mt2 = __builtin_amdgcn_sqrtf(fmaxf(pt0, eps4));
+            const float d = my2 - mt2;
+            const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+            const float inv = 1.0f / my2;
+            const float g = csc_half * d + sg * (clog2 * inv + clin);
+            const float s = py0 > eps4 ? g * inv : 0.0f;
+            return (f2){s * Y2.x, -(s * Y2.y)};
+        };
+#pragma unroll
+        for (int q = 0; q < P / 2; ++q) v[q] = cbin(sl + SUB * q);
+        v[P / 2] = (f2){0.0f, 0.0f};
+        if (sl == 0) v[P / 2] = cbin(N / 2);
+#pragma unroll
+        for (int q = P / 2 + 1; q < P; ++q) v[q] = (f2){0.0f, 0.0f};
+        wave_lds_fence();                                      // every lane has read its bins: the buffer is free
+        stockham_pass<N, R0, 1, true>(v, buf, tw0, sl);
+        stockham_pass<N, R1, R0, false>(v, buf, tw1, sl);
+        stockham_pass<N, R2, R0 * R1, false>(v, buf, tw2, sl);
+        if constexpr (R3 > 1) stockham_pass<N, R3, R0 * R1 * R2, false>(v, buf, tw3, sl);
+        wave_lds_fence();
+        if (live) {
+            float *o = wss + (size_t)f * N + sl;
+#pragma unroll
+            for (int q = 0; q < P; ++q) o[SUB * q] = wreg[q] * buf[padi(sl + SUB * q)].x;
+        }
+        wave_lds_fence();
+    }
+}
+
+__global__ __launch_bounds__(256) void stft_grad_gather_kernel(const float *ws, float *dy, int64_t B, int64_t T, int64_t skip,
+                                                               int N, int hop, int n_frames, int accumulate)
+{
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= B * T) return;
+    const int64_t b = idx / T, j = idx - b * T;
+    if (j < skip) {
+        if (!accumulate) dy[idx] = 0.0f;
+        return;
+    }
+    const int64_t i = j - skip, L = T - skip;
+    const float *w = ws + (size_t)b * n_frames * N;
+    float s = 0.0f;
+    auto add = [&](int64_t p) {                     // every frame that holds padded position p, ascending
+        const int64_t q = p + N / 2;                // position in the padded signal, >= 0
+        const int64_t f_lo = q >= N ? (q - N) / hop + 1 : 0;
+        const int64_t f_hi = min(q / hop, (int64_t)n_frames - 1);
+        for (int64_t f = f_lo; f <= f_hi; ++f) s += w[f * N + (q - f * hop)];
+    };
+    add(i);
+    if (i >= 1 && i <= N / 2) add(-i);
+    const int64_t pr = 2 * (L - 1) - i;
+    if (i < L - 1 && pr < L + N / 2) add(pr);
+    dy[idx] = accumulate ? dy[idx] + s : s;
+}
+
+template <int LOG2N>
+static hipError_t launch_grad_frames(StftGradArgs &a, hipStream_t stream)
+{
+    constexpr int N = 1 << LOG2N, FSTEP = 4 * Geo<N>::FPW;
+    // whole iterations of a workgroup per chunk, about 1024 workgroups; every frame is written once by one wave, so the
+    // result does not depend on the split
+    const int iters = (a.n_frames + FSTEP - 1) / FSTEP;
+    const int want = (int)min((int64_t)iters, max((int64_t)1, (1024 + a.B - 1) / a.B));
+    a.frames_per_chunk = (iters + want - 1) / want * FSTEP;
+    a.chunks = (a.n_frames + a.frames_per_chunk - 1) / a.frames_per_chunk;
+    const size_t smem = (size_t)4 * Geo<N>::FPW * Geo<N>::NPAD * sizeof(f2);
+    auto k = stft_grad_frames_kernel<LOG2N>;
+    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * a.chunks)), dim3(256), smem, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_stft_grad(const float *y, const float *t, int64_t B, int64_t T, int64_t skip, int n_fft, int hop, int win,
+                            float eps, const float *coef, float *ws, float *dy, int accumulate, hipStream_t stream)
+{
+    StftGradArgs a;
+    a.y = y; a.t = t; a.coef = coef; a.ws = ws; a.B = B; a.T = T; a.skip = skip; a.hop = hop; a.win = win; a.eps = eps;
+    a.n_frames = (int)(1 + (T - skip) / hop);
+    hipError_t e;
+    switch (n_fft) {
+    case 64: e = launch_grad_frames<6>(a, stream); break;
+    case 128: e = launch_grad_frames<7>(a, stream); break;
+    case 256: e = launch_grad_frames<8>(a, stream); break;
+    case 512: e = launch_grad_frames<9>(a, stream); break;
+    case 1024: e = launch_grad_frames<10>(a, stream); break;
+    case 2048: e = launch_grad_frames<11>(a, stream); break;
+    default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(stft_grad_gather_kernel, dim3((unsigned)((B * T + 255) / 256)), dim3(256), 0, stream, ws, dy, B, T, skip,
+                       n_fft, hop, a.n_frames, accumulate);
+    return hipGetLastError();
+}
+
 }   // namespace ntm

@@ -1527,21 +1527,40 @@ class MRSTFTLoss(torch.nn.Module):
         self.resolutions = list(zip(fft_sizes, hop_sizes, win_lengths))
         self.w_sc, self.w_log_mag, self.w_lin_mag, self.eps = w_sc, w_log_mag, w_lin_mag, eps
 
-    def _terms(self, output, target, skip, whole_batch):
+    @torch.no_grad()
+    def _terms(self, output, target, skip, whole_batch, sums=None):
+        """The loss value(s); `sums`, a list, receives the per-stream (B,4) fp64 sums of every resolution (what the adjoint needs)."""
         total = 0.0
         for n_fft, hop, win in self.resolutions:
             s, cells = stft_sums(output, target, skip, n_fft, hop, win, self.eps)
+            if sums is not None:
+                sums.append(s)
             if whole_batch:
                 cells, s = cells * s.shape[0], s.sum(dim=0)
             total = total + (self.w_sc * torch.sqrt(s[..., 0]) / torch.sqrt(s[..., 1])
                              + self.w_log_mag * s[..., 2] / cells + self.w_lin_mag * s[..., 3] / cells)
         return total / len(self.resolutions)
 
+    def _value(self, output, target, skip, whole_batch, sums=None):
+        v = self._terms(output, target, skip, whole_batch, sums)
+        return v.float() if whole_batch else v
+
+    def _loss(self, output, target, skip, whole_batch):
+        if output.requires_grad and torch.is_grad_enabled():
+            return training.mrstft_with_grad(self, output, target, int(skip), whole_batch)
+        return self._value(output, target, skip, whole_batch)
+
     def per_segment(self, output, target, skip=0):
-        return self._terms(output, target, skip, False)
+        """[B] fp64 losses, one per stream.  With an output that requires grad a node of the graph (adjoint: ntm_stft_grad with
+        each stream's own sums), same values."""
+        return self._loss(output, target, skip, False)
 
     def forward(self, output, target):
-        return self._terms(output, target, 0, True).float()
+        """With an output that requires grad (RNN.train_epoch / DiffDelRNN.train_epoch) the same value as a differentiable scalar:
+        the adjoint runs ntm_stft_grad once per resolution, in constructor order, each after the first adding to dy.  A window
+        must be longer than half the largest frame (reflect padding, as torch.stft): the default 2048-point resolution needs
+        more than 1024 samples."""
+        return self._loss(output, target, 0, True)
 
 
 SPEC_SCALES = (2048, 1024, 512, 256, 128, 64)     # code/evaluation.py:23

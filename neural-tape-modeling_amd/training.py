@@ -12,6 +12,8 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
     backward = ntm_delay_backward, the deterministic adjoint (gradients for pre and, where it is in the graph, the old buffer).
   * loss_with_grad: the ESR / DCPreESR loss value exactly as the no-grad path computes it, and its adjoint on the device
     (ntm_esr_grad / ntm_esr_dcpre_grad).
+  * mrstft_with_grad: the MRSTFTLoss value(s) exactly as the no-grad path computes them, and the adjoint of the STFT sums on the
+    device (ntm_stft_grad, one call per resolution).
   * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
     replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
     launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
@@ -154,3 +156,53 @@ def loss_with_grad(output, target, value, pole, R=None):
     if target.requires_grad:
         raise RuntimeError("ESRLoss / DCPreESR: gradients flow to the prediction only; the target must not require grad")
     return _LossFn.apply(output, target, value, pole, R)
+
+
+class _MRSTFTLossFn(torch.autograd.Function):
+    """MRSTFTLoss.forward (whole_batch: one float32 scalar from the batch totals) / per_segment ([B] float64) as a graph node.  The
+    value is model.MRSTFTLoss._value's, computed under no_grad; the per-stream sums (B,4) fp64 of every resolution are saved."""
+
+    @staticmethod
+    def forward(ctx, output, target, loss, skip, whole_batch):
+        sums = []
+        value = loss._value(output, target, skip, whole_batch, sums)
+        ctx.save_for_backward(output, target, *sums)
+        ctx.loss, ctx.skip, ctx.whole_batch = loss, skip, whole_batch
+        return value
+
+    @staticmethod
+    def backward(ctx, gout):
+        from .model import _as_bt, _n_frames
+        output, target, *sums = ctx.saved_tensors
+        loss, skip = ctx.loss, ctx.skip
+        y = _as_bt(output, "MRSTFTLoss backward")
+        t = _as_bt(target, "MRSTFTLoss backward")
+        B, T = y.shape
+        nres = len(loss.resolutions)
+        # coefficient rows (c_sc, c_log, c_lin) per stream in float64 on the device (no host synchronisation), rounded once
+        g = gout.detach().to(device=y.device, dtype=torch.float64).reshape(1 if ctx.whole_batch else B)
+        dy = torch.empty(B, T, device=y.device, dtype=torch.float32)
+        L, st = _lib.lib(), _lib.current_stream()
+        # resolutions in constructor order: the first call stores dy, every later one adds to it (dy = dy + gradient)
+        for r, ((n_fft, hop, win), s) in enumerate(zip(loss.resolutions, sums)):
+            cells = _n_frames(T, skip, hop, "MRSTFTLoss backward") * (int(n_fft) // 2 + 1)
+            if ctx.whole_batch:
+                cells, s = cells * B, s.sum(dim=0, keepdim=True)
+            den = torch.sqrt(s[:, 0]) * torch.sqrt(s[:, 1])
+            zero = s[:, 0] == 0                                     # torch.norm's subgradient at 0
+            c_sc = torch.where(zero, torch.zeros_like(den), g * loss.w_sc / (nres * torch.where(zero, torch.ones_like(den), den)))
+            c_log = g * (loss.w_log_mag / (nres * cells))
+            c_lin = g * (loss.w_lin_mag / (nres * cells))
+            coef = torch.stack([c_sc, c_log, c_lin], dim=1).to(torch.float32).expand(B, 3).contiguous()
+            ws = torch.empty(max(int(L.ntm_stft_grad_workspace_floats(B, T, skip, int(n_fft), int(hop))), 1), device=y.device,
+                             dtype=torch.float32)
+            _lib.check(L.ntm_stft_grad(ptr(y), ptr(t), B, T, skip, int(n_fft), int(hop), int(win), float(loss.eps), ptr(coef),
+                                       ptr(ws), ptr(dy), int(r > 0), st), "ntm_stft_grad")
+        return dy.view(output.shape).to(output.dtype), None, None, None, None
+
+
+def mrstft_with_grad(loss, output, target, skip, whole_batch):
+    """The MRSTFTLoss node: value(s) of the no-grad path bit for bit; gradients flow to the prediction only."""
+    if target.requires_grad:
+        raise RuntimeError("MRSTFTLoss: gradients flow to the prediction only; the target must not require grad")
+    return _MRSTFTLossFn.apply(output, target, loss, skip, whole_batch)

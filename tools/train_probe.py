@@ -14,7 +14,13 @@ With --validate --replicas R[,R...]: one validation batch of the reference's sha
 samples) through Replicas.validate (one launch of the low-latency kernel for all R models) beside R sequential single-model
 validate() calls on the same data, host time from call to return (validate ends with the losses on the host); the forms alternate
 within a repetition, median and range over --reps repetitions.  --model diffdel: D = 11 001, warm-up 16 384.
-usage: python tools/train_probe.py [--model gru|diffdel] [--iters N] [--rocprof] [--replicas 1,2,4,8 [--reps N] [--validate]]"""
+With --loss esr|dcpre|mrstft (default esr) the single-model windows (plain and --model diffdel) use that loss; mrstft is
+MRSTFTLoss() at its default resolutions on the 2048-sample windows of --model diffdel and without the 2048-point resolution on
+the GRU's 1024-sample windows (reflect padding needs T > n_fft/2).  With mrstft the probe also lists, per resolution, the time of
+ntm_stft_sums and of its adjoint ntm_stft_grad (frame kernel + gather) on a window's shape, and --rocprof shows both adjoint
+kernels in the per-kernel split.
+usage: python tools/train_probe.py [--model gru|diffdel] [--loss esr|dcpre|mrstft] [--iters N] [--rocprof]
+                                   [--replicas 1,2,4,8 [--reps N] [--validate]]"""
 import argparse
 import glob
 import json
@@ -42,7 +48,35 @@ def _time(fn, iters):
     return a.elapsed_time(b) / iters
 
 
-def engine(B, iters):
+def _loss_fcn(name, T):
+    import ntm_amd
+    if name == "mrstft":
+        keep = [i for i, n in enumerate(ntm_amd.model.MRSTFT_FFT_SIZES) if T > n // 2]
+        return ntm_amd.MRSTFTLoss(*([v[i] for i in keep] for v in (ntm_amd.model.MRSTFT_FFT_SIZES, ntm_amd.model.MRSTFT_HOP_SIZES,
+                                                                   ntm_amd.model.MRSTFT_WIN_LENGTHS)))
+    return ntm_amd.ESRLoss() if name == "esr" else ntm_amd.DCPreESR(dc_pre=True)
+
+
+def stft_split(B, T, iters):
+    """-> {n_fft: [ms of ntm_stft_sums, ms of ntm_stft_grad]} for the resolutions of MRSTFTLoss that fit T, by events."""
+    import torch
+    import ntm_amd
+    lib, p = ntm_amd._lib.lib(), ntm_amd._lib.ptr
+    y, t = torch.rand(B, 1, T, device="cuda") - 0.5, torch.rand(B, 1, T, device="cuda") - 0.5
+    coef = torch.rand(B, 3, device="cuda")
+    dy = torch.empty(B, T, device="cuda")
+    out = {}
+    for n_fft, hop, win in _loss_fcn("mrstft", T).resolutions:
+        ws = torch.empty(lib.ntm_stft_grad_workspace_floats(B, T, 0, n_fft, hop), device="cuda")
+
+        def grad():
+            ntm_amd._lib.check(lib.ntm_stft_grad(p(y), p(t), B, T, 0, n_fft, hop, win, ntm_amd.model.STFT_EPS, p(coef), p(ws), p(dy), 0,
+                                                 ntm_amd._lib.current_stream()), "ntm_stft_grad")
+        out[str(n_fft)] = [_time(lambda: ntm_amd.stft_sums(y, t, 0, n_fft, hop, win), iters), _time(grad, iters)]
+    return out
+
+
+def engine(B, iters, loss="esr"):
     import torch
     import ntm_amd
     torch.manual_seed(0)
@@ -50,7 +84,7 @@ def engine(B, iters):
     for p in m.parameters():
         p.requires_grad_(True)
     opt = torch.optim.Adam(m.parameters(), 1e-3)
-    loss_fcn = ntm_amd.ESRLoss()
+    loss_fcn = _loss_fcn(loss, L)
     x = torch.rand(B, 1, L, device="cuda") - 0.5
     t = 0.5 * x
     m.hidden = torch.zeros(1, B, 64, device="cuda")
@@ -68,7 +102,7 @@ def engine(B, iters):
 DD_L, DD_D, DD_INIT = 2048, 11001, 16384
 
 
-def engine_diffdel(B, iters):
+def engine_diffdel(B, iters, loss="esr"):
     """-> (ms per window, ms per warm-up + first window, ms of the delay adjoint alone per window)."""
     import torch
     import ntm_amd
@@ -77,7 +111,7 @@ def engine_diffdel(B, iters):
     for p in m.parameters():
         p.requires_grad_(True)
     opt = torch.optim.Adam(m.parameters(), 1e-3)
-    loss_fcn = ntm_amd.ESRLoss()
+    loss_fcn = _loss_fcn(loss, DD_L)
     n = torch.arange(DD_INIT + DD_L, device="cuda", dtype=torch.float32)
     d = (5500.0 + 4000.0 * torch.sin(n / 7000.0) + 20.0 * torch.sin(n / 300.0)).expand(B, 1, -1).contiguous()
     x = torch.rand(B, 1, DD_INIT + DD_L, device="cuda") - 0.5
@@ -281,7 +315,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rocprof", action="store_true")
-    ap.add_argument("--child", choices=["engine", "miopen", "native", "diffdel", "replicas", "validate"])
+    ap.add_argument("--child", choices=["engine", "miopen", "native", "diffdel", "replicas", "validate", "stft"])
+    ap.add_argument("--loss", choices=["esr", "dcpre", "mrstft"], default="esr", help="loss of the single-model windows")
     ap.add_argument("--replicas", default=None, help="comma-separated replica counts, e.g. 1,2,4,8")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="32,4096")
@@ -290,7 +325,10 @@ def main():
     a = ap.parse_args()
     sizes = [int(b) for b in a.sizes.split(",")]
     if a.child == "diffdel":
-        print(json.dumps({str(B): engine_diffdel(B, a.iters) for B in sizes}))
+        print(json.dumps({str(B): engine_diffdel(B, a.iters, a.loss) for B in sizes}))
+        return
+    if a.child == "stft":
+        print(json.dumps({str(B): stft_split(B, DD_L if a.model == "diffdel" else L, a.iters) for B in sizes}))
         return
     if a.child == "validate":
         print(json.dumps({str(R): validate_probe(R, a.reps, a.model) for R in map(int, a.replicas.split(","))}))
@@ -302,7 +340,7 @@ def main():
         out = {}
         for B in sizes:
             if a.child == "engine":
-                out[str(B)] = engine(B, a.iters)
+                out[str(B)] = engine(B, a.iters, a.loss)
                 continue
             # a torch-side RuntimeError (e.g. a MIOpen status) is reported as data: the child still exits normally, so that the
             # parent can tell it from a crash
@@ -356,33 +394,48 @@ def main():
                 _rocprof(child, a, [R], "replicas", ["--replicas", R, "--reps", "1", "--model", a.model])
         return
 
+    def stft_rows():
+        if a.loss != "mrstft":
+            return
+        r = child([sys.executable, __file__, "--child", "stft", "--iters", str(a.iters), "--sizes", a.sizes, "--model", a.model], "stft child")
+        print(f"\nper resolution on a window's shape, ms: {'B':>6} {'n_fft':>6} {'ntm_stft_sums':>14} {'ntm_stft_grad':>14}")
+        for B, rows in json.loads(r.stdout.strip().splitlines()[-1]).items():
+            for n_fft, (fwd, adj) in rows.items():
+                print(f"{'':<39} {B:>6} {n_fft:>6} {fwd:14.4f} {adj:14.4f}")
+
+    extra = ["--loss", a.loss]
     if a.model == "diffdel":
-        r = child([sys.executable, __file__, "--child", "diffdel", "--iters", str(a.iters), "--sizes", a.sizes], "diffdel child")
+        r = child([sys.executable, __file__, "--child", "diffdel", "--iters", str(a.iters), "--sizes", a.sizes] + extra, "diffdel child")
         res = json.loads(r.stdout.strip().splitlines()[-1])
-        print(f"DiffDelGRU-HS[64], ms (L = {DD_L}, D = {DD_D}; window = forward + ESR loss + backward + Adam):")
+        print(f"DiffDelGRU-HS[64], ms (L = {DD_L}, D = {DD_D}; window = forward + {a.loss} loss + backward + Adam):")
         print(f"{'B':>6} {'window':>9} {'warm-up + window 1':>19} {'delay adjoint':>14} {'adjoint share':>14}")
         for B in map(str, sizes):
             w, f, adj = res[B]
             print(f"{B:>6} {w:9.3f} {f:19.3f} {adj:14.4f} {adj / w * 100:13.2f}%")
+        stft_rows()
         if a.rocprof:
-            _rocprof(child, a, sizes, "diffdel")
+            _rocprof(child, a, sizes, "diffdel", extra)
         return
 
     rows = {}
     for kind in ("engine", "miopen", "native"):
-        r = child([sys.executable, __file__, "--child", kind, "--iters", str(a.iters), "--sizes", a.sizes], f"{kind} child")
+        if kind != "engine" and a.loss != "esr":
+            rows[kind] = {str(B): None for B in sizes}           # the torch baselines are written for the ESR loss only
+            continue
+        r = child([sys.executable, __file__, "--child", kind, "--iters", str(a.iters), "--sizes", a.sizes] + extra, f"{kind} child")
         rows[kind] = json.loads(r.stdout.strip().splitlines()[-1])
     fmt = lambda v: f"{v:.3f}" if isinstance(v, float) else "n/a"      # noqa: E731
-    print("ms per TBPTT window (L = 1024; forward + ESR loss + backward + Adam):")
+    print(f"ms per TBPTT window (L = 1024; forward + {a.loss} loss + backward + Adam):")
     print(f"{'B':>6} {'this engine':>12} {'MIOpen':>10} {'torch native':>13}")
     for B in map(str, sizes):
         print(f"{B:>6} {fmt(rows['engine'][B]):>12} {fmt(rows['miopen'][B]):>10} {fmt(rows['native'][B]):>13}")
     for kind in ("miopen", "native"):
         for B in map(str, sizes):
-            if not isinstance(rows[kind][B], float):
+            if isinstance(rows[kind][B], str):
                 print(f"  {kind} B={B}: {rows[kind][B]}")
+    stft_rows()
     if a.rocprof:
-        _rocprof(child, a, sizes, "engine")
+        _rocprof(child, a, sizes, "engine", extra)
 
 
 def _rocprof(child, a, sizes, kind, extra=()):
