@@ -293,6 +293,35 @@ int ntm_stft_grad(const float *y, const float *t, int64_t B, int64_t T, int64_t 
                   float power_eps, const float *coef, float *ws, float *dy, int accumulate, void *stream);
 
 /*
+ * The power spectrogram ITSELF, for a caller that reads its cells: the front end of the reference's spectral critics
+ * (`TimeFreqConverter`, code/utilities/utilities.py:627-672 = torchaudio Spectrogram(power = 2) = |torch.stft|^2).
+ *   P[b][k][f] = |stft(y_b, n_fft, hop, win_length, periodic Hann, centred, reflect padding)[k, f]|^2
+ * y [B,T] fp32 contiguous; P [B][n_fft/2 + 1][1 + T/hop] fp32 contiguous (torch's layout: bins, then frames).  Frames,
+ * padding and window placement are those of ntm_stft_sums without `skip`.  Window, transform and powers are computed in
+ * fp64 and each cell is rounded to fp32 once (a network behind P divides by it: DESIGN.md 11.5).  Two frames (2j, 2j + 1) of a stream share one complex transform; a last frame without a
+ * partner is paired with itself.  Every cell is written once: equal calls give equal bits; a stream's result does not
+ * depend on its batch.  Argument checks as ntm_stft_sums (n_fft in {64, ..., 2048}; 0 < win_length <= n_fft; hop >= 1;
+ * T > n_fft/2; T < 2^31 - 4096, B * frames < 2^31), made before anything touches a device; P must not be y.  B == 0
+ * returns NTM_OK without looking at the pointers.
+ */
+int ntm_spectrogram(const float *y, int64_t B, int64_t T, int n_fft, int hop, int win_length, float *P, void *stream);
+
+/*
+ * Adjoint of ntm_spectrogram: with an upstream gradient gP in P's layout,
+ *   dy[b] = d/dy sum_{k,f} gP[b][k][f] P[b][k][f]
+ * -- per frame g_f[n] = w[n] Re sum_{k=0}^{n_fft/2} conj(c_k) e^{-2 pi i k n / n_fft}, c_k = 2 gP[b][k][f] Y_k (every bin once,
+ * no 1/N, no doubling), Y recomputed from y in fp64 (nothing is saved by the forward), each frame gradient rounded to fp32, then the overlap-add back through the
+ * reflect padding.  dy [B,T] fp32; accumulate != 0: dy[i] = dy[i] + gradient in place of the store.  ws:
+ * ntm_stft_grad_workspace_floats(B, T, 0, n_fft, hop) floats of device scratch (the windowed frame gradients,
+ * [B][frames][n_fft]).  No atomics: the overlap-add is ntm_stft_grad's gather with its fixed order of addition (direct
+ * position, left mirror, right mirror; frames ascending -- csrc/stft_kernels.hip), so equal calls give equal bits, and a
+ * stream's result does not depend on its batch.  Same argument checks as ntm_spectrogram; dy and ws must not be y, gP or
+ * each other.  B == 0 returns NTM_OK without looking at the pointers.
+ */
+int ntm_spectrogram_grad(const float *y, const float *gP, int64_t B, int64_t T, int n_fft, int hop, int win_length,
+                         float *ws, float *dy, int accumulate, void *stream);
+
+/*
  * "Next" row N2 plumbing: pitched asynchronous copy between (pinned) host memory and the device, rows x
  * width_bytes with independent pitches -- what the segment feeder uses to send a TIME CHUNK of many segments
  * ([B, c0:c1] of a [B,T] batch) so that the copy of chunk c+1 overlaps the GRU launch on chunk c.

@@ -74,6 +74,8 @@ _SIGNATURES = {
     "ntm_diffdel_stream_block": (_int, [_vp] * 9 + [_i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _int, _int, _vp, _vp]),
     # adjoint of the STFT sums (additions within ABI version 9)
     "ntm_stft_grad_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _int]),
+    "ntm_spectrogram": (_int, [_vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
+    "ntm_spectrogram_grad": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _int, _vp]),
     "ntm_stft_grad": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, ctypes.c_float, _vp, _vp, _vp, _int, _vp]),
 }
 TRAIN_GRAD_FLOATS = 12929   # include/ntm.h NTM_TRAIN_GRAD_FLOATS: w_ih | w_hh | b_ih | b_hh | w_o | b_o of GRU(1, 64) + Linear(64, 1)

@@ -25,6 +25,9 @@ hipError_t launch_stft_sums(const float *y, const float *t, int64_t B, int64_t T
                             const int *mel_first = nullptr, const int *mel_start = nullptr, const float *mel_w = nullptr);
 hipError_t launch_stft_grad(const float *y, const float *t, int64_t B, int64_t T, int64_t skip, int n_fft, int hop, int win,
                             float eps, const float *coef, float *ws, float *dy, int accumulate, hipStream_t stream);
+hipError_t launch_spectrogram(const float *y, int64_t B, int64_t T, int n_fft, int hop, int win, float *P, hipStream_t stream);
+hipError_t launch_spectrogram_grad(const float *y, const float *gP, int64_t B, int64_t T, int n_fft, int hop, int win, float *ws,
+                                   float *dy, int accumulate, hipStream_t stream);
 hipError_t launch_demodulate(const float *x, float *out, int C, int64_t N, const int64_t *y_idx, int P, int64_t period,
                              int64_t shift, double *scratch, hipStream_t stream);
 hipError_t launch_tape_record_field(const double *I, const double *bias, double *H, int64_t B, int64_t N, double gain,
@@ -455,6 +458,37 @@ int ntm_stft_grad(const float *y, const float *t, int64_t B, int64_t T, int64_t 
     hipError_t e = ntm::launch_stft_grad(y, t, B, T, skip, n_fft, hop, win_length, power_eps, coef, ws, dy, accumulate,
                                          (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_stft_grad");
+}
+
+// the argument checks ntm_spectrogram and ntm_spectrogram_grad share (those of ntm_stft_sums without skip, floor and chunks)
+static int spectrogram_sizes(const std::string &w, int64_t B, int64_t T, int n_fft, int hop, int win_length)
+{
+    if (int rc = stft_grad_sizes(w, B, T, 0, n_fft, hop)) return rc;
+    if (win_length <= 0 || win_length > n_fft) return fail(NTM_EINVAL, w + ": bad hop or win_length");
+    return NTM_OK;
+}
+
+int ntm_spectrogram(const float *y, int64_t B, int64_t T, int n_fft, int hop, int win_length, float *P, void *stream)
+{
+    const std::string w("ntm_spectrogram");
+    if (int rc = spectrogram_sizes(w, B, T, n_fft, hop, win_length)) return rc;
+    if (B == 0) return NTM_OK;
+    if (!y || !P) return fail(NTM_EINVAL, w + ": null pointer");
+    if (P == y) return fail(NTM_EINVAL, w + ": P must not alias y");
+    hipError_t e = ntm::launch_spectrogram(y, B, T, n_fft, hop, win_length, P, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_spectrogram");
+}
+
+int ntm_spectrogram_grad(const float *y, const float *gP, int64_t B, int64_t T, int n_fft, int hop, int win_length, float *ws,
+                         float *dy, int accumulate, void *stream)
+{
+    const std::string w("ntm_spectrogram_grad");
+    if (int rc = spectrogram_sizes(w, B, T, n_fft, hop, win_length)) return rc;
+    if (B == 0) return NTM_OK;
+    if (!y || !gP || !ws || !dy) return fail(NTM_EINVAL, w + ": null pointer");
+    if (dy == y || dy == gP || ws == y || ws == gP || ws == dy) return fail(NTM_EINVAL, w + ": dy and ws must not alias y, gP or each other");
+    hipError_t e = ntm::launch_spectrogram_grad(y, gP, B, T, n_fft, hop, win_length, ws, dy, accumulate, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_spectrogram_grad");
 }
 
 int ntm_copy2d_async(void *dst, int64_t dst_pitch_bytes, const void *src, int64_t src_pitch_bytes, int64_t width_bytes,

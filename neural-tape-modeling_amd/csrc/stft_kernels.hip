@@ -665,4 +665,277 @@ hipError_t launch_stft_grad(const float *y, const float *t, int64_t B, int64_t T
     return hipGetLastError();
 }
 
+// ---- the power spectrogram itself (ntm_spectrogram) and its adjoint (ntm_spectrogram_grad): the front end of the
+// reference's spectral critics (TimeFreqConverter, code/utilities/utilities.py:627-672), whose output a network reads and
+// whose input gets a gradient.
+//
+//   P[b][k][f] = |STFT(y_b)[k, f]|^2,   k = 0 .. N/2,  f = 0 .. T / hop       (frames, padding, window placement: stft_sums_kernel's)
+//   g_f[n] = w[n] Re sum_{k=0}^{N/2} conj(c_k) e^{-2 pi i k n / N},   c_k = 2 gP[b][k][f] Y_k
+//
+// ARITHMETIC: fp64 inside (window, twiddles, transform, powers, c), fp32 at the interfaces (y, P, gP, the workspace).  A
+// network behind P divides by it -- the critics take log10(P + 1e-5) -- so a cell of small power multiplies the ABSOLUTE error
+// of Y, which in an fp32 transform is the roundoff of the frame's largest bins, by up to 1/(P + 1e-5): the fp32 form of this
+// kernel (the packed-fp32 passes of stft_sums_kernel) was within a quarter of the bar on the spectrogram and on its adjoint and
+// 8 x above it on the gradient of such a head.  In fp64 the error of a cell is its own rounding to fp32.  The
+// vector unit runs fp64 at the rate of unpacked fp32, and the calls are short, so the passes are plain: Stockham autosort,
+// radix 4 (one radix-2 pass at the end for an odd log2 N), the lane / point / exchange-buffer mapping of stockham_pass
+// (v[q] = point sl + SUB q, one padded buffer per frame slot, wave-level fences), twiddles from one table
+// e^{-2 pi i j / N}, j < N, that the workgroup fills in LDS at its start (sincospi in fp64).
+//
+// Mapping: ONE signal, so a frame slot packs two FRAMES of the stream, z = w (y_f + i y_{f+1}), f even, into the one complex
+// transform and separates them afterwards (2 Y_a[k] = Z[k] + conj Z[N-k], 2 Y_b[k] = (Z[k] - conj Z[N-k]) / i); the exact factor
+// 1/4 of the powers is applied to each stored value.  The pairs are (2j, 2j + 1) of the stream whatever the split into chunks
+// (a chunk is whole iterations), and a last frame without a partner is paired with ITSELF, so a cell's bits depend neither on
+// the batch nor on the chunk count.  A slot with no frame at all reloads the chunk's first frame and stores nothing.  The
+// frame loop is uniform over the workgroup (it holds two workgroup barriers, see the tile); a workgroup of WAVES waves and
+// iteration covers TF = 2 * WAVES * 64/SUB consecutive frames (WAVES = 4; 2 at n_fft 2048, where four fp64 buffers, the
+// table and the tile do not fit the LDS).
+//
+// The tile: P and gP are [B][bins][frames] (torch's layout: bins are the channels of the critics' Conv1d), and a lane owns
+// bins sl + SUB i of its two frames -- a direct access is 64 runs of 8 bytes `frames` floats apart per instruction.  The
+// workgroup stages [bins][TF] floats (row stride TF + 1) in LDS behind the exchange buffers instead: the waves write / read
+// their columns there, and all threads move the tile with f running along the lanes (runs of TF floats).
+//
+// Adjoint (ADJ): Re FFT(conj c_a + i conj c_b) does not separate two frames, so c is extended Hermitian-symmetrically:
+// d_k = conj(c_k) / 2, d_{N-k} = c_k / 2 (0 < k < N/2), d_0 = Re c_0, d_{N/2} = Re c_{N/2}.  FFT(d) is then real and equal
+// to the sum above (every bin of 0 .. N/2 once, no 1/N, no doubling), so FFT(d_a + i d_b) = g_a / w + i g_b / w: two frames
+// share the second transform as they share the first -- two transforms per frame pair where a transform per frame would take
+// three.  The lane that owns bin k writes z_k and z_{N-k} into the exchange buffer in place (nobody else reads those two),
+// and the first pass of the second transform reads its points like every later pass.  With 2 Y from the separation,
+// conj(c_k) / 2 = (gP / 2) conj(2 Y_k): the halving is exact.  The windowed frame gradients go, rounded to fp32, to
+// ws[stream][frame][n]; stft_grad_gather_kernel (skip 0) adds them up in its fixed order.
+struct SpecArgs {
+    const float *y, *gp;     // gp: the upstream gradient (ADJ)
+    float *out;              // P, or ws (ADJ)
+    int64_t B, T;
+    int hop, win, chunks, frames_per_chunk, n_frames;
+};
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+template <int N> struct SpecGeo {
+    static constexpr int WAVES = N >= 2048 ? 2 : 4;
+    static constexpr int NT = 64 * WAVES;                  // threads of a workgroup
+    static constexpr int NB = N / 2 + 1;                   // bins
+    static constexpr int TF = 2 * WAVES * Geo<N>::FPW;     // frames per workgroup and iteration: WAVES x FPW slots x 2
+    static constexpr int TS = TF + 1;                      // tile row stride (floats): odd, the column accesses spread over the banks
+    static constexpr int SLOTS = WAVES * Geo<N>::FPW;
+    static constexpr size_t smem = ((size_t)SLOTS * Geo<N>::NPAD + N) * sizeof(d2) + (size_t)NB * TS * sizeof(float);
+};
+
+__device__ __forceinline__ d2 cmul_d(d2 a, d2 b) { return (d2){a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+
+// One Stockham pass in fp64, radix R in {2, 4}, sub-transform size Ns: stockham_pass's mapping (v[q] = point sl + SUB q; butterfly b
+// of a lane is j = sl + SUB b, k = j mod Ns, input t times e^{-2 pi i t k / (Ns R)} = tab[t k N / (Ns R)]).
+template <int N, int R, int Ns, bool FIRST>
+__device__ __forceinline__ void spec_pass(d2 (&v)[Geo<N>::P], d2 *buf, const d2 *tab, int sl)
+{
+    constexpr int SUB = Geo<N>::SUB, P = Geo<N>::P, NB = N / R / SUB;
+    static_assert(NB >= 1 && (R == 2 || R == 4), "radix");
+    if constexpr (!FIRST) {
+        wave_lds_fence();
+#pragma unroll
+        for (int q = 0; q < P; ++q) v[q] = buf[padi(sl + SUB * q)];
+        wave_lds_fence();
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = sl + SUB * b;
+        const int k = j & (Ns - 1);
+        d2 x[R];
+#pragma unroll
+        for (int t = 0; t < R; ++t) x[t] = v[b + t * NB];
+        if constexpr (Ns > 1) {
+#pragma unroll
+            for (int t = 1; t < R; ++t) x[t] = cmul_d(x[t], tab[t * k * (N / (Ns * R))]);
+        }
+        if constexpr (R == 2) {
+            const d2 t0 = x[0];
+            x[0] = t0 + x[1]; x[1] = t0 - x[1];
+        } else {
+            const d2 s02 = x[0] + x[2], d02 = x[0] - x[2], s13 = x[1] + x[3], d13 = x[1] - x[3];
+            x[0] = s02 + s13; x[1] = (d2){d02.x + d13.y, d02.y - d13.x};
+            x[2] = s02 - s13; x[3] = (d2){d02.x - d13.y, d02.y + d13.x};
+        }
+        const int o = (j - k) * R + k;
+#pragma unroll
+        for (int m = 0; m < R; ++m) buf[padi(o + m * Ns)] = x[m];
+    }
+}
+
+// the passes from sub-transform size Ns up: radix 4 while it fits, then one radix 2.  FIRST: the points are in v (else in buf)
+template <int N, int Ns, bool FIRST>
+__device__ __forceinline__ void spec_fft(d2 (&v)[Geo<N>::P], d2 *buf, const d2 *tab, int sl)
+{
+    if constexpr (Ns < N) {
+        constexpr int R = N / Ns >= 4 ? 4 : 2;
+        spec_pass<N, R, Ns, FIRST>(v, buf, tab, sl);
+        spec_fft<N, Ns * R, false>(v, buf, tab, sl);
+    }
+}
+
+template <int LOG2N, bool ADJ>
+__global__ __launch_bounds__(SpecGeo<(1 << LOG2N)>::NT) void spectrogram_kernel(SpecArgs a)
+{
+    constexpr int N = 1 << LOG2N;
+    using G = Geo<N>;
+    using SG = SpecGeo<N>;
+    constexpr int SUB = G::SUB, P = G::P, FPW = G::FPW, NPAD = G::NPAD;
+    constexpr int NB = SG::NB, TF = SG::TF, TS = SG::TS, NT = SG::NT;
+    extern __shared__ f2 stft_smem[];
+    d2 *smem = reinterpret_cast<d2 *>(stft_smem);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sl = lane & (SUB - 1), fs = lane / SUB;
+    d2 *buf = smem + (wave * FPW + fs) * NPAD;                               // this frame slot's exchange buffer
+    d2 *tab = smem + SG::SLOTS * NPAD;                                       // e^{-2 pi i j / N}, j < N
+    float *tile = reinterpret_cast<float *>(tab + N);                        // [NB][TS]
+    const int col = 2 * (wave * FPW + fs);                                   // this slot's two columns of the tile
+
+    for (int j = tid; j < N; j += NT) {
+        double sn, cs;
+        sincospi(-2.0 * (double)j / (double)N, &sn, &cs);
+        tab[j] = (d2){cs, sn};
+    }
+    // periodic Hann of `win` samples, centred in n_fft: sin^2(pi n / win) in fp64
+    const int left = (N - a.win) / 2;
+    double wreg[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        const int n = sl + SUB * q - left;
+        const double sn = sinpi((double)n / (double)a.win);
+        wreg[q] = (n >= 0 && n < a.win) ? sn * sn : 0.0;
+    }
+    __syncthreads();                                                         // the table is complete
+
+    const int64_t stream = blockIdx.x / a.chunks;
+    const int chunk = blockIdx.x % a.chunks;
+    const int L = (int)a.T;
+    const float *ys = a.y + stream * a.T;
+    const int f_begin = chunk * a.frames_per_chunk;                          // (a multiple of TF)
+    const int f_end = min(f_begin + a.frames_per_chunk, a.n_frames);
+    const size_t cells = (size_t)stream * NB * a.n_frames;                   // this stream's [NB][n_frames] of P / gP
+
+    for (int fb = f_begin; fb < f_end; fb += TF) {          // uniform over the workgroup
+        int fa = fb + col;
+        const bool live_a = fa < f_end, live_b = fa + 1 < f_end;
+        if (!live_a) fa = f_begin;                          // idle slot: reload a valid frame, nothing is stored for it
+        const int fp = live_b ? fa + 1 : fa;                // no partner (odd frame count): the frame itself
+        if constexpr (ADJ) {                                // the iteration's gP cells, f along the lanes (zero past the end)
+            for (int idx = tid; idx < NB * TF; idx += NT) {
+                const int k = idx / TF, fi = idx % TF;
+                tile[k * TS + fi] = fb + fi < f_end ? a.gp[cells + (size_t)k * a.n_frames + fb + fi] : 0.0f;
+            }
+        }
+        // z = w (y_fa + i y_fp), samples reflected at the ends (torch.stft center=True, pad_mode="reflect")
+        d2 v[P];
+        const int sa = fa * a.hop - N / 2 + sl, sp = fp * a.hop - N / 2 + sl;    // (T < 2^31 - n_fft: checked by the API)
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            int ia = sa + SUB * q, ip = sp + SUB * q;
+            ia = ia < 0 ? -ia : ia;
+            ia = ia >= L ? 2 * (L - 1) - ia : ia;
+            ip = ip < 0 ? -ip : ip;
+            ip = ip >= L ? 2 * (L - 1) - ip : ip;
+            v[q] = (d2){wreg[q] * (double)ys[ia], wreg[q] * (double)ys[ip]};
+        }
+        spec_fft<N, 1, true>(v, buf, tab, sl);
+        if constexpr (!ADJ) {
+            wave_lds_fence();
+            auto bin = [&](int k) {                         // 4 x the powers of the slot's two frames -> its tile columns
+                const d2 zk = buf[padi(k)], zn = buf[padi((N - k) & (N - 1))];
+                const d2 A2 = {zk.x + zn.x, zk.y - zn.y}, B2 = {zk.y + zn.y, zn.x - zk.x};
+                tile[k * TS + col] = (float)(0.25 * (A2.x * A2.x + A2.y * A2.y));
+                tile[k * TS + col + 1] = (float)(0.25 * (B2.x * B2.x + B2.y * B2.y));
+            };
+#pragma unroll
+            for (int i = 0; i < P / 2; ++i) bin(sl + SUB * i);
+            if (sl == 0) bin(N / 2);
+            __syncthreads();                                // the tile is complete
+            for (int idx = tid; idx < NB * TF; idx += NT) {
+                const int k = idx / TF, fi = idx % TF;
+                if (fb + fi < f_end) a.out[cells + (size_t)k * a.n_frames + fb + fi] = tile[k * TS + fi];
+            }
+        } else {
+            __syncthreads();                                // the tile is complete; every lane's transform is in its buffer
+            auto bin = [&](int k) {                         // z_k and z_{N-k} of d_a + i d_b, in place
+                const int kn = (N - k) & (N - 1);
+                const d2 zk = buf[padi(k)], zn = buf[padi(kn)];
+                const d2 A2 = {zk.x + zn.x, zk.y - zn.y}, B2 = {zk.y + zn.y, zn.x - zk.x};
+                const double h = (k == 0 || k == N / 2) ? 1.0 : 0.5;        // (there A2.y = B2.y = 0 exactly, and kn = k)
+                const double ga = h * (double)tile[k * TS + col], gb = h * (double)tile[k * TS + col + 1];
+                const d2 da = {ga * A2.x, -(ga * A2.y)}, db = {gb * B2.x, -(gb * B2.y)};
+                buf[padi(k)] = (d2){da.x - db.y, da.y + db.x};              // d_a + i d_b
+                buf[padi(kn)] = (d2){da.x + db.y, db.x - da.y};             // conj d_a + i conj d_b
+            };
+#pragma unroll
+            for (int i = 0; i < P / 2; ++i) bin(sl + SUB * i);
+            if (sl == 0) bin(N / 2);
+            spec_fft<N, 1, false>(v, buf, tab, sl);
+            wave_lds_fence();
+            if (live_a) {
+                float *o = a.out + ((size_t)stream * a.n_frames + fa) * N + sl;
+#pragma unroll
+                for (int q = 0; q < P; ++q) {
+                    const d2 g = buf[padi(sl + SUB * q)];
+                    o[SUB * q] = (float)(wreg[q] * g.x);
+                    if (live_b) o[N + SUB * q] = (float)(wreg[q] * g.y);
+                }
+            }
+        }
+        __syncthreads();                                    // tile and exchange buffers are free for the next iteration
+    }
+}
+
+template <int LOG2N, bool ADJ>
+static hipError_t launch_spec(SpecArgs &a, hipStream_t stream)
+{
+    constexpr int N = 1 << LOG2N, TF = SpecGeo<N>::TF;
+    // whole iterations of a workgroup per chunk, about 1024 workgroups; every cell is written once, from a frame pair that
+    // does not depend on the split
+    const int iters = (a.n_frames + TF - 1) / TF;
+    const int want = (int)min((int64_t)iters, max((int64_t)1, (1024 + a.B - 1) / a.B));
+    a.frames_per_chunk = (iters + want - 1) / want * TF;
+    a.chunks = (a.n_frames + a.frames_per_chunk - 1) / a.frames_per_chunk;
+    auto k = spectrogram_kernel<LOG2N, ADJ>;
+    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SpecGeo<N>::smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3((unsigned)(a.B * a.chunks)), dim3(SpecGeo<N>::NT), SpecGeo<N>::smem, stream, a);
+    return hipGetLastError();
+}
+
+template <bool ADJ>
+static hipError_t launch_spec_n(int n_fft, SpecArgs &a, hipStream_t stream)
+{
+    switch (n_fft) {
+    case 64: return launch_spec<6, ADJ>(a, stream);
+    case 128: return launch_spec<7, ADJ>(a, stream);
+    case 256: return launch_spec<8, ADJ>(a, stream);
+    case 512: return launch_spec<9, ADJ>(a, stream);
+    case 1024: return launch_spec<10, ADJ>(a, stream);
+    case 2048: return launch_spec<11, ADJ>(a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_spectrogram(const float *y, int64_t B, int64_t T, int n_fft, int hop, int win, float *P, hipStream_t stream)
+{
+    SpecArgs a;
+    a.y = y; a.gp = nullptr; a.out = P; a.B = B; a.T = T; a.hop = hop; a.win = win;
+    a.n_frames = (int)(1 + T / hop);
+    return launch_spec_n<false>(n_fft, a, stream);
+}
+
+hipError_t launch_spectrogram_grad(const float *y, const float *gP, int64_t B, int64_t T, int n_fft, int hop, int win, float *ws,
+                                   float *dy, int accumulate, hipStream_t stream)
+{
+    SpecArgs a;
+    a.y = y; a.gp = gP; a.out = ws; a.B = B; a.T = T; a.hop = hop; a.win = win;
+    a.n_frames = (int)(1 + T / hop);
+    hipError_t e = launch_spec_n<true>(n_fft, a, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(stft_grad_gather_kernel, dim3((unsigned)((B * T + 255) / 256)), dim3(256), 0, stream, ws, dy, B, T,
+                       (int64_t)0, n_fft, hop, a.n_frames, accumulate);
+    return hipGetLastError();
+}
+
 }   // namespace ntm

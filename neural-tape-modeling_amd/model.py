@@ -1647,3 +1647,47 @@ class ValLossSupervised(torch.nn.Module):
         d = esr_dcpre_sums(output, target).sum(dim=0)
         losses["ESRDCPre"] = float((d[0] / n) / (d[1] / n + ESR_EPS))
         return losses
+
+
+class TimeFreqConverter(torch.nn.Module):
+    """`TimeFreqConverter` of code/utilities/utilities.py:627-672, the front end of the reference's spectral critics, on the
+    device and differentiable: same constructor arguments, same buffers (`window`, `mel_basis`) and attributes.  As in the
+    reference the transform is torchaudio's Spectrogram(n_fft, hop_length = n_fft // 4, power = 2) -- the hop is n_fft / 4 and the
+    window a periodic Hann of n_fft samples WHATEVER `hop_length` and `win_length` say (they are stored, and `window` is built
+    from `win_length`, but neither reaches the transform).  `mel_basis` is the dense [n_mels, n_fft/2 + 1] float32 form of
+    utilities.mel_filterbank_sparse (librosa's published algorithm restated: parity unpinned).
+    forward(audio (..., T), mel=False) -> power spectrogram (..., bins, frames).squeeze(); mel=True -> (P, mel_basis @ P).
+    With an input that requires grad the output is a node of the graph (training.SpectrogramFn: ntm_spectrogram /
+    ntm_spectrogram_grad; the mel product is torch.matmul); otherwise no node is recorded."""
+
+    def __init__(self, n_fft=2048, hop_length=512, win_length=2048, sampling_rate=44100, n_mel_channels=160, mel_fmin=0.0,
+                 mel_fmax=None):
+        super().__init__()
+        from .utilities import mel_filterbank_sparse
+        first, start, w = mel_filterbank_sparse(sampling_rate, n_fft, n_mel_channels, mel_fmin, mel_fmax)
+        basis = np.zeros((n_mel_channels, n_fft // 2 + 1), np.float32)
+        for m in range(n_mel_channels):
+            basis[m, first[m]:first[m] + start[m + 1] - start[m]] = w[start[m]:start[m + 1]]
+        self.register_buffer("mel_basis", torch.from_numpy(basis))
+        self.register_buffer("window", torch.hann_window(win_length).float())
+        self.n_fft, self.hop_length, self.win_length = n_fft, hop_length, win_length
+        self.sampling_rate, self.n_mel_channels = sampling_rate, n_mel_channels
+
+    def n_frames(self, n_samples):
+        """Frames the transform makes of `n_samples` samples: the hop is n_fft // 4, not `hop_length`."""
+        return 1 + int(n_samples) // (int(self.n_fft) // 4)
+
+    def forward(self, audio, mel=False):
+        _require_hip(audio, "TimeFreqConverter")
+        n_fft = int(self.n_fft)
+        lead = audio.shape[:-1]
+        y = audio.reshape(-1, audio.shape[-1])
+        y = (y if y.dtype == torch.float32 else y.float()).contiguous()
+        if y.requires_grad and torch.is_grad_enabled():
+            P = training.SpectrogramFn.apply(y, n_fft, n_fft // 4, n_fft)
+        else:
+            P = training.spectrogram(y.detach(), n_fft, n_fft // 4, n_fft)
+        magnitude = P.reshape(lead + P.shape[-2:]).squeeze()
+        if mel:
+            return magnitude, torch.matmul(self.mel_basis, magnitude)
+        return magnitude

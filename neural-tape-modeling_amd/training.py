@@ -14,6 +14,8 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
     (ntm_esr_grad / ntm_esr_dcpre_grad).
   * mrstft_with_grad: the MRSTFTLoss value(s) exactly as the no-grad path computes them, and the adjoint of the STFT sums on the
     device (ntm_stft_grad, one call per resolution).
+  * SpectrogramFn: the power spectrogram |STFT|^2 as a graph node whose OUTPUT a network reads (TimeFreqConverter, the front end
+    of the reference's spectral critics): forward = ntm_spectrogram, backward = ntm_spectrogram_grad on the upstream gradient.
   * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
     replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
     launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
@@ -206,3 +208,40 @@ def mrstft_with_grad(loss, output, target, skip, whole_batch):
     if target.requires_grad:
         raise RuntimeError("MRSTFTLoss: gradients flow to the prediction only; the target must not require grad")
     return _MRSTFTLossFn.apply(output, target, loss, skip, whole_batch)
+
+
+def spectrogram(y, n_fft, hop, win):
+    """ntm_spectrogram on a contiguous float32 [B,T] device tensor -> P [B, n_fft/2 + 1, 1 + T // hop] float32, no graph."""
+    B, T = y.shape
+    if int(hop) <= 0:
+        raise _lib.NtmError(f"ntm_spectrogram: bad hop or win_length (hop = {hop})")
+    P = torch.empty(B, int(n_fft) // 2 + 1, 1 + T // int(hop), device=y.device, dtype=torch.float32)
+    _lib.check(_lib.lib().ntm_spectrogram(ptr(y), B, T, int(n_fft), int(hop), int(win), ptr(P), _lib.current_stream()),
+               "ntm_spectrogram")
+    return P
+
+
+class SpectrogramFn(torch.autograd.Function):
+    """(y [B,T] fp32 contiguous, n_fft, hop, win) -> P [B, bins, frames].  Only y is saved: the adjoint recomputes the spectrum.
+    Gradients go to the signal; no double backward."""
+
+    @staticmethod
+    def forward(ctx, y, n_fft, hop, win):
+        P = spectrogram(y, n_fft, hop, win)
+        ctx.save_for_backward(y)
+        ctx.res = (int(n_fft), int(hop), int(win))
+        return P
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gP):
+        y, = ctx.saved_tensors
+        n_fft, hop, win = ctx.res
+        B, T = y.shape
+        gP = gP.to(torch.float32).contiguous()
+        L = _lib.lib()
+        ws = torch.empty(max(int(L.ntm_stft_grad_workspace_floats(B, T, 0, n_fft, hop)), 1), device=y.device, dtype=torch.float32)
+        dy = torch.empty(B, T, device=y.device, dtype=torch.float32)
+        _lib.check(L.ntm_spectrogram_grad(ptr(y), ptr(gP), B, T, n_fft, hop, win, ptr(ws), ptr(dy), 0, _lib.current_stream()),
+                   "ntm_spectrogram_grad")
+        return dy, None, None, None
