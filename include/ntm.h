@@ -322,6 +322,45 @@ int ntm_spectrogram_grad(const float *y, const float *gP, int64_t B, int64_t T, 
                          float *ws, float *dy, int accumulate, void *stream);
 
 /*
+ * The conv stack of the reference's spectral critics behind the spectrogram (`SpecCrit`, code/critics.py:181-259), forward
+ * and backward: n_layers weight-normed Conv1d(c_in, c_out, k, groups) with stride 1, dilation 1 and no padding, effective
+ * weight w = g v / |v| (the norm over (c_in/groups, k) per output channel: torch.nn.utils.weight_norm, dim 0), LeakyReLU(0.2)
+ * after every layer but the last.  fp32 in, fp32 accumulate on the matrix pipe (csrc/critic_kernels.hip).
+ *   x    [B][C0][F0] fp32 contiguous: the layout of ntm_spectrogram's P, or of the mel product.  log_floor > 0: the first
+ *        layer reads log10(max(x, log_floor)) as it loads x (SpecCrit(log=True)); log_floor == 0: x as it is.
+ *   g, v, bias (and dg, dv, dbias): HOST arrays of n_layers DEVICE pointers -- g[l] [c_out], v[l] [c_out][c_in/groups][k],
+ *        bias[l] [c_out], the separate tensors a module owns.
+ *   out, gout  [B][c_out of the last layer][F_out], F_out = F0 - sum (k - 1).
+ *   saved  ntm_speccrit_saved_floats(...) floats the forward fills and the backward of the SAME sizes and parameters reads:
+ *        2 W + R + sum_{l < n-1} B c_out[l] F[l+1], with W = sum c_out (c_in/groups) k (the effective weights in the two
+ *        layouts the kernels read), R = sum c_out (1/|v|), then the post-activation output of every layer but the last (it is
+ *        the next layer's input; the LeakyReLU slope is recovered from its sign, y > 0 <=> pre > 0, and y == 0 takes 0.2).
+ *   ws   ntm_speccrit_workspace_floats(...) floats of device scratch for the backward: 2 max_{l < n-1} B c_out[l] F[l+1]
+ *        + min(B, 32)' (W + R), min(B, 32)' = ceil(B / ceil(B / min(B, 32))) the number of stream chunks of the weight gradient.
+ *   gx   [B][C0][F0] or NULL: no input gradient (the first layer's data-gradient kernel is skipped).  With the log head
+ *        gx = gX / (x ln 10) where x >= log_floor (it passes at equality: torch's clamp), else 0.
+ *   dg   NULL: no parameter gradients (dv and dbias are then not looked at).  Gradients are stored, not accumulated.
+ * No floating-point atomics: the weight gradient adds the streams of a chunk in order inside a workgroup and the chunks in order
+ * afterwards, so equal calls give equal bits; a stream's out and gx do not depend on the batch it is in.  Refused (-1 from the
+ * two size functions; NTM_EINVAL and a message starting with the function's name from the others) before anything touches a
+ * device: null pointers, n_layers outside [1, 8], a channel count outside [1, 1024] (C0 alone may be
+ * 1025, the bins of ntm_spectrogram's largest transform), k outside [1, 64], groups not dividing
+ * both channel counts, c_in of a layer not c_out of the one before it (C0 for the first), a k larger than the frames that
+ * reach it, B * C * F >= 2^31 for any tensor of the stack, a negative or NaN log_floor.  B == 0 returns NTM_OK without looking
+ * at the device pointers (the size functions then count the weights alone).
+ */
+typedef struct { int32_t c_in, c_out, k, groups; } ntm_conv1d_layer;      /* stride 1, dilation 1, no padding */
+int64_t ntm_speccrit_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers);
+int64_t ntm_speccrit_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers);
+int ntm_speccrit_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float log_floor, int n_layers,
+                         const ntm_conv1d_layer *layers, const float *const *g, const float *const *v, const float *const *bias,
+                         float *saved, float *out, void *stream);
+int ntm_speccrit_backward(const float *x, int64_t B, int64_t C0, int64_t F0, float log_floor, int n_layers,
+                          const ntm_conv1d_layer *layers, const float *const *g, const float *const *v,
+                          const float *saved, const float *gout, float *gx, float *const *dg, float *const *dv,
+                          float *const *dbias, float *ws, void *stream);
+
+/*
  * "Next" row N2 plumbing: pitched asynchronous copy between (pinned) host memory and the device, rows x
  * width_bytes with independent pitches -- what the segment feeder uses to send a TIME CHUNK of many segments
  * ([B, c0:c1] of a [B,T] batch) so that the copy of chunk c+1 overlaps the GRU launch on chunk c.

@@ -13,7 +13,7 @@ from .model import (RNN, DCPreESR, DiffDelRNN, ESRLoss, MRSTFTLoss, Replicas, Ti
 from .tape import Tape, TapeMagnetization  # noqa: F401
 from .tcn import TCN  # noqa: F401
 from .utilities import nextpow2, parse_hidden_size, parse_loss, parse_model  # noqa: F401
-from . import distributed, feeder, harness, weights  # noqa: F401
+from . import critics, distributed, feeder, harness, weights  # noqa: F401
 
 __all__ = ["RNN", "DiffDelRNN", "Replicas", "TimeVaryingDelayLine", "TCN", "Tape", "TapeMagnetization", "ESRLoss", "DCPreESR", "MRSTFTLoss", "ValLossSupervised", "TimeFreqConverter", "stft_sums", "spec_sums", "mel_sums", "esr_dcpre_sums", "esr_sums", "esr_per_segment",
-           "parse_hidden_size", "parse_model", "parse_loss", "nextpow2", "weights", "build", "NtmError"]
+           "parse_hidden_size", "parse_model", "parse_loss", "nextpow2", "weights", "critics", "build", "NtmError"]

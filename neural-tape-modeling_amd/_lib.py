@@ -77,7 +77,28 @@ _SIGNATURES = {
     "ntm_spectrogram": (_int, [_vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "ntm_spectrogram_grad": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _int, _vp]),
     "ntm_stft_grad": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, ctypes.c_float, _vp, _vp, _vp, _int, _vp]),
+    # the conv stack of the spectral critics (additions within ABI version 9); layers: ConvLayer[n], g / v / bias / dg / dv / dbias:
+    # host arrays of n device pointers (ptr_array)
+    "ntm_speccrit_saved_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
+    "ntm_speccrit_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
+    "ntm_speccrit_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ntm_speccrit_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+
+
+class ConvLayer(ctypes.Structure):
+    """include/ntm.h ntm_conv1d_layer: Conv1d(c_in, c_out, k, groups), stride 1, dilation 1, no padding."""
+    _fields_ = [("c_in", ctypes.c_int32), ("c_out", ctypes.c_int32), ("k", ctypes.c_int32), ("groups", ctypes.c_int32)]
+
+
+def conv_layers(spec):
+    """((c_in, c_out, k, groups), ...) -> a ConvLayer array for the ntm_speccrit entry points."""
+    return (ConvLayer * len(spec))(*[ConvLayer(*map(int, s)) for s in spec])
+
+
+def ptr_array(tensors):
+    """Host array of the device pointers of `tensors`, as the ntm_speccrit entry points take their parameters."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 TRAIN_GRAD_FLOATS = 12929   # include/ntm.h NTM_TRAIN_GRAD_FLOATS: w_ih | w_hh | b_ih | b_hh | w_o | b_o of GRU(1, 64) + Linear(64, 1)
 
 # include/ntm_lab.h: libntm_lab.so (older / experimental GRU kernels, diagnostic builds) -- tests and tools only

@@ -1,0 +1,138 @@
+"""The spectral critics of the reference's adversarial training (code/critics.py:125-259, 337-348) on the device: `SpecCrit`,
+`MultiSpecCrit` and `get_critic` with the reference's constructor signatures, attribute names and methods.
+
+A SpecCrit is the reference's ModuleList: index 0 the TimeFreqConverter (model.py, the device spectrogram), then real
+weight_norm(nn.Conv1d) modules with nn.LeakyReLU(0.2, True) between them at the reference's indices -- so state_dict(), .to(),
+parameters(), zero_grad() and an optimizer see what they see in the reference.  forward() does not call those modules: it
+hands their weight_g, weight_v and bias to training.SpecCritFn, one graph node for the whole stack on the kernels of
+csrc/critic_kernels.hip (the log10 head is read into the first layer).  The mel product stays torch.matmul; the hinge / mean
+losses on the outputs and the optimizers stay torch's.  Built: the stride-1 stacks of configs/AdversarialConfig.py's
+MultiSpecCrit entries (critic 1, 2 and 5).  MelGCrit and DilatedConvDisc, the time-domain critics, are not."""
+import torch
+import torch.nn.functional as F
+from torch import nn
+from torch.nn.utils import weight_norm
+
+from . import training
+from .model import TimeFreqConverter
+
+SUPPORTED = "MultiSpecCrit / SpecCrit with stride=1 (tf_rep 'spec' or 'mel') on a HIP device"
+
+
+def WNConv1d(*args, **kwargs):
+    return weight_norm(nn.Conv1d(*args, **kwargs))
+
+
+class SpecCrit(nn.Module):
+    """Spectral critic that takes the TF representation of audio as input (code/critics.py:181-259)."""
+
+    def __init__(self, scale, kernel_size, hop_size, layers, chan_in, chan_fac, stride, g_fac, tf_rep, log, test_in_len):
+        super().__init__()
+        if stride != 1:
+            raise RuntimeError(f"SpecCrit: stride={stride} has no kernel; supported: {SUPPORTED}")
+        if tf_rep not in ("spec", "mel"):
+            raise RuntimeError(f"SpecCrit: tf_rep={tf_rep!r}; supported: {SUPPORTED}")
+        self.scale = scale
+        self.layers = nn.ModuleList()
+        self.log = log
+        self.log_eps = 1e-5
+        self.tf_rep = tf_rep
+
+        self.layers += [TimeFreqConverter(n_fft=scale, hop_length=hop_size, win_length=scale, sampling_rate=44100, n_mel_channels=160)]
+        layer1_chan = (scale // 2) + 1 if tf_rep == "spec" else 160
+        self.layers += [WNConv1d(in_channels=layer1_chan, out_channels=chan_in, kernel_size=10), nn.LeakyReLU(0.2, True)]
+        for _ in range(layers - 2):
+            out_channels = min(chan_in * chan_fac, 1024)
+            self.layers += [WNConv1d(in_channels=chan_in, out_channels=out_channels, kernel_size=kernel_size, stride=stride,
+                                     groups=out_channels // g_fac),
+                            nn.LeakyReLU(0.2, True)]
+            chan_in = out_channels
+        self.layers += [WNConv1d(in_channels=chan_in, out_channels=chan_in, kernel_size=5), nn.LeakyReLU(0.2, True)]
+        self.layers += [WNConv1d(in_channels=chan_in, out_channels=1, kernel_size=3)]
+
+        # the reference runs test_input() here: a CPU draw that moves the generator on (a seeded construction must give the
+        # next model the reference's weights) and a forward for the printed size.  The draw is made and dropped, the size
+        # follows from the sizes: the constructor touches no device
+        torch.randn((10, 1, test_in_len))
+        print('Spect Disc = {}, kernel size = {}, layers = {}, output size = {},{},{} '
+              .format(scale, kernel_size, layers, 10, 1, self.output_frames(test_in_len)))
+
+    def convs(self):
+        """The conv modules of the stack, in order."""
+        return [m for m in self.layers[1:] if isinstance(m, nn.Conv1d)]
+
+    def spec(self):
+        """((c_in, c_out, k, groups), ...) as training.SpecCritFn takes it."""
+        return tuple((c.in_channels, c.out_channels, c.kernel_size[0], c.groups) for c in self.convs())
+
+    def output_frames(self, n_samples):
+        """Frames of the output for `n_samples` samples of audio."""
+        return self.layers[0].n_frames(n_samples) - sum(c.kernel_size[0] - 1 for c in self.convs())
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError(f"SpecCrit: HIP device only (no CPU fallback); supported: {SUPPORTED}")
+        if self.tf_rep == 'spec':
+            x = self.layers[0](x).squeeze()
+        else:
+            _, x = self.layers[0](x, mel=True)
+            x = x.squeeze()
+        if x.dim() not in (2, 3):
+            raise RuntimeError(f"SpecCrit: expected (bins, frames) or (batch, bins, frames) behind the transform, got {tuple(x.shape)}")
+        params = [p for c in self.convs() for p in (c.weight_g, c.weight_v, c.bias)]
+        floor = self.log_eps if self.log else 0.0
+        out = training.SpecCritFn.apply(x if x.dim() == 3 else x.unsqueeze(0), floor, self.spec(), *params)
+        return out if x.dim() == 3 else out[0]
+
+    def test_input(self, seq_len):
+        """The reference's dummy pass: its CPU draw, run where the parameters are."""
+        dummy_input = torch.randn((10, 1, seq_len))
+        return self(dummy_input.to(self.layers[1].bias.device))
+
+
+class MultiSpecCrit(nn.Module):
+    """Multi-scale container for the spectral critic (code/critics.py:125-178)."""
+
+    def __init__(self, scales, kernel_sizes, hop_sizes, layers, chan_in, chan_fac, stride, g_fac, test_in_len, tf_rep='spec',
+                 log=False):
+        super().__init__()
+        self.scales = scales
+        self.models = nn.ModuleList()
+        for i in range(len(scales)):
+            self.models.append(SpecCrit(scales[i], kernel_sizes[i], hop_sizes[i], layers, chan_in, chan_fac, stride, g_fac, tf_rep,
+                                        log, test_in_len))
+
+    def forward(self, x):
+        return [model(x) for model in self.models]
+
+    def train_crit(self, fake_ins, real_ins, optimiser):
+        D_fake = self(fake_ins)
+        D_real = self(real_ins)
+        loss_D = 0
+        for scale in D_fake:
+            loss_D += F.relu(1 + scale).mean()
+        for scale in D_real:
+            loss_D += F.relu(1 - scale).mean()
+        loss_D.backward()
+        optimiser.step()
+        return loss_D.item()
+
+    def train_gen(self, gen_out, optimiser):
+        D_fake = self(gen_out)
+        loss_G = 0
+        for scale in D_fake:
+            loss_G += -scale.mean()
+        loss_G.backward()
+        optimiser.step()
+        return loss_G.item()
+
+
+def get_critic(critic_name, critic_pars, device, crit_lr, test_in_len):
+    """code/critics.py:337-348.  Adam(lr=crit_lr, betas=(0.5, 0.9)) as there, whatever crit_lr is (the configs carry 0)."""
+    if critic_name != 'MultiSpecCrit':
+        raise RuntimeError(f"get_critic: {critic_name!r} is not built (the time-domain critics MelGanCrit and DilatedConvDisc "
+                           f"are another kernel family); built: {SUPPORTED}")
+    critic_pars['test_in_len'] = test_in_len
+    critic = MultiSpecCrit(**critic_pars).to(device=device)
+    optC = torch.optim.Adam(critic.parameters(), lr=crit_lr, betas=(0.5, 0.9))
+    return critic, optC

@@ -491,6 +491,81 @@ int ntm_spectrogram_grad(const float *y, const float *gP, int64_t B, int64_t T, 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_spectrogram_grad");
 }
 
+// the argument checks the four ntm_speccrit entry points share, then the plan
+static int speccrit_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers,
+                          ntm::CritPlan &p)
+{
+    if (B < 0 || C0 < 1 || F0 < 1) return fail(NTM_EINVAL, w + ": bad size");
+    if (n_layers < 1 || n_layers > 8) return fail(NTM_EINVAL, w + ": n_layers must lie in [1, 8]");
+    if (!layers) return fail(NTM_EINVAL, w + ": null pointer");
+    if (C0 > 1025) return fail(NTM_EINVAL, w + ": C0 must lie in [1, 1025] (the bins of the largest transform)");
+    int64_t c = C0, F = F0;
+    for (int l = 0; l < n_layers; ++l) {
+        const ntm_conv1d_layer &y = layers[l];
+        if (y.c_in < 1 || y.c_in > (l ? 1024 : 1025) || y.c_out < 1 || y.c_out > 1024)
+            return fail(NTM_EINVAL, w + ": channel counts must lie in [1, 1024]");
+        if (y.k < 1 || y.k > 64) return fail(NTM_EINVAL, w + ": k must lie in [1, 64]");
+        if (y.groups < 1 || y.c_in % y.groups || y.c_out % y.groups) return fail(NTM_EINVAL, w + ": groups must divide both channel counts");
+        if (y.c_in != c) return fail(NTM_EINVAL, w + ": c_in of a layer must be c_out of the layer before it (C0 for the first)");
+        if (y.k > F) return fail(NTM_EINVAL, w + ": k is larger than the frames that reach the layer");
+        if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+        F -= y.k - 1;
+        c = y.c_out;
+    }
+    if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+    ntm::crit_plan(p, B, C0, F0, n_layers, layers);
+    return NTM_OK;
+}
+
+int64_t ntm_speccrit_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers)
+{
+    ntm::CritPlan p;
+    if (speccrit_sizes("ntm_speccrit_saved_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
+    return p.saved_total;
+}
+
+int64_t ntm_speccrit_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers)
+{
+    ntm::CritPlan p;
+    if (speccrit_sizes("ntm_speccrit_workspace_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
+    return p.ws_total;
+}
+
+int ntm_speccrit_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float log_floor, int n_layers,
+                         const ntm_conv1d_layer *layers, const float *const *g, const float *const *v, const float *const *bias,
+                         float *saved, float *out, void *stream)
+{
+    const std::string w("ntm_speccrit_forward");
+    ntm::CritPlan p;
+    if (int rc = speccrit_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
+    if (!(log_floor >= 0.0f)) return fail(NTM_EINVAL, w + ": log_floor must be positive, or 0 for no log");
+    if (B == 0) return NTM_OK;
+    if (!x || !g || !v || !bias || !saved || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int l = 0; l < n_layers; ++l)
+        if (!g[l] || !v[l] || !bias[l]) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_speccrit_forward(p, x, B, log_floor, g, v, bias, saved, out, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_speccrit_forward");
+}
+
+int ntm_speccrit_backward(const float *x, int64_t B, int64_t C0, int64_t F0, float log_floor, int n_layers,
+                          const ntm_conv1d_layer *layers, const float *const *g, const float *const *v, const float *saved,
+                          const float *gout, float *gx, float *const *dg, float *const *dv, float *const *dbias, float *ws,
+                          void *stream)
+{
+    const std::string w("ntm_speccrit_backward");
+    ntm::CritPlan p;
+    if (int rc = speccrit_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
+    if (!(log_floor >= 0.0f)) return fail(NTM_EINVAL, w + ": log_floor must be positive, or 0 for no log");
+    if (B == 0) return NTM_OK;
+    if (!x || !g || !v || !saved || !gout || !ws) return fail(NTM_EINVAL, w + ": null pointer");
+    if (dg && (!dv || !dbias)) return fail(NTM_EINVAL, w + ": null pointer (dg, dv and dbias come together)");
+    for (int l = 0; l < n_layers; ++l)
+        if (!g[l] || !v[l] || (dg && (!dg[l] || !dv[l] || !dbias[l]))) return fail(NTM_EINVAL, w + ": null pointer");
+    if (gx && (gx == x || gx == gout)) return fail(NTM_EINVAL, w + ": gx must not alias x or gout");
+    hipError_t e = ntm::launch_speccrit_backward(p, x, B, log_floor, g, v, saved, gout, gx, dg, dv, dbias, ws, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_speccrit_backward");
+}
+
 int ntm_copy2d_async(void *dst, int64_t dst_pitch_bytes, const void *src, int64_t src_pitch_bytes, int64_t width_bytes,
                      int64_t rows, int kind, void *stream)
 {

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ntm.h"
+
 namespace ntm {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -102,6 +104,27 @@ hipError_t launch_esr_grad_replicas(const float *y, const float *t, int64_t R, i
 hipError_t launch_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t bper, int64_t T, float pole,
                                           const double *sums2, const float *gout, double eps, float *dy, hipStream_t stream);
 hipError_t launch_loss_sums_replicas(const double *rows, int64_t R, int64_t bper, int splits, double *out, hipStream_t stream);
+// the conv stack of the spectral critics (critic_kernels.hip): where everything lies in `saved` and `ws`, filled by crit_plan
+// from sizes ntm_api.hip has checked
+constexpr int kCritMaxLayers = 8;   // include/ntm.h: n_layers in [1, 8]
+struct CritPlan {
+    int n;
+    int c_in[kCritMaxLayers], c_out[kCritMaxLayers], k[kCritMaxLayers], groups[kCritMaxLayers];
+    int64_t F[kCritMaxLayers + 1];           // frames entering layer l; F[n]: frames of the output
+    int64_t w_off[kCritMaxLayers], w_total;  // floats of layer l's weights within wF / wB
+    int row0[kCritMaxLayers], rows;          // output channels counted through the layers
+    int64_t act_off[kCritMaxLayers];         // saved: wF | wB | 1/|v| | outputs of layers 0 .. n-2
+    int64_t saved_total;
+    int nchunk, per;                         // weight gradient: chunks of `per` streams
+    int64_t gz_size;                         // ws: gz ping | gz pong | per layer the chunk partials of dW, then of dbias
+    int64_t part_off[kCritMaxLayers], bpart_off[kCritMaxLayers], ws_total;
+};
+void crit_plan(CritPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer *L);
+hipError_t launch_speccrit_forward(const CritPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
+                                   const float *const *v, const float *const *bias, float *saved, float *out, hipStream_t stream);
+hipError_t launch_speccrit_backward(const CritPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
+                                    const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
+                                    float *const *dv, float *const *dbias, float *ws, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
                             int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm
