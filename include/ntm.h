@@ -361,6 +361,48 @@ int ntm_speccrit_backward(const float *x, int64_t B, int64_t C0, int64_t F0, flo
                           float *const *dbias, float *ws, void *stream);
 
 /*
+ * The conv stack of the reference's time-domain critic (`DilatedConvDisc`, code/critics.py:262-331), forward and backward: the
+ * ntm_speccrit family with a dilation per layer, up to 16 layers, a LeakyReLU slope passed by the caller and no log head.
+ * n_layers weight-normed Conv1d(c_in, c_out, k, groups, dilation) with stride 1 and no padding, frames shrinking as
+ * F[l+1] = F[l] - (k - 1) dilation; effective weight w = g v / |v| (the norm over (c_in/groups, k) per output channel);
+ * LeakyReLU(slope) after every layer but the last.  fp32 in, fp32 accumulate on the matrix pipe (csrc/convstack_kernels.hip).
+ *   x    [B][C0][F0] fp32 contiguous (the waveform: C0 = 1).
+ *   g, v, bias (and dg, dv, dbias): HOST arrays of n_layers DEVICE pointers, as in the ntm_speccrit family.
+ *   out, gout  [B][c_out of the last layer][F_out], F_out = F0 - sum (k - 1) dilation.
+ *   saved  ntm_convstack_saved_floats(...) floats the forward fills and the backward of the SAME sizes, slope and parameters
+ *        reads: 2 W + R + sum_{l < n-1} B c_out[l] F[l+1], with W = sum c_out (c_in/groups) k, R = sum c_out, as in the
+ *        ntm_speccrit family (the slope's side is recovered from the sign of the saved output: y > 0 <=> pre > 0 because
+ *        slope > 0, and y == 0 takes the slope).
+ *   ws   ntm_convstack_workspace_floats(...) floats of device scratch for the backward:
+ *        2 max_{l < n-1} B c_out[l] F[l+1] + sum_l min(B, 32)' ceil(F[l+1] / 1024) (W_l + c_out[l]),
+ *        W_l = c_out (c_in/groups) k of layer l.  The chunk rule of the weight gradient: the streams are cut into
+ *        min(B, 32)' = ceil(B / ceil(B / min(B, 32))) contiguous chunks (as in the ntm_speccrit family; none for B == 0) and the
+ *        output frames of layer l into segments of 1024; one workgroup per (stream chunk, segment) adds its streams in
+ *        order and its frames in order (256 frames from 0 at a time, then to its total) and stores one partial; the partials
+ *        are added stream chunk major, segment minor.
+ *   gx   [B][C0][F0] or NULL: no input gradient (the first layer's data-gradient kernel is skipped).
+ *   dg   NULL: no parameter gradients (dv and dbias are then not looked at).  Gradients are stored, not accumulated.
+ * No floating-point atomics: equal calls give equal bits; a stream's out and gx do not depend on the batch it is in.  Refused
+ * (-1 from the two size functions; NTM_EINVAL and a message starting with the function's name from the others) before
+ * anything touches a device: null pointers, n_layers outside [1, 16], a channel count outside [1, 1024], k outside [1, 64],
+ * dilation outside [1, 2^20], groups not dividing both channel counts, c_in of a layer not c_out of the one before it (C0 for
+ * the first), a layer whose (k - 1) dilation + 1 is larger than the frames that reach it, B * C * F >= 2^31 for any tensor of
+ * the stack, a slope outside (0, 1) or NaN (forward and backward).  B == 0 returns NTM_OK without looking at the device
+ * pointers (the size functions then count the weights alone).  Additions within ABI version 9: ntm_conv1d_layer and the
+ * ntm_speccrit entry points are unchanged.
+ */
+typedef struct { int32_t c_in, c_out, k, groups, dilation; } ntm_conv1d_layer_d;   /* stride 1, no padding */
+int64_t ntm_convstack_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers);
+int64_t ntm_convstack_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers);
+int ntm_convstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                          const ntm_conv1d_layer_d *layers, const float *const *g, const float *const *v, const float *const *bias,
+                          float *saved, float *out, void *stream);
+int ntm_convstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                           const ntm_conv1d_layer_d *layers, const float *const *g, const float *const *v,
+                           const float *saved, const float *gout, float *gx, float *const *dg, float *const *dv,
+                           float *const *dbias, float *ws, void *stream);
+
+/*
  * "Next" row N2 plumbing: pitched asynchronous copy between (pinned) host memory and the device, rows x
  * width_bytes with independent pitches -- what the segment feeder uses to send a TIME CHUNK of many segments
  * ([B, c0:c1] of a [B,T] batch) so that the copy of chunk c+1 overlaps the GRU launch on chunk c.

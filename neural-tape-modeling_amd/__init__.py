@@ -4,7 +4,8 @@
 The directory name contains a hyphen, so import it through the root-level shim:  `import ntm_amd`.
 Layout:  csrc/ (HIP kernels + C ABI -> libntm.so), model.py (reference object protocol),
 utilities.py (name parsers), weights.py (exported checkpoints), harness.py (test-model.py loss loop),
-distributed.py (stream sharding + the one RCCL all-reduce).
+distributed.py (stream sharding + the one RCCL all-reduce), critics.py (the adversarial run's critics: MultiSpecCrit on the
+spectrogram, DilatedConvDisc on the waveform).
 """
 from . import _lib  # noqa: F401
 from ._lib import NtmError, build  # noqa: F401

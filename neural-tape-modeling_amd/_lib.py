@@ -83,6 +83,12 @@ _SIGNATURES = {
     "ntm_speccrit_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
     "ntm_speccrit_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ntm_speccrit_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the dilated conv stack of the time-domain critic (additions within ABI version 9); layers: ConvLayerD[n], the float is the
+    # LeakyReLU slope
+    "ntm_convstack_saved_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
+    "ntm_convstack_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
+    "ntm_convstack_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ntm_convstack_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -94,6 +100,17 @@ class ConvLayer(ctypes.Structure):
 def conv_layers(spec):
     """((c_in, c_out, k, groups), ...) -> a ConvLayer array for the ntm_speccrit entry points."""
     return (ConvLayer * len(spec))(*[ConvLayer(*map(int, s)) for s in spec])
+
+
+class ConvLayerD(ctypes.Structure):
+    """include/ntm.h ntm_conv1d_layer_d: Conv1d(c_in, c_out, k, groups, dilation), stride 1, no padding."""
+    _fields_ = [("c_in", ctypes.c_int32), ("c_out", ctypes.c_int32), ("k", ctypes.c_int32), ("groups", ctypes.c_int32),
+                ("dilation", ctypes.c_int32)]
+
+
+def conv_layers_d(spec):
+    """((c_in, c_out, k, groups, dilation), ...) -> a ConvLayerD array for the ntm_convstack entry points."""
+    return (ConvLayerD * len(spec))(*[ConvLayerD(*map(int, s)) for s in spec])
 
 
 def ptr_array(tensors):

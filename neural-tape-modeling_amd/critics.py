@@ -1,5 +1,5 @@
-"""The spectral critics of the reference's adversarial training (code/critics.py:125-259, 337-348) on the device: `SpecCrit`,
-`MultiSpecCrit` and `get_critic` with the reference's constructor signatures, attribute names and methods.
+"""The critics of the reference's adversarial training (code/critics.py:125-331, 337-348) on the device: `SpecCrit`,
+`MultiSpecCrit`, `DilatedConvDisc` and `get_critic` with the reference's constructor signatures, attribute names and methods.
 
 A SpecCrit is the reference's ModuleList: index 0 the TimeFreqConverter (model.py, the device spectrogram), then real
 weight_norm(nn.Conv1d) modules with nn.LeakyReLU(0.2, True) between them at the reference's indices -- so state_dict(), .to(),
@@ -7,7 +7,13 @@ parameters(), zero_grad() and an optimizer see what they see in the reference.  
 hands their weight_g, weight_v and bias to training.SpecCritFn, one graph node for the whole stack on the kernels of
 csrc/critic_kernels.hip (the log10 head is read into the first layer).  The mel product stays torch.matmul; the hinge / mean
 losses on the outputs and the optimizers stay torch's.  Built: the stride-1 stacks of configs/AdversarialConfig.py's
-MultiSpecCrit entries (critic 1, 2 and 5).  MelGCrit and DilatedConvDisc, the time-domain critics, are not."""
+MultiSpecCrit entries (critic 1, 2 and 5).
+
+A DilatedConvDisc (critic 3: configurations 3 and 7) is the reference's ModuleList in the same way -- weight_norm(nn.Conv1d(...,
+dilation=d)) at the even indices, the activation modules at the odd ones -- on the raw waveform; forward() hands the parameters
+to training.ConvStackFn, one graph node on the kernels of csrc/convstack_kernels.hip.  Built: nl_func "LeakyReLU" with a
+negative_slope in (0, 1), stacks of at most 16 conv layers.  MelGCrit (get_critic's 'MelGanCrit': strided grouped convolutions
+with reflection and zero padding) is not built."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -16,7 +22,8 @@ from torch.nn.utils import weight_norm
 from . import training
 from .model import TimeFreqConverter
 
-SUPPORTED = "MultiSpecCrit / SpecCrit with stride=1 (tf_rep 'spec' or 'mel') on a HIP device"
+SUPPORTED = ("MultiSpecCrit / SpecCrit with stride=1 (tf_rep 'spec' or 'mel') and DilatedConvDisc with nl_func='LeakyReLU' "
+             "(negative_slope in (0, 1)) on a HIP device")
 
 
 def WNConv1d(*args, **kwargs):
@@ -127,12 +134,99 @@ class MultiSpecCrit(nn.Module):
         return loss_G.item()
 
 
+class DilatedConvDisc(nn.Module):
+    """Time domain crit based on dilated convolutions (code/critics.py:262-331)."""
+
+    def __init__(self, in_channels=1, out_channels=1, kernel_size=5, layers=12, blocks=2, conv_channels=64, dil_fac=2,
+                 nl_func="LeakyReLU", nl_params={"negative_slope": 0.2}, test_in_len=1):
+        super().__init__()
+        if nl_func != "LeakyReLU":
+            raise RuntimeError(f"DilatedConvDisc: nl_func={nl_func!r} has no kernel; supported: {SUPPORTED}")
+        self.slope = float(nn.LeakyReLU(**nl_params).negative_slope)
+        if not 0.0 < self.slope < 1.0:
+            raise RuntimeError(f"DilatedConvDisc: LeakyReLU(negative_slope={self.slope}) has no kernel; supported: {SUPPORTED}")
+        self.layers = nn.ModuleList()
+        # the reference's loops as they stand: range(blocks - 1) builds one block for blocks=2, and the final layer takes
+        # in_channels=conv_channels whatever came before it
+        for blocks in range(blocks - 1):
+            dilation = 1
+            for _ in range(layers - 1):
+                self.layers += [WNConv1d(in_channels=in_channels, out_channels=conv_channels, kernel_size=kernel_size, dilation=dilation),
+                                getattr(nn, nl_func)(**nl_params)]
+                dilation *= dil_fac
+                in_channels = conv_channels
+        self.layers += [WNConv1d(in_channels=conv_channels, out_channels=out_channels, kernel_size=kernel_size, dilation=1)]
+
+        # the reference runs test_input() here: a CPU draw that moves the generator on and a forward for the printed size (which
+        # raises where the input is shorter than a kernel's span: its default test_in_len=1 does).  The draw is made and
+        # dropped, the size follows from the sizes: the constructor touches no device
+        torch.randn((10, 1, test_in_len))
+        if test_in_len < self.receptive_field():
+            raise RuntimeError(f"DilatedConvDisc: test_in_len={test_in_len} is shorter than the receptive field of "
+                               f"{self.receptive_field()} samples")
+        print('Dilated Conv Disc, output size = {},{},{} '.format(10, out_channels, self.output_frames(test_in_len)))
+
+    def convs(self):
+        """The conv modules of the stack, in order."""
+        return [m for m in self.layers if isinstance(m, nn.Conv1d)]
+
+    def spec(self):
+        """((c_in, c_out, k, groups, dilation), ...) as training.ConvStackFn takes it."""
+        return tuple((c.in_channels, c.out_channels, c.kernel_size[0], c.groups, c.dilation[0]) for c in self.convs())
+
+    def receptive_field(self):
+        """Samples of input under one sample of output."""
+        return 1 + sum((k - 1) * d for _, _, k, _, d in self.spec())
+
+    def output_frames(self, n_samples):
+        """Samples of the output for `n_samples` samples of audio."""
+        return n_samples - self.receptive_field() + 1
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError(f"DilatedConvDisc: HIP device only (no CPU fallback); supported: {SUPPORTED}")
+        c_in = self.layers[0].in_channels
+        if x.dim() not in (2, 3) or x.shape[-2] != c_in:
+            raise RuntimeError(f"DilatedConvDisc: expected ({c_in}, samples) or (batch, {c_in}, samples), got {tuple(x.shape)}")
+        params = [p for c in self.convs() for p in (c.weight_g, c.weight_v, c.bias)]
+        out = training.ConvStackFn.apply(x if x.dim() == 3 else x.unsqueeze(0), self.slope, self.spec(), *params)
+        return out if x.dim() == 3 else out[0]
+
+    def train_crit(self, fake_ins, real_ins, optimiser):
+        D_fake = self(fake_ins)
+        D_real = self(real_ins)
+        loss_D = F.relu(1 + D_fake).mean()
+        loss_D += F.relu(1 - D_real).mean()
+        loss_D.backward()
+        optimiser.step()
+        return loss_D.item()
+
+    def train_gen(self, gen_out, optimiser):
+        D_fake = self(gen_out)
+        loss_G = -D_fake.mean()
+        loss_G.backward()
+        optimiser.step()
+        return loss_G.item()
+
+    def test_input(self, seq_len):
+        """The reference's dummy pass: its CPU draw, run where the parameters are."""
+        dummy_input = torch.randn((10, 1, seq_len))
+        return self(dummy_input.to(self.layers[0].bias.device))
+
+
 def get_critic(critic_name, critic_pars, device, crit_lr, test_in_len):
     """code/critics.py:337-348.  Adam(lr=crit_lr, betas=(0.5, 0.9)) as there, whatever crit_lr is (the configs carry 0)."""
-    if critic_name != 'MultiSpecCrit':
-        raise RuntimeError(f"get_critic: {critic_name!r} is not built (the time-domain critics MelGanCrit and DilatedConvDisc "
-                           f"are another kernel family); built: {SUPPORTED}")
-    critic_pars['test_in_len'] = test_in_len
-    critic = MultiSpecCrit(**critic_pars).to(device=device)
+    if critic_name == 'MultiSpecCrit':
+        critic_pars['test_in_len'] = test_in_len
+        critic = MultiSpecCrit(**critic_pars).to(device=device)
+    elif critic_name == 'DilatedConvDisc':
+        # no CPU path: an instance on another device could do nothing, so it is refused before anything is built
+        if torch.device(device).type != 'cuda':
+            raise RuntimeError(f"get_critic: DilatedConvDisc on device {str(device)!r}: HIP device only (no CPU fallback); built: {SUPPORTED}")
+        critic_pars['test_in_len'] = test_in_len
+        critic = DilatedConvDisc(**critic_pars).to(device=device)
+    else:
+        raise RuntimeError(f"get_critic: {critic_name!r} is not built (MelGanCrit, the strided grouped time-domain critic, is "
+                           f"another kernel family); built: {SUPPORTED}")
     optC = torch.optim.Adam(critic.parameters(), lr=crit_lr, betas=(0.5, 0.9))
     return critic, optC

@@ -566,6 +566,82 @@ int ntm_speccrit_backward(const float *x, int64_t B, int64_t C0, int64_t F0, flo
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_speccrit_backward");
 }
 
+// the argument checks the four ntm_convstack entry points share, then the plan
+static int convstack_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers,
+                           ntm::ConvStackPlan &p)
+{
+    if (B < 0 || C0 < 1 || F0 < 1) return fail(NTM_EINVAL, w + ": bad size");
+    if (n_layers < 1 || n_layers > ntm::kConvStackMaxLayers) return fail(NTM_EINVAL, w + ": n_layers must lie in [1, 16]");
+    if (!layers) return fail(NTM_EINVAL, w + ": null pointer");
+    int64_t c = C0, F = F0;
+    for (int l = 0; l < n_layers; ++l) {
+        const ntm_conv1d_layer_d &y = layers[l];
+        if (c > 1024 || y.c_in < 1 || y.c_in > 1024 || y.c_out < 1 || y.c_out > 1024)
+            return fail(NTM_EINVAL, w + ": channel counts must lie in [1, 1024]");
+        if (y.k < 1 || y.k > 64) return fail(NTM_EINVAL, w + ": k must lie in [1, 64]");
+        if (y.dilation < 1 || y.dilation > (1 << 20)) return fail(NTM_EINVAL, w + ": dilation must lie in [1, 2^20]");
+        if (y.groups < 1 || y.c_in % y.groups || y.c_out % y.groups) return fail(NTM_EINVAL, w + ": groups must divide both channel counts");
+        if (y.c_in != c) return fail(NTM_EINVAL, w + ": c_in of a layer must be c_out of the layer before it (C0 for the first)");
+        const int64_t span = (int64_t)(y.k - 1) * y.dilation;
+        if (span + 1 > F) return fail(NTM_EINVAL, w + ": (k - 1) * dilation + 1 is larger than the frames that reach the layer");
+        if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+        F -= span;
+        c = y.c_out;
+    }
+    if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+    ntm::convstack_plan(p, B, C0, F0, n_layers, layers);
+    return NTM_OK;
+}
+
+int64_t ntm_convstack_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers)
+{
+    ntm::ConvStackPlan p;
+    if (convstack_sizes("ntm_convstack_saved_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
+    return p.saved_total;
+}
+
+int64_t ntm_convstack_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers)
+{
+    ntm::ConvStackPlan p;
+    if (convstack_sizes("ntm_convstack_workspace_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
+    return p.ws_total;
+}
+
+int ntm_convstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                          const ntm_conv1d_layer_d *layers, const float *const *g, const float *const *v, const float *const *bias,
+                          float *saved, float *out, void *stream)
+{
+    const std::string w("ntm_convstack_forward");
+    ntm::ConvStackPlan p;
+    if (int rc = convstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
+    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (B == 0) return NTM_OK;
+    if (!x || !g || !v || !bias || !saved || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int l = 0; l < n_layers; ++l)
+        if (!g[l] || !v[l] || !bias[l]) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_convstack_forward(p, x, B, slope, g, v, bias, saved, out, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_convstack_forward");
+}
+
+int ntm_convstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                           const ntm_conv1d_layer_d *layers, const float *const *g, const float *const *v, const float *saved,
+                           const float *gout, float *gx, float *const *dg, float *const *dv, float *const *dbias, float *ws,
+                           void *stream)
+{
+    const std::string w("ntm_convstack_backward");
+    ntm::ConvStackPlan p;
+    if (int rc = convstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
+    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (B == 0) return NTM_OK;
+    if (!x || !g || !v || !saved || !gout || !ws) return fail(NTM_EINVAL, w + ": null pointer");
+    if (dg && (!dv || !dbias)) return fail(NTM_EINVAL, w + ": null pointer (dg, dv and dbias come together)");
+    for (int l = 0; l < n_layers; ++l)
+        if (!g[l] || !v[l] || (dg && (!dg[l] || !dv[l] || !dbias[l]))) return fail(NTM_EINVAL, w + ": null pointer");
+    if (gx && (gx == x || gx == gout)) return fail(NTM_EINVAL, w + ": gx must not alias x or gout");
+    hipError_t e = ntm::launch_convstack_backward(p, x, B, slope, g, v, saved, gout, gx, dg, dv, dbias, ws, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_convstack_backward");
+}
+
 int ntm_copy2d_async(void *dst, int64_t dst_pitch_bytes, const void *src, int64_t src_pitch_bytes, int64_t width_bytes,
                      int64_t rows, int kind, void *stream)
 {

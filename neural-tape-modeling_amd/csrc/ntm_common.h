@@ -125,6 +125,29 @@ hipError_t launch_speccrit_forward(const CritPlan &p, const float *x, int64_t B,
 hipError_t launch_speccrit_backward(const CritPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
                                     const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
                                     float *const *dv, float *const *dbias, float *ws, hipStream_t stream);
+// the dilated conv stack of the time-domain critic (convstack_kernels.hip): the same record with a dilation per layer, up to
+// 16 layers, and a weight-gradient reduction cut over (stream chunk, frame segment)
+constexpr int kConvStackMaxLayers = 16;   // include/ntm.h: n_layers in [1, 16]
+struct ConvStackPlan {
+    int n;
+    int c_in[kConvStackMaxLayers], c_out[kConvStackMaxLayers], k[kConvStackMaxLayers], groups[kConvStackMaxLayers],
+        dil[kConvStackMaxLayers];
+    int64_t F[kConvStackMaxLayers + 1];           // frames entering layer l; F[n]: frames of the output
+    int64_t w_off[kConvStackMaxLayers], w_total;  // floats of layer l's weights within wF / wB
+    int row0[kConvStackMaxLayers], rows;          // output channels counted through the layers
+    int64_t act_off[kConvStackMaxLayers];         // saved: wF | wB | 1/|v| | outputs of layers 0 .. n-2
+    int64_t saved_total;
+    int nchunk, per;                              // weight gradient: chunks of `per` streams ...
+    int64_t nseg[kConvStackMaxLayers];            // ... times segments of 1024 output frames of layer l
+    int64_t gz_size;                              // ws: gz ping | gz pong | per layer the partials of dW, then of dbias
+    int64_t part_off[kConvStackMaxLayers], bpart_off[kConvStackMaxLayers], ws_total;
+};
+void convstack_plan(ConvStackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_d *L);
+hipError_t launch_convstack_forward(const ConvStackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+                                    const float *const *v, const float *const *bias, float *saved, float *out, hipStream_t stream);
+hipError_t launch_convstack_backward(const ConvStackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+                                     const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
+                                     float *const *dv, float *const *dbias, float *ws, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
                             int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm

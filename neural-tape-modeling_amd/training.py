@@ -19,6 +19,9 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
   * SpecCritFn: the conv stack of a spectral critic behind its spectrogram (critics.SpecCrit: weight-normed Conv1d layers with
     LeakyReLU(0.2) between them, the log10 head read into the first) as ONE graph node: forward = ntm_speccrit_forward,
     backward = ntm_speccrit_backward (data, weight and weight-norm gradients; the input gradient only where it is needed).
+  * ConvStackFn: the dilated conv stack of the time-domain critic (critics.DilatedConvDisc: weight-normed Conv1d layers with a
+    dilation each and LeakyReLU(slope) between them, on the raw waveform) as ONE graph node: forward = ntm_convstack_forward,
+    backward = ntm_convstack_backward, with the same rules as SpecCritFn.
   * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
     replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
     launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
@@ -306,6 +309,70 @@ class SpecCritFn(torch.autograd.Function):
         _lib.check(L.ntm_speccrit_backward(ptr(x), B, C0, F0, log_floor, n, layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]),
                                            ptr(saved), ptr(gout), ptr(gx), arr(grads[0::3]), arr(grads[1::3]), arr(grads[2::3]),
                                            ptr(ws), _lib.current_stream()), "ntm_speccrit_backward")
+        if B == 0:
+            gx = None if gx is None else gx.zero_()
+            grads = [g.zero_() for g in grads]
+        pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
+        return (gx, None, None, *pg)
+
+
+def _convstack_sizes(x, spec):
+    B, C0, F0 = x.shape
+    F_out = F0 - sum((k - 1) * d for _, _, k, _, d in spec)
+    return B, C0, F0, F_out
+
+
+class ConvStackFn(torch.autograd.Function):
+    """(x [B, C0, F0] fp32 contiguous, slope, spec, g_0, v_0, bias_0, g_1, ...) -> out [B, c_out of the last layer, F_out].
+    spec: ((c_in, c_out, k, groups, dilation), ...), one entry per layer (at most 16); the parameters are the layers' weight_g
+    [c_out, 1, 1], weight_v [c_out, c_in/groups, k] and bias [c_out], three per layer.  slope in (0, 1): the LeakyReLU after every
+    layer but the last.  Saved: x, the parameters and the buffer ntm_convstack_forward fills (effective weights, 1/|v|, every
+    layer's output but the last).  The input gradient and the parameter gradients are computed only where needs_input_grad asks
+    for them; no double backward."""
+
+    @staticmethod
+    def forward(ctx, x, slope, spec, *params):
+        spec = tuple(tuple(int(q) for q in s) for s in spec)
+        n = len(spec)
+        if len(params) != 3 * n:
+            raise RuntimeError(f"ConvStackFn: {n} layers need {3 * n} parameters (weight_g, weight_v, bias each), got {len(params)}")
+        if not x.is_cuda:
+            raise RuntimeError("ConvStackFn: HIP device only (no CPU fallback)")
+        x = x.detach().to(torch.float32).contiguous()
+        ps = [p.detach().to(torch.float32).contiguous() for p in params]
+        B, C0, F0, F_out = _convstack_sizes(x, spec)
+        L = _lib.lib()
+        layers = _lib.conv_layers_d(spec)
+        n_saved = int(L.ntm_convstack_saved_floats(B, C0, F0, n, layers))
+        if n_saved < 0:
+            raise _lib.NtmError(f"ntm_convstack_forward refused the sizes: {L.ntm_last_error().decode()}")
+        saved = torch.empty(max(n_saved, 1), device=x.device, dtype=torch.float32)
+        out = torch.empty(B, spec[-1][1], F_out, device=x.device, dtype=torch.float32)
+        _lib.check(L.ntm_convstack_forward(ptr(x), B, C0, F0, float(slope), n, layers, _lib.ptr_array(ps[0::3]),
+                                           _lib.ptr_array(ps[1::3]), _lib.ptr_array(ps[2::3]), ptr(saved), ptr(out),
+                                           _lib.current_stream()), "ntm_convstack_forward")
+        ctx.save_for_backward(x, saved, *ps)
+        ctx.res = (float(slope), spec)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, saved, *ps = ctx.saved_tensors
+        slope, spec = ctx.res
+        n = len(spec)
+        B, C0, F0, _ = _convstack_sizes(x, spec)
+        gout = gout.to(torch.float32).contiguous()
+        L = _lib.lib()
+        layers = _lib.conv_layers_d(spec)
+        ws = torch.empty(max(int(L.ntm_convstack_workspace_floats(B, C0, F0, n, layers)), 1), device=x.device, dtype=torch.float32)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        want = any(ctx.needs_input_grad[3:])
+        grads = [torch.empty_like(p) for p in ps] if want else []
+        arr = (lambda q: _lib.ptr_array(q) if want else None)
+        _lib.check(L.ntm_convstack_backward(ptr(x), B, C0, F0, slope, n, layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]),
+                                            ptr(saved), ptr(gout), ptr(gx), arr(grads[0::3]), arr(grads[1::3]), arr(grads[2::3]),
+                                            ptr(ws), _lib.current_stream()), "ntm_convstack_backward")
         if B == 0:
             gx = None if gx is None else gx.zero_()
             grads = [g.zero_() for g in grads]
