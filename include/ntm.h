@@ -403,6 +403,62 @@ int ntm_convstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, fl
                            float *const *dbias, float *ws, void *stream);
 
 /*
+ * The conv stack of the reference's MelGAN critic (`MelGCrit` / `NLayerDiscriminator`, code/critics.py:18-122), forward and
+ * backward: n_layers weight-normed Conv1d(c_in, c_out, k, groups, stride, pad) with dilation 1, frames following
+ * F[l+1] = floor((F[l] + 2 pad - k) / stride) + 1; effective weight w = g v / |v| (the norm over (c_in/groups, k) per output
+ * channel); LeakyReLU(slope) after every layer but the last.  pad_mode 0: frames outside the input read zero; pad_mode 1: they
+ * read the mirrored sample (torch's ReflectionPad1d(pad) in front of the conv), on the FIRST layer only.  The output of EVERY
+ * layer is returned, and a gradient may arrive at every one of them.  fp32 in, fp32 accumulate on the matrix pipe
+ * (csrc/sconv_kernels.hip).
+ *   x    [B][C0][F0] fp32 contiguous (the waveform: C0 = 1).
+ *   g, v, bias (and dg, dv, dbias): HOST arrays of n_layers DEVICE pointers, as in the ntm_speccrit family.
+ *   outs   HOST array of n_layers DEVICE pointers, outs[l] [B][c_out[l]][F[l+1]]: the post-activation output of layer l (the
+ *        bare conv output for the last).  They are the activations the backward reads: hand it the same tensors, unchanged
+ *        (the slope's side is recovered from the sign: y > 0 <=> pre > 0 because slope > 0, and y == 0 takes the slope).
+ *   gouts  HOST array of n_layers DEVICE pointers in outs' shapes; an entry may be NULL (no gradient arrives at that output),
+ *        at least one is not.  Layers above the highest non-NULL entry get exact zeros in dg, dv and dbias and no kernel.
+ *   saved  ntm_sconvstack_saved_floats(...) floats the forward fills and the backward of the SAME sizes, slope and parameters
+ *        reads: 2 W + R, W = sum c_out (c_in/groups) k (the effective weights in the two layouts the kernels read), R = sum
+ *        c_out (1/|v|).  No activations.
+ *   ws   ntm_sconvstack_workspace_floats(...) floats of device scratch for the backward:
+ *        2 max_l B c_out[l] F[l+1]  +  (layer 0 reflected with pad > 0: B C0 (F0 + 2 pad), else 0)
+ *        +  sum_l nchunk_l nseg_l (W_l + c_out[l]),   W_l = c_out (c_in/groups) k of layer l.
+ *        The chunk rule of the weight gradient, a function of the sizes only, per layer (Fo = F[l+1]):
+ *          seg    = 1024, doubled while ceil(Fo / seg) > 1 and ceil(Fo / seg) W_l > 2^24   (frames per segment)
+ *          nseg   = ceil(Fo / seg)
+ *          per    = max(ceil(B / 32), ceil(2048 / min(Fo, seg)), ceil(B / max(1, floor(2^24 / (nseg W_l))))), at most B
+ *          nchunk = ceil(B / per)   (0 for B == 0)
+ *        so a partial sums at least 2048 frames where the layer has them (a layer of 64 output frames at B = 16 is ONE partial,
+ *        not 16), there are at most 32 stream chunks, and the partials of a layer stay within 2^24 floats (64 MiB) unless one
+ *        partial alone is larger.  One workgroup per (stream chunk, segment) adds its streams in order and its frames in order
+ *        (256 frames from 0 at a time, then to its total) and stores one partial; the partials are added stream chunk major,
+ *        segment minor.
+ *   gx   [B][C0][F0] or NULL: no input gradient (the first layer's data-gradient kernel is skipped).  Under a reflected first
+ *        layer the border terms are added back in a fixed order: interior, left mirror, right mirror.
+ *   dg   NULL: no parameter gradients (dv and dbias are then not looked at).  Gradients are stored, not accumulated.
+ * No floating-point atomics: equal calls give equal bits; a stream's outputs and gx do not depend on the batch it is in.  Refused
+ * (-1 from the two size functions; NTM_EINVAL and a message starting with the function's name from the others) before
+ * anything touches a device: null pointers, n_layers outside [1, 16], a channel count outside [1, 1024], k outside [1, 64],
+ * stride outside [1, 64], pad outside [0, k - 1], a pad_mode other than 0 or 1, pad_mode 1 on a layer other than the first or
+ * with pad >= F0, groups not dividing both channel counts, c_in of a layer not c_out of the one before it (C0 for the first), a
+ * layer with no output frame (F + 2 pad < k), B * C * F >= 2^31 for any tensor of the stack (the padded first input included),
+ * B ceil(F[l+1] / 64) or B stride ceil(ceil((F[l] + pad) / stride) / 64) >= 2^24 for any layer (the workgroups of one launch; a
+ * reflected first layer counts F0 + 2 pad), a
+ * slope outside (0, 1) or NaN (forward and backward), gouts with every entry NULL.  B == 0 returns NTM_OK without looking at the
+ * device pointers (the size functions then count the weights alone).  Additions within ABI version 9.
+ */
+typedef struct { int32_t c_in, c_out, k, groups, stride, pad, pad_mode; } ntm_conv1d_layer_s;   /* pad_mode 0 zeros, 1 reflect */
+int64_t ntm_sconvstack_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers);
+int64_t ntm_sconvstack_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers);
+int ntm_sconvstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                           const ntm_conv1d_layer_s *layers, const float *const *g, const float *const *v,
+                           const float *const *bias, float *saved, float *const *outs, void *stream);
+int ntm_sconvstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                            const ntm_conv1d_layer_s *layers, const float *const *g, const float *const *v,
+                            const float *saved, const float *const *outs, const float *const *gouts, float *gx,
+                            float *const *dg, float *const *dv, float *const *dbias, float *ws, void *stream);
+
+/*
  * "Next" row N2 plumbing: pitched asynchronous copy between (pinned) host memory and the device, rows x
  * width_bytes with independent pitches -- what the segment feeder uses to send a TIME CHUNK of many segments
  * ([B, c0:c1] of a [B,T] batch) so that the copy of chunk c+1 overlaps the GRU launch on chunk c.

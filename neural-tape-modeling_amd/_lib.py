@@ -89,6 +89,12 @@ _SIGNATURES = {
     "ntm_convstack_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
     "ntm_convstack_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ntm_convstack_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the strided conv stack of the MelGAN critic (additions within ABI version 9); layers: ConvLayerS[n]; outs / gouts: host
+    # arrays of n device pointers, one tensor per layer (a gouts entry may be null)
+    "ntm_sconvstack_saved_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
+    "ntm_sconvstack_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
+    "ntm_sconvstack_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ntm_sconvstack_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -113,9 +119,20 @@ def conv_layers_d(spec):
     return (ConvLayerD * len(spec))(*[ConvLayerD(*map(int, s)) for s in spec])
 
 
+class ConvLayerS(ctypes.Structure):
+    """include/ntm.h ntm_conv1d_layer_s: Conv1d(c_in, c_out, k, groups, stride, pad), dilation 1; pad_mode 0 zeros, 1 reflect."""
+    _fields_ = [("c_in", ctypes.c_int32), ("c_out", ctypes.c_int32), ("k", ctypes.c_int32), ("groups", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("pad", ctypes.c_int32), ("pad_mode", ctypes.c_int32)]
+
+
+def conv_layers_s(spec):
+    """((c_in, c_out, k, groups, stride, pad, pad_mode), ...) -> a ConvLayerS array for the ntm_sconvstack entry points."""
+    return (ConvLayerS * len(spec))(*[ConvLayerS(*map(int, s)) for s in spec])
+
+
 def ptr_array(tensors):
-    """Host array of the device pointers of `tensors`, as the ntm_speccrit entry points take their parameters."""
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    """Host array of the device pointers of `tensors`, as the ntm_speccrit entry points take their parameters (None: null)."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 TRAIN_GRAD_FLOATS = 12929   # include/ntm.h NTM_TRAIN_GRAD_FLOATS: w_ih | w_hh | b_ih | b_hh | w_o | b_o of GRU(1, 64) + Linear(64, 1)
 
 # include/ntm_lab.h: libntm_lab.so (older / experimental GRU kernels, diagnostic builds) -- tests and tools only

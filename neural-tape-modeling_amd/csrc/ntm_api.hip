@@ -642,6 +642,96 @@ int ntm_convstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, fl
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_convstack_backward");
 }
 
+// the argument checks the four ntm_sconvstack entry points share, then the plan
+static int sconvstack_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers,
+                            ntm::SConvPlan &p)
+{
+    if (B < 0 || C0 < 1 || F0 < 1) return fail(NTM_EINVAL, w + ": bad size");
+    if (n_layers < 1 || n_layers > ntm::kConvStackMaxLayers) return fail(NTM_EINVAL, w + ": n_layers must lie in [1, 16]");
+    if (!layers) return fail(NTM_EINVAL, w + ": null pointer");
+    int64_t c = C0, F = F0;
+    for (int l = 0; l < n_layers; ++l) {
+        const ntm_conv1d_layer_s &y = layers[l];
+        if (c > 1024 || y.c_in < 1 || y.c_in > 1024 || y.c_out < 1 || y.c_out > 1024)
+            return fail(NTM_EINVAL, w + ": channel counts must lie in [1, 1024]");
+        if (y.k < 1 || y.k > 64) return fail(NTM_EINVAL, w + ": k must lie in [1, 64]");
+        if (y.stride < 1 || y.stride > 64) return fail(NTM_EINVAL, w + ": stride must lie in [1, 64]");
+        if (y.pad < 0 || y.pad > y.k - 1) return fail(NTM_EINVAL, w + ": pad must lie in [0, k - 1]");
+        if (y.pad_mode != 0 && y.pad_mode != 1) return fail(NTM_EINVAL, w + ": pad_mode must be 0 (zeros) or 1 (reflect)");
+        if (y.pad_mode == 1 && l != 0) return fail(NTM_EINVAL, w + ": pad_mode 1 (reflect) is built for the first layer only");
+        if (y.pad_mode == 1 && y.pad >= F) return fail(NTM_EINVAL, w + ": a reflected pad must be smaller than F0");
+        if (y.groups < 1 || y.c_in % y.groups || y.c_out % y.groups) return fail(NTM_EINVAL, w + ": groups must divide both channel counts");
+        if (y.c_in != c) return fail(NTM_EINVAL, w + ": c_in of a layer must be c_out of the layer before it (C0 for the first)");
+        if (F + 2 * (int64_t)y.pad < y.k) return fail(NTM_EINVAL, w + ": a layer has no output frame (F + 2 pad < k)");
+        if (B * c * (F + (l == 0 ? 2 * (int64_t)y.pad : 0)) > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+        // one workgroup of 256 threads per (stream, 64 output frames) forward, per (stream, phase, 64 columns) in the data gradient,
+        // whose columns are the frames of the (padded) input over the stride: both below 2^24 workgroups (2^32 threads per launch)
+        const int64_t Fin = F + (y.pad_mode == 1 ? 2 * (int64_t)y.pad : 0), pad_eff = y.pad_mode == 1 ? 0 : y.pad;
+        F = (F + 2 * (int64_t)y.pad - y.k) / y.stride + 1;
+        c = y.c_out;
+        if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+        const int64_t cols = (Fin - 1 + pad_eff) / y.stride + 1;
+        if (B * ((F + 63) / 64) >= (1 << 24) || B * y.stride * ((cols + 63) / 64) >= (1 << 24))
+            return fail(NTM_EINVAL, w + ": B * stride * ceil(frames / (64 stride)) must be below 2^24 (workgroups of one launch)");
+    }
+    ntm::sconv_plan(p, B, C0, F0, n_layers, layers);
+    return NTM_OK;
+}
+
+int64_t ntm_sconvstack_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers)
+{
+    ntm::SConvPlan p;
+    if (sconvstack_sizes("ntm_sconvstack_saved_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
+    return p.saved_total;
+}
+
+int64_t ntm_sconvstack_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers)
+{
+    ntm::SConvPlan p;
+    if (sconvstack_sizes("ntm_sconvstack_workspace_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
+    return p.ws_total;
+}
+
+int ntm_sconvstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                           const ntm_conv1d_layer_s *layers, const float *const *g, const float *const *v,
+                           const float *const *bias, float *saved, float *const *outs, void *stream)
+{
+    const std::string w("ntm_sconvstack_forward");
+    ntm::SConvPlan p;
+    if (int rc = sconvstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
+    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (B == 0) return NTM_OK;
+    if (!x || !g || !v || !bias || !saved || !outs) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int l = 0; l < n_layers; ++l)
+        if (!g[l] || !v[l] || !bias[l] || !outs[l]) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_sconvstack_forward(p, x, B, slope, g, v, bias, saved, outs, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_sconvstack_forward");
+}
+
+int ntm_sconvstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
+                            const ntm_conv1d_layer_s *layers, const float *const *g, const float *const *v,
+                            const float *saved, const float *const *outs, const float *const *gouts, float *gx,
+                            float *const *dg, float *const *dv, float *const *dbias, float *ws, void *stream)
+{
+    const std::string w("ntm_sconvstack_backward");
+    ntm::SConvPlan p;
+    if (int rc = sconvstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
+    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (B == 0) return NTM_OK;
+    if (!x || !g || !v || !saved || !outs || !gouts || !ws) return fail(NTM_EINVAL, w + ": null pointer");
+    if (dg && (!dv || !dbias)) return fail(NTM_EINVAL, w + ": null pointer (dg, dv and dbias come together)");
+    bool any = false;
+    for (int l = 0; l < n_layers; ++l) {
+        if (!g[l] || !v[l] || !outs[l] || (dg && (!dg[l] || !dv[l] || !dbias[l]))) return fail(NTM_EINVAL, w + ": null pointer");
+        any = any || gouts[l];
+        if (gx && (gx == outs[l] || gx == gouts[l])) return fail(NTM_EINVAL, w + ": gx must not alias x, outs or gouts");
+    }
+    if (!any) return fail(NTM_EINVAL, w + ": every entry of gouts is null (at least one gradient must arrive)");
+    if (gx && gx == x) return fail(NTM_EINVAL, w + ": gx must not alias x, outs or gouts");
+    hipError_t e = ntm::launch_sconvstack_backward(p, x, B, slope, g, v, saved, outs, gouts, gx, dg, dv, dbias, ws, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_sconvstack_backward");
+}
+
 int ntm_copy2d_async(void *dst, int64_t dst_pitch_bytes, const void *src, int64_t src_pitch_bytes, int64_t width_bytes,
                      int64_t rows, int kind, void *stream)
 {

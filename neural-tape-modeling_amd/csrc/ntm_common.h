@@ -148,6 +148,29 @@ hipError_t launch_convstack_forward(const ConvStackPlan &p, const float *x, int6
 hipError_t launch_convstack_backward(const ConvStackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                      const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
                                      float *const *dv, float *const *dbias, float *ws, hipStream_t stream);
+// the strided conv stack of the MelGAN critic (sconv_kernels.hip): stride, zero padding and a reflection pad on the first layer;
+// every layer's output is a tensor of the caller's, so `saved` holds the weights alone
+struct SConvPlan {
+    int n;
+    int c_in[kConvStackMaxLayers], c_out[kConvStackMaxLayers], k[kConvStackMaxLayers], groups[kConvStackMaxLayers],
+        stride[kConvStackMaxLayers], pad[kConvStackMaxLayers], reflect[kConvStackMaxLayers];
+    int64_t F[kConvStackMaxLayers + 1];           // frames entering layer l; F[n]: frames of the last output
+    int64_t w_off[kConvStackMaxLayers], w_total;  // floats of layer l's weights within wF / wB
+    int row0[kConvStackMaxLayers], rows;          // output channels counted through the layers
+    int64_t saved_total;                          // saved: wF | wB | 1/|v|
+    int nchunk[kConvStackMaxLayers], per[kConvStackMaxLayers];   // weight gradient of layer l: chunks of `per` streams ...
+    int64_t seg[kConvStackMaxLayers], nseg[kConvStackMaxLayers]; // ... times segments of `seg` output frames
+    int64_t gz_size, fold_size;                   // ws: gz ping | gz pong | padded gx of a reflected first layer | partials
+    int64_t part_off[kConvStackMaxLayers], bpart_off[kConvStackMaxLayers], ws_total;
+};
+void sconv_plan(SConvPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_s *L);
+hipError_t launch_sconvstack_forward(const SConvPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+                                     const float *const *v, const float *const *bias, float *saved, float *const *outs,
+                                     hipStream_t stream);
+hipError_t launch_sconvstack_backward(const SConvPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+                                      const float *const *v, const float *saved, const float *const *outs,
+                                      const float *const *gouts, float *gx, float *const *dg, float *const *dv,
+                                      float *const *dbias, float *ws, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
                             int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm

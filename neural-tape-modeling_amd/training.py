@@ -22,6 +22,9 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
   * ConvStackFn: the dilated conv stack of the time-domain critic (critics.DilatedConvDisc: weight-normed Conv1d layers with a
     dilation each and LeakyReLU(slope) between them, on the raw waveform) as ONE graph node: forward = ntm_convstack_forward,
     backward = ntm_convstack_backward, with the same rules as SpecCritFn.
+  * StridedConvStackFn: the strided, grouped, padded conv stack of the MelGAN critic (critics.NLayerDiscriminator) as ONE graph
+    node that returns EVERY layer's output: forward = ntm_sconvstack_forward, backward = ntm_sconvstack_backward, which takes a
+    gradient (or none) at each of them.
   * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
     replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
     launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
@@ -376,5 +379,78 @@ class ConvStackFn(torch.autograd.Function):
         if B == 0:
             gx = None if gx is None else gx.zero_()
             grads = [g.zero_() for g in grads]
+        pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
+        return (gx, None, None, *pg)
+
+
+def _sconvstack_frames(F0, spec):
+    """Frames entering every layer and leaving the last: F[l+1] = floor((F[l] + 2 pad - k) / stride) + 1."""
+    F = [int(F0)]
+    for _, _, k, _, stride, pad, _ in spec:
+        F.append((F[-1] + 2 * pad - k) // stride + 1)
+    return F
+
+
+class StridedConvStackFn(torch.autograd.Function):
+    """(x [B, C0, F0] fp32 contiguous, slope, spec, g_0, v_0, bias_0, g_1, ...) -> a tuple of n tensors, the output of every layer:
+    [B, c_out[l], F[l+1]], post-activation for all but the last.  spec: ((c_in, c_out, k, groups, stride, pad, pad_mode), ...), one
+    entry per layer (at most 16), pad_mode 0 zeros, 1 reflect (first layer only); the parameters are the layers' weight_g
+    [c_out, 1, 1], weight_v [c_out, c_in/groups, k] and bias [c_out], three per layer.  slope in (0, 1): the LeakyReLU after every
+    layer but the last.  Saved: x, the parameters, the buffer ntm_sconvstack_forward fills (effective weights, 1/|v|) and the
+    OUTPUTS themselves -- they are the activations the backward reads, so an in-place edit of a returned feature before backward
+    raises torch's version error.  An output no gradient arrives at is a NULL entry of gouts; the input gradient and the parameter
+    gradients are computed only where needs_input_grad asks for them; no double backward."""
+
+    @staticmethod
+    def forward(ctx, x, slope, spec, *params):
+        spec = tuple(tuple(int(q) for q in s) for s in spec)
+        n = len(spec)
+        if len(params) != 3 * n:
+            raise RuntimeError(f"StridedConvStackFn: {n} layers need {3 * n} parameters (weight_g, weight_v, bias each), got {len(params)}")
+        if not x.is_cuda:
+            raise RuntimeError("StridedConvStackFn: HIP device only (no CPU fallback)")
+        x = x.detach().to(torch.float32).contiguous()
+        ps = [p.detach().to(torch.float32).contiguous() for p in params]
+        B, C0, F0 = x.shape
+        L = _lib.lib()
+        layers = _lib.conv_layers_s(spec)
+        n_saved = int(L.ntm_sconvstack_saved_floats(B, C0, F0, n, layers))
+        if n_saved < 0:
+            raise _lib.NtmError(f"ntm_sconvstack_forward refused the sizes: {L.ntm_last_error().decode()}")
+        F = _sconvstack_frames(F0, spec)
+        saved = torch.empty(max(n_saved, 1), device=x.device, dtype=torch.float32)
+        outs = [torch.empty(B, spec[l][1], F[l + 1], device=x.device, dtype=torch.float32) for l in range(n)]
+        _lib.check(L.ntm_sconvstack_forward(ptr(x), B, C0, F0, float(slope), n, layers, _lib.ptr_array(ps[0::3]),
+                                            _lib.ptr_array(ps[1::3]), _lib.ptr_array(ps[2::3]), ptr(saved), _lib.ptr_array(outs),
+                                            _lib.current_stream()), "ntm_sconvstack_forward")
+        ctx.save_for_backward(x, saved, *ps, *outs)
+        ctx.res = (float(slope), spec)
+        ctx.set_materialize_grads(False)        # an output no gradient arrives at stays None: a NULL gouts entry, no zero tensor
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gouts):
+        slope, spec = ctx.res
+        n = len(spec)
+        x, saved, *rest = ctx.saved_tensors
+        ps, outs = rest[:3 * n], rest[3 * n:]
+        B, C0, F0 = x.shape
+        gouts = [None if g is None else g.to(torch.float32).contiguous() for g in gouts]
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        want = any(ctx.needs_input_grad[3:])
+        grads = [torch.empty_like(p) for p in ps] if want else []
+        if all(g is None for g in gouts) or B == 0:
+            gx = None if gx is None else gx.zero_()
+            grads = [g.zero_() for g in grads]
+        else:
+            L = _lib.lib()
+            layers = _lib.conv_layers_s(spec)
+            ws = torch.empty(max(int(L.ntm_sconvstack_workspace_floats(B, C0, F0, n, layers)), 1), device=x.device, dtype=torch.float32)
+            arr = (lambda q: _lib.ptr_array(q) if want else None)
+            _lib.check(L.ntm_sconvstack_backward(ptr(x), B, C0, F0, slope, n, layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]),
+                                                 ptr(saved), _lib.ptr_array(outs), _lib.ptr_array(gouts), ptr(gx), arr(grads[0::3]),
+                                                 arr(grads[1::3]), arr(grads[2::3]), ptr(ws), _lib.current_stream()),
+                       "ntm_sconvstack_backward")
         pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
         return (gx, None, None, *pg)
