@@ -693,6 +693,50 @@ int ntm_diffdel_stream_block(const float *w_ih, const float *w_hh, const float *
                              int64_t x_stride_b, int64_t d_stride_b, int64_t y_stride_b, float *h_state, float *ring, int64_t C,
                              int64_t *pos, int D, int warmup, int32_t *err_flag, void *stream);
 
+/*
+ * ---- The hinge / mean heads of the adversarial losses (additions within ABI version 9): what code/critics.py's train_crit and
+ * train_gen evaluate on the K outputs of a critic, as one node.  outs: host array of K device pointers, output k a contiguous
+ * fp32 tensor of `rows` rows of elems[k] floats (elems: host array); K in [1, NTM_ADV_HEAD_MAX_K], rows and every elems[k] >= 1.
+ *   NTM_ADV_HEAD_CRIT  rows [0, n_fake) are fake with the terms relu(fp32(1 + o)), rows [n_fake, rows) real with
+ *                      relu(fp32(1 - o)); 0 < n_fake < rows; every half of every output has a mean of its own and
+ *                          loss = sum_k mean(fake terms of k) + sum_k mean(real terms of k);
+ *   NTM_ADV_HEAD_GEN   loss = sum_k -mean(o_k) over all rows (n_fake is not read).
+ * The terms are formed in fp32 and summed in fp64 in a fixed order: chunks of NTM_ADV_HEAD_CHUNK terms over workgroups, then
+ * the chunk sums in a second, single-workgroup launch.  No atomics: equal calls give equal bits.  Every mean is rounded to fp32
+ * once and the means are added in fp32 in the order written above, as the reference adds them.
+ * ws: device workspace of ws_doubles >= (K or, in the critic mode, 2 K) * ceil(longest half in floats / NTM_ADV_HEAD_CHUNK)
+ * doubles; loss: one device float.  Two launches, nothing else.
+ */
+#define NTM_ADV_HEAD_CRIT 0
+#define NTM_ADV_HEAD_GEN 1
+#define NTM_ADV_HEAD_MAX_K 8
+#define NTM_ADV_HEAD_CHUNK 4096
+int ntm_adv_head_forward(const float *const *outs, const int64_t *elems, int K, int64_t rows, int64_t n_fake, int mode, double *ws,
+                         int64_t ws_doubles, float *loss, void *stream);
+
+/*
+ * Its adjoint in one launch: grads[k] (host array of K device pointers, each of output k's size, all written) receives
+ *     fake rows  +c_k [fp32(1 + o) > 0],   real rows  -c_k' [fp32(1 - o) > 0],   generator mode  -c_k,
+ * with c = gout[0] * (1.0f / fp32(floats of that half)): the arithmetic of torch's autograd on the reference's expression (its
+ * mean divides by a host scalar, which torch evaluates as a product with the fp32 reciprocal), so the gradients are its bits;
+ * the mask is torch's relu mask, zero at a term of exactly 0 and one at a NaN.  gout: the upstream gradient, one device float.
+ * grads[k] must not alias outs[k].
+ */
+int ntm_adv_head_backward(const float *const *outs, const int64_t *elems, int K, int64_t rows, int64_t n_fake, int mode,
+                          const float *gout, float *const *grads, void *stream);
+
+/*
+ * ntm_delay_forward with the delays in float64 (an addition within ABI version 9): x, y [B,T] fp32, d [B,T] fp64 in samples,
+ * dl_state [B,D] in / out, warmup and err_flag as there (a d > D or NaN raises the sticky flag and leaves y and dl_state of that
+ * call unspecified / untouched respectively).  The weights 1 - |m - d| of the two taps and their products with the samples are
+ * formed in float64, added in the reference's order and rounded to float32 once: what the reference's delay line returns, cast
+ * to float32, when its data set hands float64 trajectories (code/train-adversarial.py with VADataset(double=True)).  A float32
+ * delay of several hundred samples is 3e-5 to 6e-5 samples wide, which on a noise-like signal is 1e-5 at the output.
+ * B <= 65535.  Two launches (the interpolation, one sample per thread; the buffer update of ntm_delay_forward).
+ */
+int ntm_delay_forward_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
+                          int32_t *err_flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

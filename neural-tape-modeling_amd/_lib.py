@@ -95,7 +95,15 @@ _SIGNATURES = {
     "ntm_sconvstack_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
     "ntm_sconvstack_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ntm_sconvstack_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the hinge / mean heads of the adversarial losses (additions within ABI version 9); outs / grads: host arrays of K device
+    # pointers (ptr_array), elems: host int64 array (i64_array)
+    "ntm_adv_head_forward": (_int, [_vp, _vp, _int, _i64, _i64, _int, _vp, _i64, _vp, _vp]),
+    "ntm_adv_head_backward": (_int, [_vp, _vp, _int, _i64, _i64, _int, _vp, _vp, _vp]),
+    # the delay line with float64 delays (an addition within ABI version 9): ntm_delay_forward's arguments, d a double pointer
+    "ntm_delay_forward_f64": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _vp, _vp]),
 }
+ADV_HEAD_MODES = {"crit": 0, "gen": 1}      # include/ntm.h NTM_ADV_HEAD_CRIT / NTM_ADV_HEAD_GEN
+ADV_HEAD_MAX_K, ADV_HEAD_CHUNK = 8, 4096    # include/ntm.h NTM_ADV_HEAD_MAX_K, NTM_ADV_HEAD_CHUNK
 
 
 class ConvLayer(ctypes.Structure):
@@ -133,6 +141,13 @@ def conv_layers_s(spec):
 def ptr_array(tensors):
     """Host array of the device pointers of `tensors`, as the ntm_speccrit entry points take their parameters (None: null)."""
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def i64_array(values):
+    """Host int64 array, as the ntm_adv_head entry points take the row lengths of their outputs."""
+    return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
+
+
 TRAIN_GRAD_FLOATS = 12929   # include/ntm.h NTM_TRAIN_GRAD_FLOATS: w_ih | w_hh | b_ih | b_hh | w_o | b_o of GRU(1, 64) + Linear(64, 1)
 
 # include/ntm_lab.h: libntm_lab.so (older / experimental GRU kernels, diagnostic builds) -- tests and tools only

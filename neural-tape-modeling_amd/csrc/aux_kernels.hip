@@ -159,6 +159,57 @@ hipError_t launch_delay(const float *x, const float *d, float *y, int64_t B, int
     return hipGetLastError();
 }
 
+// The same interpolation for delays given in float64 (ntm_delay_forward_f64): what the reference computes when its data set
+// hands float64 trajectories (VADataset(double=True), code/train-adversarial.py) -- the weights 1 - |m - d| and the two
+// products in float64, added in the reference's order (m = k + 1, then m = k), rounded to float32 once.  One sample per
+// thread, grid (ceil(T / 256), B); the validation pass of the adversarial loop is its only caller, so it is the plain form.
+__global__ __launch_bounds__(256) void delay_apply_f64_kernel(const float *x, const double *d, float *y, int64_t T, const float *buf,
+                                                              int D, int warmup, int32_t *flag)
+{
+#pragma clang fp contract(off)   // products and the sum round separately, as in the reference
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (n >= T) return;
+    if (flag && *flag) return;                       // sticky: an earlier violation froze this state
+    const float *xb = x + b * T, *bb = buf + b * (int64_t)D;
+    if (warmup) {
+        y[b * T + n] = xb[n];
+        return;
+    }
+    const double dn = d[b * T + n];
+    if (!(dn <= (double)D)) {                        // NaN too: the reference's assert (code/model.py:284)
+        if (flag) *flag = 1;
+        return;
+    }
+    const double kf = floor(dn);
+    double acc = 0.0;
+#pragma unroll
+    for (int tap = 1; tap >= 0; --tap) {
+        const double mf = kf + (double)tap;
+        if (mf < 0.0 || mf > (double)D) continue;
+        const double w = 1.0 - fabs(mf - dn);
+        if (!(w > 0.0)) continue;
+        const int64_t src = n - (int64_t)mf;
+        const double prod = w * (double)(src >= 0 ? xb[src] : bb[D + src]);
+        acc = acc + prod;
+    }
+    y[b * T + n] = (float)acc;
+}
+
+hipError_t launch_delay_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
+                            int32_t *err_flag, hipStream_t stream)
+{
+    if (B == 0 || T == 0) return hipSuccess;
+    const int64_t tiles = (T + 255) / 256;
+    if (tiles > 0x7fffffffLL || B > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(delay_apply_f64_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), 0, stream, x, d, y, T, dl_state, D,
+                       warmup, err_flag);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (D > 0)
+        hipLaunchKernelGGL(delay_update_kernel, dim3((unsigned)B), dim3(DU_THREADS), 0, stream, x, dl_state, T, D, err_flag);
+    return hipGetLastError();
+}
+
 // the buffer update alone: behind the fused DiffDelRNN kernel (gru_mfma2.hip, FUSE), which interpolates but leaves the
 // carried buffer to this launch -- it has to see the range flag of EVERY workgroup of that kernel
 hipError_t launch_delay_update(const float *x, int64_t B, int64_t T, float *dl_state, int D, const int32_t *err_flag,

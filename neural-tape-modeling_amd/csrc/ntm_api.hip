@@ -230,6 +230,18 @@ int ntm_delay_forward(const float *x, const float *d, float *y, int64_t B, int64
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_delay_forward");
 }
 
+int ntm_delay_forward_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
+                          int32_t *err_flag, void *stream)
+{
+    if (B < 0 || T < 0 || D < 0) return fail(NTM_EINVAL, "ntm_delay_forward_f64: negative size");
+    if (B == 0 || T == 0) return NTM_OK;
+    if (B > 65535) return fail(NTM_EINVAL, "ntm_delay_forward_f64: at most 65535 streams per call");
+    if (!x || !d || !y || (D > 0 && !dl_state)) return fail(NTM_EINVAL, "ntm_delay_forward_f64: null pointer");
+    if (x == y) return fail(NTM_EINVAL, "ntm_delay_forward_f64: y must not alias x");
+    hipError_t e = ntm::launch_delay_f64(x, d, y, B, T, dl_state, D, warmup, err_flag, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_delay_forward_f64");
+}
+
 // ntm_diffdel_gru_forward[_ex] (ls == NULL) and ntm_diffdel_gru_forward_esr / _losses share this body
 static int diffdel_impl(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o, int H,
                         const float *x, const float *d, float *y, float *pre_d, int64_t B, int64_t T, float *h_state,
@@ -1190,6 +1202,62 @@ int ntm_diffdel_stream_block(const float *w_ih, const float *w_hh, const float *
     sa.mask = C - 1;
     hipError_t e = ntm::launch_diffdel_stream(sa, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_diffdel_stream_block");
+}
+
+// the argument checks the two ntm_adv_head entry points share, then the kernels' record (a.g is left null)
+static int adv_head_args(const std::string &w, const float *const *outs, const int64_t *elems, int K, int64_t rows, int64_t n_fake,
+                         int mode, ntm::AdvHeadArgs &a)
+{
+    if (mode != NTM_ADV_HEAD_CRIT && mode != NTM_ADV_HEAD_GEN) return fail(NTM_EINVAL, w + ": mode must be NTM_ADV_HEAD_CRIT or NTM_ADV_HEAD_GEN");
+    if (K < 1 || K > NTM_ADV_HEAD_MAX_K) return fail(NTM_EINVAL, w + ": K must lie in [1, 8]");
+    if (rows < 1) return fail(NTM_EINVAL, w + ": bad size");
+    if (mode == NTM_ADV_HEAD_CRIT && (n_fake < 1 || n_fake >= rows))
+        return fail(NTM_EINVAL, w + ": n_fake must lie in [1, rows - 1] (each half has a mean of its own)");
+    if (!outs || !elems) return fail(NTM_EINVAL, w + ": null pointer");
+    a = ntm::AdvHeadArgs{};
+    a.rows = rows;
+    a.n_fake = mode == NTM_ADV_HEAD_CRIT ? n_fake : 0;
+    a.K = K;
+    a.mode = mode;
+    for (int k = 0; k < K; ++k) {
+        if (elems[k] < 1) return fail(NTM_EINVAL, w + ": bad size");
+        if (elems[k] > (int64_t)1 << 40 || rows > (int64_t)1 << 40 || rows * elems[k] > (int64_t)1 << 40)
+            return fail(NTM_EINVAL, w + ": an output must hold at most 2^40 floats");
+        if (!outs[k]) return fail(NTM_EINVAL, w + ": null pointer");
+        a.o[k] = outs[k];
+        a.elems[k] = elems[k];
+    }
+    if (ntm::adv_head_chunks(a) > 0x7fffffff) return fail(NTM_EINVAL, w + ": more than 2^31 - 1 chunks in one half");
+    return NTM_OK;
+}
+
+int ntm_adv_head_forward(const float *const *outs, const int64_t *elems, int K, int64_t rows, int64_t n_fake, int mode, double *ws,
+                         int64_t ws_doubles, float *loss, void *stream)
+{
+    const std::string w("ntm_adv_head_forward");
+    ntm::AdvHeadArgs a;
+    if (int rc = adv_head_args(w, outs, elems, K, rows, n_fake, mode, a)) return rc;
+    if (!ws || !loss) return fail(NTM_EINVAL, w + ": null pointer");
+    if (ws_doubles < (mode == NTM_ADV_HEAD_GEN ? K : 2 * K) * ntm::adv_head_chunks(a))
+        return fail(NTM_EINVAL, w + ": the workspace is smaller than segments * chunks doubles");
+    hipError_t e = ntm::launch_adv_head_forward(a, ws, loss, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_adv_head_forward");
+}
+
+int ntm_adv_head_backward(const float *const *outs, const int64_t *elems, int K, int64_t rows, int64_t n_fake, int mode,
+                          const float *gout, float *const *grads, void *stream)
+{
+    const std::string w("ntm_adv_head_backward");
+    ntm::AdvHeadArgs a;
+    if (int rc = adv_head_args(w, outs, elems, K, rows, n_fake, mode, a)) return rc;
+    if (!gout || !grads) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int k = 0; k < K; ++k) {
+        if (!grads[k]) return fail(NTM_EINVAL, w + ": null pointer");
+        if (grads[k] == outs[k]) return fail(NTM_EINVAL, w + ": grads[k] must not alias outs[k]");
+        a.g[k] = grads[k];
+    }
+    hipError_t e = ntm::launch_adv_head_backward(a, gout, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_adv_head_backward");
 }
 
 }  // extern "C"

@@ -171,6 +171,19 @@ hipError_t launch_sconvstack_backward(const SConvPlan &p, const float *x, int64_
                                       const float *const *v, const float *saved, const float *const *outs,
                                       const float *const *gouts, float *gx, float *const *dg, float *const *dv,
                                       float *const *dbias, float *ws, hipStream_t stream);
+// the hinge / mean heads of the adversarial losses (advhead_kernels.hip): the K outputs, their gradients (backward only) and sizes
+struct AdvHeadArgs {
+    const float *o[NTM_ADV_HEAD_MAX_K];
+    float *g[NTM_ADV_HEAD_MAX_K];
+    int64_t elems[NTM_ADV_HEAD_MAX_K];       // floats per row of output k
+    int64_t rows, n_fake;
+    int K, mode;
+};
+int64_t adv_head_chunks(const AdvHeadArgs &a);   // chunks of the longest half: the first grid dimension, the row length of ws
+hipError_t launch_adv_head_forward(const AdvHeadArgs &a, double *ws, float *loss, hipStream_t stream);
+hipError_t launch_adv_head_backward(const AdvHeadArgs &a, const float *gout, hipStream_t stream);
+hipError_t launch_delay_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
+                            int32_t *err_flag, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,
                             int D, int warmup, int force_scan, hipStream_t stream);
 }  // namespace ntm

@@ -535,6 +535,18 @@ class TimeVaryingDelayLine(torch.nn.Module):
         self._launched()
         return y
 
+    def _run_f64(self, xbt, d64, warmup):
+        """_run with the delays in float64 [B,T] (ntm_delay_forward_f64): the weights and products in float64, as the reference
+        forms them from a float64 trajectory."""
+        B, T = xbt.shape
+        D = self._prepare(B, xbt.device)
+        y = torch.empty_like(xbt)
+        rc = _lib.lib().ntm_delay_forward_f64(ptr(xbt), ptr(d64), ptr(y), B, T, ptr(self.buffer), D, int(bool(warmup)),
+                                              ptr(self._err), _lib.current_stream())
+        _lib.check(rc, "ntm_delay_forward_f64")
+        self._launched()
+        return y
+
     @torch.no_grad()
     def forward(self, x, dt, warmup=False):
         """x, dt (N,1,T), dt in samples -> y (N,1,T) (code/model.py:269-320)."""
@@ -669,6 +681,28 @@ class DiffDelRNN(_GRUHead):
         y = self.diffdel._run(pre, dbt, warmup)
         if _events:
             _events[2].record()
+        return y.view(B, 1, T), pre.view(B, 1, T)
+
+    @torch.no_grad()
+    def forward_f64_delays(self, x, del_traj, warmup=False):
+        """forward(x, del_traj) without grad for a FLOAT64 delay trajectory (N,1,T) in samples, kept in float64 down to the
+        interpolation weights (forward() rounds the delays to float32 first, which at several hundred samples of delay moves a
+        noise-like output by 1e-5): the GRU launch of forward(), then ntm_delay_forward_f64.  -> (y, pre_d) float32; pre_d and
+        the hidden state are forward()'s bits, the state is carried the same way.  What the reference computes when its data
+        set hands float64 trajectories (the validation pass of code/train-adversarial.py)."""
+        xbt = _as_bt(x, "DiffDelRNN.forward_f64_delays")
+        if del_traj.dim() != 3 or del_traj.shape[1] != 1 or del_traj.dtype != torch.float64:
+            raise RuntimeError(f"DiffDelRNN.forward_f64_delays: a float64 (N, 1, T) delay trajectory, got {tuple(del_traj.shape)} {del_traj.dtype}")
+        _require_hip(del_traj, "DiffDelRNN.forward_f64_delays")
+        d64 = del_traj.contiguous().view(del_traj.shape[0], del_traj.shape[2])
+        if d64.shape != xbt.shape:
+            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+        B, T = xbt.shape
+        pre = torch.empty_like(xbt)
+        self._launch(xbt, pre)
+        if self.skip:
+            pre += xbt
+        y = self.diffdel._run_f64(pre, d64, warmup)
         return y.view(B, 1, T), pre.view(B, 1, T)
 
     @torch.no_grad()

@@ -25,6 +25,9 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
   * StridedConvStackFn: the strided, grouped, padded conv stack of the MelGAN critic (critics.NLayerDiscriminator) as ONE graph
     node that returns EVERY layer's output: forward = ntm_sconvstack_forward, backward = ntm_sconvstack_backward, which takes a
     gradient (or none) at each of them.
+  * AdvHeadFn: the hinge / mean losses of the adversarial run on the K outputs of a critic (train_crit / train_gen of
+    code/critics.py) as ONE graph node on the kernels of csrc/advhead_kernels.hip: forward = ntm_adv_head_forward, backward =
+    ntm_adv_head_backward.
   * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
     replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
     launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
@@ -454,3 +457,56 @@ class StridedConvStackFn(torch.autograd.Function):
                        "ntm_sconvstack_backward")
         pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
         return (gx, None, None, *pg)
+
+
+class AdvHeadFn(torch.autograd.Function):
+    """(mode, n_fake, *outs) -> the adversarial loss on the K outputs of a critic as ONE graph node, a 0-dim float32 tensor:
+    mode "crit"  sum_k relu(1 + o_k[:n_fake]).mean() + sum_k relu(1 - o_k[n_fake:]).mean()   (train_crit, code/critics.py:47-58),
+    mode "gen"   sum_k -o_k.mean()                                                          (train_gen, :60-68; n_fake is not read).
+    outs: K (at most 8) float32 tensors [rows, ...] of one row count (`.contiguous()` is called on the others): a MultiSpecCrit's
+    list, [D] of a DilatedConvDisc, [scale[-1] for scale in D] of a MelGCrit.  forward = ntm_adv_head_forward (the terms in fp32 as
+    torch forms them, fixed-order fp64 sums, every mean rounded to fp32 once, the means added in fp32 in the reference's order;
+    two launches), backward = ntm_adv_head_backward (one launch writes all K gradients with the bits of torch's autograd on the
+    reference's expression; a None upstream gradient writes nothing).  No atomics; no double backward."""
+
+    @staticmethod
+    def forward(ctx, mode, n_fake, *outs):
+        if mode not in _lib.ADV_HEAD_MODES:
+            raise RuntimeError(f"AdvHeadFn: mode {mode!r}; built: 'crit' and 'gen'")
+        K = len(outs)
+        if not 1 <= K <= _lib.ADV_HEAD_MAX_K:
+            raise RuntimeError(f"AdvHeadFn: {K} outputs; built: 1 to {_lib.ADV_HEAD_MAX_K}")
+        if not all(o.is_cuda for o in outs):
+            raise RuntimeError("AdvHeadFn: HIP device only (no CPU fallback)")
+        outs = [o.detach().to(torch.float32).contiguous() for o in outs]
+        rows = outs[0].shape[0] if outs[0].dim() else 0
+        if any(o.dim() < 1 or o.shape[0] != rows for o in outs):
+            raise RuntimeError(f"AdvHeadFn: the outputs must share their first dimension, got {[tuple(o.shape) for o in outs]}")
+        n_fake = int(n_fake) if mode == "crit" else 0
+        elems = [o.numel() // max(rows, 1) for o in outs]
+        segs = K if mode == "gen" else 2 * K
+        longest = max(max(n_fake, rows - n_fake) * e for e in elems)
+        n_ws = segs * max(-(-longest // _lib.ADV_HEAD_CHUNK), 1)
+        ws = torch.empty(n_ws, device=outs[0].device, dtype=torch.float64)
+        loss = torch.empty((), device=outs[0].device, dtype=torch.float32)
+        _lib.check(_lib.lib().ntm_adv_head_forward(_lib.ptr_array(outs), _lib.i64_array(elems), K, rows, n_fake,
+                                                   _lib.ADV_HEAD_MODES[mode], ptr(ws), n_ws, ptr(loss), _lib.current_stream()),
+                   "ntm_adv_head_forward")
+        ctx.save_for_backward(*outs)
+        ctx.res = (mode, n_fake, rows, elems)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        outs = ctx.saved_tensors
+        if gout is None:
+            return (None, None) + (None,) * len(outs)
+        mode, n_fake, rows, elems = ctx.res
+        g = gout.detach().to(device=outs[0].device, dtype=torch.float32).reshape(1).contiguous()
+        grads = [torch.empty_like(o) for o in outs]
+        _lib.check(_lib.lib().ntm_adv_head_backward(_lib.ptr_array(outs), _lib.i64_array(elems), len(outs), rows, n_fake,
+                                                    _lib.ADV_HEAD_MODES[mode], ptr(g), _lib.ptr_array(grads), _lib.current_stream()),
+                   "ntm_adv_head_backward")
+        return (None, None, *[gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:])])
