@@ -737,6 +737,74 @@ int ntm_adv_head_backward(const float *const *outs, const int64_t *elems, int K,
 int ntm_delay_forward_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
                           int32_t *err_flag, void *stream);
 
+/*
+ * The diffusion generators (`UNet1D`, code/networks/unet_1d.py, under `DiffusionGenerator`, code/model.py:656-891): the network's
+ * fused blocks and the sampler's step, inference only (csrc/unet_kernels.hip).  Additions within ABI version 9.
+ *
+ * ntm_unet_resblock_forward: one ResnetBlock(bias=False, use_norm=False) in one launch (two in the tiled form):
+ *     x = film * [src0 from frame off0 | src1 from frame off1]       the concatenation is never materialised; off0 is
+ *                                                                    CropConcatBlock's centre crop
+ *     y = W_first gelu(x);  n_layers times  y <- (y + Conv1d_{k = 5, dilation 2^l, "same", zeros}(gelu(y))) / sqrt 2
+ *     out = (y + W_res x) / sqrt 2                                   W_res == NULL: the identity (c0 + c1 == c_out)
+ *   src0 [B][c0][T0], src1 [B][c1][T1] (c1 == 0: NULL), out [B][c_out][T] fp32 contiguous; T frames are read from each source.
+ *   init != 0: src0 is the waveform [B][1][T0] and its c0 channels are Conv1d(1, c0, 5, "same", zeros) of it with
+ *     init_w [c0][5], computed on the fly (the network's init_conv).
+ *   film [1 or B][c0 + c1] with film_stride floats between streams (0: one vector for all); w_first [c_out][c0 + c1];
+ *   w_gated [n_layers][c_out][c_out][5]; w_res [c_out][c0 + c1] or NULL.  gelu is the exact (erf) one.
+ *   form NTM_UNET_AUTO: the whole form for T <= NTM_UNET_WHOLE_MAX_T, else the tiled one; _WHOLE / _TILED force one.
+ *     whole: one workgroup per stream holds the signal, no halo, one launch.
+ *     tiled: windows of 1024 frames = a tile of NTM_UNET_TILE and a halo of 256 a side; a run of layers is one launch while
+ *       2 sum(dilation) <= 256: layers 0-6 and layer 7 for the eight dilations 1 .. 128.  ws holds y between the runs:
+ *       ntm_unet_resblock_workspace_floats(B, blk) floats (0 for one launch; -1 on arguments the forward refuses).
+ *   Frames outside [0, T) are zero at every layer, as the reference's per-layer padding makes them.
+ *   Contractions on v_mfma_f32_16x16x4_f32, fp32 accumulate.  Refused (NTM_EINVAL, a message starting with the function's
+ *   name) before anything touches a device: null pointers, B outside [0, 65535], c0 < 1, c1 < 0, c0 + c1 > 32, c_out outside
+ *   [1, 16], n_layers outside [1, 8], T < 1, a source shorter than off + T or a negative off, 32 T0 or 32 T1 >= 2^31, an unknown
+ *   form, the whole form with T > NTM_UNET_WHOLE_MAX_T, film_stride neither 0 nor >= c0 + c1, W_res == NULL with
+ *   c0 + c1 != c_out, out aliasing a source.  B == 0 returns NTM_OK.
+ *
+ * ntm_unet_down_combine: Downsample(S) of x [B][C][F] and pyr [B][1][F] by the polyphase FIR ker [taps], taps == 2 width + S
+ *   (the module's `resample.kernel` buffer), then CombinerDown: x_out [B][C][Fo] = (wc[c] pyr_d + x_d) / sqrt 2, pyr_out
+ *   [B][1][Fo] = pyr_d, Fo = ceil(F / S).
+ * ntm_unet_up_combine: CombinerUp, p = sum_c wc[c] x[c] on [B][C][F], with a pyramid pyr [B][1][pyr_T >= F] p = (pyr[:F] + p) /
+ *   sqrt 2; then Upsample(S) of x and p by the S phases ker [S][taps], taps == 2 width + 1: x_out [B][C][S F], pyr_out [B][1][S F].
+ *   S == 1 (ker NULL, width == taps == 0, x_out NULL): the combiner alone, pyr_out [B][1][F].
+ * ntm_unet_upsample: the upsampler alone on x [B][F] -> out [B][S F] (the sampler's 100 Hz -> 44.1 kHz resampler: S = 441).
+ *   Refused: null pointers, B outside [0, 65535], C outside [1, 32], F < 1, S outside [1, 1024], width < 0, taps > 64 or not as
+ *   stated, S F or C S F >= 2^31, pyr_T < F.  One launch each.
+ *
+ * ntm_edm_pre / ntm_edm_post: the sampler's step around the network on [B][T] fp32, every product and sum rounded on its own in
+ *   the reference's order (code/model.py:797-837, 764-769):
+ *     pre:  z' = z + eps_scale (eps snoise)            eps != NULL (the Schurn branch)
+ *           z' = mask (x_out + n sigma0) + (1 - mask) z'     mask != NULL (outpainting; mask_stride 0: one row for all, else T)
+ *           z_out = z', net_in = cin z'
+ *     post: x0 = cskip z + cout F;  out = z - k ((x0 - z) / b2)        b2 = sigma^2, k = (sigma_next - sigma) sigma
+ *   Refused: null z / z_out / net_in / F / out, mask without x_out and n, negative sizes, mask_stride neither 0 nor T.
+ */
+#define NTM_UNET_WHOLE_MAX_T 1024
+#define NTM_UNET_TILE 512
+#define NTM_UNET_AUTO 0
+#define NTM_UNET_WHOLE 1
+#define NTM_UNET_TILED 2
+typedef struct {
+    int32_t c0, c1, c_out, n_layers;
+    int64_t T, T0, off0, T1, off1;
+    int32_t init, form;
+} ntm_unet_block;
+int64_t ntm_unet_resblock_workspace_floats(int64_t B, const ntm_unet_block *blk);
+int ntm_unet_resblock_forward(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                              const float *w_first, const float *w_gated, const float *w_res, int64_t B, const ntm_unet_block *blk,
+                              float *ws, float *out, void *stream);
+int ntm_unet_down_combine(const float *x, const float *pyr, const float *ker, const float *wc, int64_t B, int C, int64_t F, int S,
+                          int width, int taps, float *x_out, float *pyr_out, void *stream);
+int ntm_unet_up_combine(const float *x, const float *pyr, int64_t pyr_T, const float *ker, const float *wc, int64_t B, int C,
+                        int64_t F, int S, int width, int taps, float *x_out, float *pyr_out, void *stream);
+int ntm_unet_upsample(const float *x, const float *ker, int64_t B, int64_t F, int S, int width, int taps, float *out, void *stream);
+int ntm_edm_pre(const float *z, const float *eps, float eps_scale, float snoise, const float *mask, int64_t mask_stride,
+                const float *x_out, const float *n, float sigma0, float cin, int64_t B, int64_t T, float *z_out, float *net_in,
+                void *stream);
+int ntm_edm_post(const float *z, const float *F, float cskip, float cout, float b2, float k, int64_t N, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

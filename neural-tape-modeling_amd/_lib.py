@@ -101,6 +101,14 @@ _SIGNATURES = {
     "ntm_adv_head_backward": (_int, [_vp, _vp, _int, _i64, _i64, _int, _vp, _vp, _vp]),
     # the delay line with float64 delays (an addition within ABI version 9): ntm_delay_forward's arguments, d a double pointer
     "ntm_delay_forward_f64": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _int, _int, _vp, _vp]),
+    # the diffusion generators (additions within ABI version 9): blk is a pointer to diffusion.BlockSpec (ntm_unet_block)
+    "ntm_unet_resblock_workspace_floats": (_i64, [_i64, _vp]),
+    "ntm_unet_resblock_forward": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ntm_unet_down_combine": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp]),
+    "ntm_unet_up_combine": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp]),
+    "ntm_unet_upsample": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
+    "ntm_edm_pre": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64, _vp, _vp, _vp]),
+    "ntm_edm_post": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i64, _vp, _vp]),
 }
 ADV_HEAD_MODES = {"crit": 0, "gen": 1}      # include/ntm.h NTM_ADV_HEAD_CRIT / NTM_ADV_HEAD_GEN
 ADV_HEAD_MAX_K, ADV_HEAD_CHUNK = 8, 4096    # include/ntm.h NTM_ADV_HEAD_MAX_K, NTM_ADV_HEAD_CHUNK

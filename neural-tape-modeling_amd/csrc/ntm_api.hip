@@ -242,6 +242,123 @@ int ntm_delay_forward_f64(const float *x, const double *d, float *y, int64_t B, 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_delay_forward_f64");
 }
 
+// the argument checks ntm_unet_resblock_workspace_floats and _forward share
+static int unet_block_check(const std::string &w, int64_t B, const ntm_unet_block *k)
+{
+    if (!k) return fail(NTM_EINVAL, w + ": null pointer");
+    if (B < 0 || B > 65535) return fail(NTM_EINVAL, w + ": B must lie in [0, 65535]");
+    if (k->c0 < 1 || k->c1 < 0 || k->c0 + k->c1 > 32) return fail(NTM_EINVAL, w + ": input channels c0 + c1 must lie in [1, 32]");
+    if (k->c_out < 1 || k->c_out > 16) return fail(NTM_EINVAL, w + ": c_out must lie in [1, 16]");
+    if (k->n_layers < 1 || k->n_layers > 8) return fail(NTM_EINVAL, w + ": n_layers must lie in [1, 8]");
+    if (k->T < 1) return fail(NTM_EINVAL, w + ": T must be positive");
+    if (k->off0 < 0 || k->off0 + k->T > k->T0) return fail(NTM_EINVAL, w + ": src0 is shorter than off0 + T (or off0 < 0)");
+    if (k->c1 > 0 && (k->off1 < 0 || k->off1 + k->T > k->T1)) return fail(NTM_EINVAL, w + ": src1 is shorter than off1 + T (or off1 < 0)");
+    if (k->T0 > 0x7fffffff / 32 || (k->c1 > 0 && k->T1 > 0x7fffffff / 32)) return fail(NTM_EINVAL, w + ": 32 * frames must be below 2^31");
+    if (k->form != NTM_UNET_AUTO && k->form != NTM_UNET_WHOLE && k->form != NTM_UNET_TILED) return fail(NTM_EINVAL, w + ": unknown form");
+    if (k->form == NTM_UNET_WHOLE && k->T > NTM_UNET_WHOLE_MAX_T) return fail(NTM_EINVAL, w + ": the whole form takes T <= 1024");
+    return NTM_OK;
+}
+
+int64_t ntm_unet_resblock_workspace_floats(int64_t B, const ntm_unet_block *blk)
+{
+    if (unet_block_check("ntm_unet_resblock_workspace_floats", B, blk) != NTM_OK) return -1;
+    return ntm::unet_block_workspace(B, *blk);
+}
+
+int ntm_unet_resblock_forward(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                              const float *w_first, const float *w_gated, const float *w_res, int64_t B, const ntm_unet_block *blk,
+                              float *ws, float *out, void *stream)
+{
+    const std::string w("ntm_unet_resblock_forward");
+    if (int rc = unet_block_check(w, B, blk)) return rc;
+    const int cin = blk->c0 + blk->c1;
+    if (film_stride != 0 && film_stride < cin) return fail(NTM_EINVAL, w + ": film_stride must be 0 or at least c0 + c1");
+    if (!w_res && cin != blk->c_out) return fail(NTM_EINVAL, w + ": an identity residual (w_res == NULL) needs c0 + c1 == c_out");
+    if (B == 0) return NTM_OK;
+    if (!src0 || !film || !w_first || !w_gated || !out || (blk->c1 > 0 && !src1) || (blk->init && !init_w))
+        return fail(NTM_EINVAL, w + ": null pointer");
+    if (ntm::unet_block_workspace(B, *blk) > 0 && !ws) return fail(NTM_EINVAL, w + ": null pointer (ws)");
+    if (out == src0 || out == src1) return fail(NTM_EINVAL, w + ": out must not alias a source");
+    hipError_t e = ntm::launch_unet_block(src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, *blk, ws, out,
+                                          (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_forward");
+}
+
+// the size checks of the three resampling entry points
+static int unet_resample_check(const std::string &w, int64_t B, int C, int64_t F, int S, int width, int taps, int64_t Fo)
+{
+    if (B < 0 || B > 65535) return fail(NTM_EINVAL, w + ": B must lie in [0, 65535]");
+    if (C < 1 || C > 32) return fail(NTM_EINVAL, w + ": C must lie in [1, 32]");
+    if (F < 1) return fail(NTM_EINVAL, w + ": F must be positive");
+    if (S < 1 || S > 1024) return fail(NTM_EINVAL, w + ": S must lie in [1, 1024]");
+    if (width < 0 || taps < 0 || taps > 64) return fail(NTM_EINVAL, w + ": width must not be negative, taps at most 64");
+    if (F > 0x7fffffff / 2 || Fo > 0x7fffffff / C) return fail(NTM_EINVAL, w + ": C * frames must be below 2^31");
+    return NTM_OK;
+}
+
+int ntm_unet_down_combine(const float *x, const float *pyr, const float *ker, const float *wc, int64_t B, int C, int64_t F, int S,
+                          int width, int taps, float *x_out, float *pyr_out, void *stream)
+{
+    const std::string w("ntm_unet_down_combine");
+    if (int rc = unet_resample_check(w, B, C, F, S, width, taps, F)) return rc;
+    if (taps != 2 * width + S) return fail(NTM_EINVAL, w + ": taps must be 2 * width + S");
+    if (B == 0) return NTM_OK;
+    if (!x || !pyr || !ker || !wc || !x_out || !pyr_out) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_unet_down(x, pyr, ker, wc, B, C, F, S, width, taps, x_out, pyr_out, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_down_combine");
+}
+
+int ntm_unet_up_combine(const float *x, const float *pyr, int64_t pyr_T, const float *ker, const float *wc, int64_t B, int C,
+                        int64_t F, int S, int width, int taps, float *x_out, float *pyr_out, void *stream)
+{
+    const std::string w("ntm_unet_up_combine");
+    if (int rc = unet_resample_check(w, B, C, F, S, width, taps, (int64_t)S * F)) return rc;
+    if (S == 1 ? (taps != 0 || width != 0) : taps != 2 * width + 1)
+        return fail(NTM_EINVAL, w + ": taps must be 2 * width + 1 (S == 1: no filter, width == taps == 0)");
+    if (pyr && pyr_T < F) return fail(NTM_EINVAL, w + ": the pyramid is shorter than F");
+    if (B == 0) return NTM_OK;
+    if (!x || !wc || !pyr_out || (S > 1 && (!ker || !x_out))) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_unet_up(x, pyr, pyr_T, ker, wc, B, C, F, S, width, taps, S > 1 ? x_out : nullptr, pyr_out,
+                                       (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_up_combine");
+}
+
+int ntm_unet_upsample(const float *x, const float *ker, int64_t B, int64_t F, int S, int width, int taps, float *out, void *stream)
+{
+    const std::string w("ntm_unet_upsample");
+    if (int rc = unet_resample_check(w, B, 1, F, S, width, taps, (int64_t)S * F)) return rc;
+    if (S < 2 || taps != 2 * width + 1) return fail(NTM_EINVAL, w + ": S must be at least 2 and taps 2 * width + 1");
+    if (B == 0) return NTM_OK;
+    if (!x || !ker || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_unet_up(x, nullptr, 0, ker, nullptr, B, 1, F, S, width, taps, nullptr, out, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_upsample");
+}
+
+int ntm_edm_pre(const float *z, const float *eps, float eps_scale, float snoise, const float *mask, int64_t mask_stride,
+                const float *x_out, const float *n, float sigma0, float cin, int64_t B, int64_t T, float *z_out, float *net_in,
+                void *stream)
+{
+    if (B < 0 || T < 0) return fail(NTM_EINVAL, "ntm_edm_pre: negative size");
+    if (mask && mask_stride != 0 && mask_stride != T) return fail(NTM_EINVAL, "ntm_edm_pre: mask_stride must be 0 or T");
+    if (mask && (!x_out || !n)) return fail(NTM_EINVAL, "ntm_edm_pre: null pointer (a mask comes with x_out and n)");
+    if (B == 0 || T == 0) return NTM_OK;
+    if (!z || !z_out || !net_in) return fail(NTM_EINVAL, "ntm_edm_pre: null pointer");
+    if (B * T / 256 > 0x7fffffff) return fail(NTM_EINVAL, "ntm_edm_pre: B * T must be below 2^39");
+    hipError_t e = ntm::launch_edm_pre(z, eps, eps_scale, snoise, mask, mask_stride, x_out, n, sigma0, cin, B, T, z_out, net_in,
+                                       (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_edm_pre");
+}
+
+int ntm_edm_post(const float *z, const float *F, float cskip, float cout, float b2, float k, int64_t N, float *out, void *stream)
+{
+    if (N < 0) return fail(NTM_EINVAL, "ntm_edm_post: negative size");
+    if (N == 0) return NTM_OK;
+    if (!z || !F || !out) return fail(NTM_EINVAL, "ntm_edm_post: null pointer");
+    if (N / 256 > 0x7fffffff) return fail(NTM_EINVAL, "ntm_edm_post: N must be below 2^39");
+    hipError_t e = ntm::launch_edm_post(z, F, cskip, cout, b2, k, N, out, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_edm_post");
+}
+
 // ntm_diffdel_gru_forward[_ex] (ls == NULL) and ntm_diffdel_gru_forward_esr / _losses share this body
 static int diffdel_impl(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o, int H,
                         const float *x, const float *d, float *y, float *pre_d, int64_t B, int64_t T, float *h_state,

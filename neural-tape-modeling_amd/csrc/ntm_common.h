@@ -182,6 +182,21 @@ struct AdvHeadArgs {
 int64_t adv_head_chunks(const AdvHeadArgs &a);   // chunks of the longest half: the first grid dimension, the row length of ws
 hipError_t launch_adv_head_forward(const AdvHeadArgs &a, double *ws, float *loss, hipStream_t stream);
 hipError_t launch_adv_head_backward(const AdvHeadArgs &a, const float *gout, hipStream_t stream);
+// the diffusion generators' network and sampler step (unet_kernels.hip); the sizes are checked by ntm_api.hip
+int unet_block_launches(const ntm_unet_block &k);
+int64_t unet_block_workspace(int64_t B, const ntm_unet_block &k);
+hipError_t launch_unet_block(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                             const float *w_first, const float *w_gated, const float *w_res, int64_t B, const ntm_unet_block &k,
+                             float *ws, float *out, hipStream_t stream);
+hipError_t launch_unet_down(const float *x, const float *pyr, const float *ker, const float *wc, int64_t B, int C, int64_t F, int S,
+                            int width, int taps, float *x_out, float *pyr_out, hipStream_t stream);
+hipError_t launch_unet_up(const float *x, const float *pyr, int64_t pyr_T, const float *ker, const float *wc, int64_t B, int C,
+                          int64_t F, int S, int width, int taps, float *x_out, float *pyr_out, hipStream_t stream);
+hipError_t launch_edm_pre(const float *z, const float *eps, float eps_scale, float snoise, const float *mask, int64_t mask_stride,
+                          const float *x_out, const float *n, float sigma0, float cin, int64_t B, int64_t T, float *z_out,
+                          float *net_in, hipStream_t stream);
+hipError_t launch_edm_post(const float *z, const float *F, float cskip, float cout, float b2, float k, int64_t N, float *out,
+                           hipStream_t stream);
 hipError_t launch_delay_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
                             int32_t *err_flag, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,

@@ -1,0 +1,839 @@
+"""The diffusion generators of the reference (`DiffusionGenerator`, code/model.py:656-891, on `UNet1D`,
+code/networks/unet_1d.py): the wow-and-flutter delay trajectories that drive DiffDelRNN and the tape hiss added to its output.
+
+  load_config(name)            configs/conf_{noise,trajectories,toytrajectories}.yaml as plain data with attribute access
+  UNet1D(args, device)         the reference's parameters and buffers under the reference's state_dict keys;
+                               forward_torch: this project's restatement in torch ops (any dtype, any device),
+                               forward: the HIP path (csrc/unet_kernels.hip), HIP device only
+  DiffusionGenerator(args, device)   the EDM sampler with the reference's attributes and methods
+
+Inference only: nothing here records a graph.  Two additions to the reference's protocol, both keyword arguments:
+  draws=   an iterator of (B, seg_len) tensors that stands in for torch.randn, in the reference's draw order for one sample
+           (the first latent; then per step the extra noise where gamma != 0, then the outpainting noise);
+  sample_batch(B) / sample_long(Length, batch=B) run B independent samples through every launch together where the reference
+           loops over them: the draw order then differs from the reference's loop, the distribution does not, and with draws=
+           given per stream every stream equals its own sample() bit for bit.
+"""
+import math
+import os
+import pickle
+import re
+import types
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+SUPPORTED = "fp32 on a HIP device, Nin = 1, c_in <= 32, c_out <= 16, at most 8 gated layers, use_norm = False"
+WHOLE_MAX_T, TILE = 1024, 512      # include/ntm.h NTM_UNET_WHOLE_MAX_T, NTM_UNET_TILE
+FORMS = {"auto": 0, "whole": 1, "tiled": 2}
+
+# ---- configurations: configs/conf_*.yaml restated ------------------------------------------------------------------------------
+
+_TRAIN = {"optimizer": {"type": "adam", "beta1": 0.9, "beta2": 0.999, "eps": 1e-8}, "lr": 2e-4, "lr_rampup_it": 1000,
+          "scheduler_step_size": 10000, "batch": 4, "scheduler_gamma": 0.8, "save_model": True, "save_interval": 10000,
+          "resume": False, "use_grad_clip": True, "max_grad_norm": 1.0, "ema_rampup": 1000, "ema_rate": 0.999}
+_HYDRA = {"job": {"config": {"override_dirname": {"kv_sep": "=", "item_sep": ",",
+                                                  "exclude_keys": ["path_experiment", "hydra.job_logging.handles.file.filename"]}}}}
+_TRAJ_NET = {"name": "unet_1d", "callable": "networks.unet_1d.UNet1D", "Nin": 1, "depth": 4, "Ns": [8, 16, 16, 16, 16, 16],
+             "Ss": [2, 2, 4, 4, 4], "emb_dim": 16, "num_bottleneck_layers": 1, "use_norm": False}
+_CONFIGS = {
+    "noise": {
+        "train": _TRAIN,
+        "dset": {"callable": "datasets.tapehiss.TapeHissdset", "path": "../audio/Silence_AKAI_IPS[7.5]_MAXELL_SPLIT/Train",
+                 "fs": 44100, "seg_len": 65536, "num_workers": 2},
+        "model_dir": "../weights/83",
+        "network": {"checkpoint": "../weights/83/noise-73000.pt", "name": "unet_1d", "callable": "networks.unet_1d.UNet1D",
+                    "Nin": 1, "depth": 8, "emb_dim": 32, "Ns": [8, 16, 16, 16, 16, 16, 16, 16, 16],
+                    "Ss": [4, 4, 4, 4, 4, 4, 4, 4, 4], "use_norm": False},
+        "exp": {"exp_name": "noise_diffusion", "sample_rate": 44100, "out_sample_rate": 44100, "seg_len": 65536},
+        "diff_params": {"T": 16, "sigma_data": 8e-4, "sigma_min": 5e-5, "sigma_max": 0.1, "ro": 10, "Schurn": 0.25,
+                        "Snoise": 1.0},
+        "outpainting": {"overlap": 0.2},
+        "hydra": _HYDRA,
+    },
+    "trajectories": {
+        "train": _TRAIN,
+        "dset": {"callable": "datasets.tapehiss.TapeHissdset",
+                 "path": "../audio/ReelToReel_Dataset_Mini192kHzPulse100_AKAI_IPS[7.5]_MAXELL_TRAJECTORIES_SPLIT/Train",
+                 "fs": 192000, "seg_len": 983040, "num_workers": 2},
+        "model_dir": "../weights/91",
+        "network": dict(_TRAJ_NET, checkpoint="../weights/91/trajectories-41000.pt"),
+        "exp": {"exp_name": "trajectories", "sample_rate": 100, "out_sample_rate": 44100, "seg_len": 512},
+        "diff_params": {"T": 8, "sigma_data": 1e-4, "sigma_min": 1e-5, "sigma_max": 1e-2, "ro": 7, "Schurn": 0, "Snoise": 1},
+        "outpainting": {"overlap": 1},
+        "hydra": _HYDRA,
+    },
+    "toytrajectories": {
+        "train": _TRAIN,
+        "dset": {"callable": "datasets.tapehiss.TapeHissdset",
+                 "path": "../audio/ReelToReel_Dataset_MiniPulse100_CHOWTAPE_F[0.6]_SL[60]_TRAJECTORIES/Train",
+                 "fs": 44100, "seg_len": 225792, "num_workers": 2},
+        "model_dir": "../weights/90",
+        "network": dict(_TRAJ_NET, checkpoint="../weights/90/toytrajectories-36000.pt"),
+        "exp": {"exp_name": "toytrajectories", "sample_rate": 100, "out_sample_rate": 44100, "seg_len": 512},
+        "diff_params": {"T": 4, "sigma_data": 0.0068, "sigma_min": 1e-5, "sigma_max": 0.5, "Schurn": 0, "Snoise": 1, "ro": 7},
+        "outpainting": {"overlap": 1},
+        "hydra": _HYDRA,
+    },
+}
+
+
+class Config(dict):
+    """A dict whose keys are attributes too (args.network.depth), the way the reference reads its OmegaConf objects."""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError:
+            raise AttributeError(k) from None
+
+    def __setattr__(self, k, v):
+        self[k] = v
+
+
+_FLOAT = re.compile(r"[-+]?(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?$")
+
+
+def _wrap(v):
+    # PyYAML reads `8e-4` (no dot) as a string where OmegaConf, which the reference loads these files with, reads a float
+    if isinstance(v, str) and _FLOAT.match(v):
+        return float(v)
+    if isinstance(v, dict):
+        return Config({k: _wrap(x) for k, x in v.items()})
+    if isinstance(v, (list, tuple)):
+        return [_wrap(x) for x in v]
+    return v
+
+
+def load_config(name):
+    """"noise" | "trajectories" | "toytrajectories" -> that configuration of the reference as data (a fresh copy every call);
+    any other string is the path of a YAML file of the same layout, read with PyYAML."""
+    if name in _CONFIGS:
+        return _wrap(_CONFIGS[name])
+    if not os.path.isfile(name):
+        raise ValueError(f"load_config: {name!r} is neither one of {sorted(_CONFIGS)} nor a YAML file")
+    import yaml
+    with open(name) as f:
+        return _wrap(yaml.safe_load(f))
+
+
+# ---- torchaudio's polyphase filters ----------------------------------------------------------------------------------------------
+
+def sinc_resample_kernel(orig, new, lowpass_filter_width=6, rolloff=0.99):
+    """torchaudio's published `_get_sinc_resample_kernel` (sinc_interp_hann) for the reduced ratio orig -> new: the
+    (new, 1, 2 width + orig) float32 filter bank, computed in float64, and its width."""
+    g = math.gcd(int(orig), int(new))
+    orig, new = int(orig) // g, int(new) // g
+    base = min(orig, new) * rolloff
+    width = math.ceil(lowpass_filter_width * orig / base)
+    idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, None] / orig
+    t = torch.arange(0, -new, -1, dtype=torch.float64)[:, None, None] / new + idx
+    t = (t * base).clamp_(-lowpass_filter_width, lowpass_filter_width)
+    window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t = t * math.pi
+    kernels = torch.where(t == 0, torch.tensor(1.0, dtype=torch.float64), t.sin() / t)
+    kernels = kernels * window * (base / orig)
+    return kernels.to(torch.float32), width
+
+
+def apply_resample_kernel(x, kernel, orig, new, width):
+    """torchaudio's `_apply_sinc_resample_kernel`: pad (width, width + orig), conv1d of stride orig with the `new` phases,
+    interleave, trim to ceil(new F / orig).  x (..., F)."""
+    shape, length = x.shape, x.shape[-1]
+    w = F.pad(x.reshape(-1, length), (width, width + orig))
+    r = F.conv1d(w[:, None], kernel.to(x.dtype), stride=orig)
+    r = r.transpose(1, 2).reshape(w.shape[0], -1)
+    return r[..., :int(math.ceil(new * length / orig))].reshape(shape[:-1] + (-1,))
+
+
+class _Resample(nn.Module):
+    """What torchaudio.transforms.Resample(orig, new) leaves in a state_dict: the `kernel` buffer."""
+
+    def __init__(self, orig, new):
+        super().__init__()
+        g = math.gcd(orig, new)
+        self.orig, self.new = orig // g, new // g
+        kernel, self.width = sinc_resample_kernel(self.orig, self.new)
+        self.register_buffer("kernel", kernel)
+
+    def forward(self, x):
+        return apply_resample_kernel(x, self.kernel, self.orig, self.new, self.width)
+
+
+class Upsample(nn.Module):
+    def __init__(self, S):
+        super().__init__()
+        self.S = int(S)
+        self.resample = _Resample(1, self.S)
+
+    def forward(self, x):
+        return self.resample(x)
+
+
+class Downsample(nn.Module):
+    def __init__(self, S):
+        super().__init__()
+        self.S = int(S)
+        self.resample = _Resample(self.S, 1)
+
+    def forward(self, x):
+        return self.resample(x)
+
+
+# ---- the network -------------------------------------------------------------------------------------------------------------------
+
+class RFF_MLP_Block(nn.Module):
+    def __init__(self, emb_dim):
+        super().__init__()
+        self.RFF_freq = nn.Parameter(16 * torch.randn([1, 16]), requires_grad=False)
+        self.MLP = nn.ModuleList([nn.Linear(32, emb_dim), nn.Linear(emb_dim, emb_dim)])
+
+    def forward(self, sigma):
+        table = 2 * np.pi * sigma * self.RFF_freq
+        x = torch.cat([torch.sin(table), torch.cos(table)], dim=1)
+        for layer in self.MLP:
+            x = F.relu(layer(x))
+        return x
+
+
+class Film(nn.Module):
+    # the reference's Film(bias=False) drops beta, not the Linear's own bias: gamma = W emb + b
+    def __init__(self, output_dim, emb_dim):
+        super().__init__()
+        self.output_layer = nn.Linear(emb_dim, output_dim)
+
+    def forward(self, emb):
+        return self.output_layer(emb).unsqueeze(-1)
+
+
+class GatedResidualLayer(nn.Module):
+    def __init__(self, dim, kernel_size, dilation):
+        super().__init__()
+        self.conv = nn.Conv1d(dim, dim, kernel_size=kernel_size, dilation=dilation, stride=1, padding="same",
+                              padding_mode="zeros", bias=False)
+        self.act = nn.GELU()
+
+    def forward(self, x):
+        return (x + self.conv(self.act(x))) / (2 ** 0.5)
+
+
+class ResnetBlock(nn.Module):
+    def __init__(self, dim, dim_out, emb_dim, num_dils=8):
+        super().__init__()
+        self.dim, self.dim_out, self.num_layers = dim, dim_out, num_dils
+        self.film = Film(dim, emb_dim)
+        self.res_conv = nn.Conv1d(dim, dim_out, 1, bias=False) if dim != dim_out else nn.Identity()
+        self.first_conv = nn.Sequential(nn.GELU(), nn.Conv1d(dim, dim_out, 1, bias=False))
+        self.H = nn.ModuleList([GatedResidualLayer(dim_out, 5, 2 ** i) for i in range(num_dils)])
+
+    def forward(self, x, emb):
+        x = x * self.film(emb)
+        y = self.first_conv(x)
+        for h in self.H:
+            y = h(y)
+        return (y + self.res_conv(x)) / (2 ** 0.5)
+
+
+class CombinerUp(nn.Module):
+    def __init__(self, Npyr, Nx):
+        super().__init__()
+        self.conv1x1 = nn.Conv1d(Nx, Npyr, 1, bias=False)
+        torch.nn.init.constant_(self.conv1x1.weight, 0)
+
+    def forward(self, pyr, x):
+        x = self.conv1x1(x)
+        return x if pyr is None else (pyr[..., 0:x.shape[-1]] + x) / (2 ** 0.5)
+
+
+class CombinerDown(nn.Module):
+    def __init__(self, Nin, Nout):
+        super().__init__()
+        self.conv1x1 = nn.Conv1d(Nin, Nout, 1, bias=False)
+
+    def forward(self, pyr, x):
+        return (self.conv1x1(pyr) + x) / (2 ** 0.5)
+
+
+def _crop(x, frames):
+    """CropConcatBlock's centre crop of x to `frames` -> (first frame, x cropped)."""
+    off = (x.shape[2] - frames) // 2
+    if off < 0:
+        raise ValueError(f"UNet1D: the up path carries {x.shape[2]} frames into a skip of {frames}: nothing to crop")
+    return off, x[:, :, off:off + frames]
+
+
+class BlockSpec(_lib.ctypes.Structure):
+    """include/ntm.h ntm_unet_block."""
+    _fields_ = [("c0", _lib.ctypes.c_int32), ("c1", _lib.ctypes.c_int32), ("c_out", _lib.ctypes.c_int32),
+                ("n_layers", _lib.ctypes.c_int32), ("T", _lib.ctypes.c_int64), ("T0", _lib.ctypes.c_int64),
+                ("off0", _lib.ctypes.c_int64), ("T1", _lib.ctypes.c_int64), ("off1", _lib.ctypes.c_int64),
+                ("init", _lib.ctypes.c_int32), ("form", _lib.ctypes.c_int32)]
+
+
+def _require_hip(what, *tensors):
+    for t in tensors:
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise RuntimeError(f"{what}: HIP device only (no CPU fallback), fp32; supported: {SUPPORTED}")
+
+
+def resblock_forward(src0, film, w_first, w_gated, w_res=None, src1=None, off0=0, frames=None, init_w=None, form="auto"):
+    """One fused ResnetBlock on the device (ntm_unet_resblock_forward).
+    src0 (B, c0, T0), read from frame off0; src1 (B, c1, frames) or None: the second half of the concatenation.  With init_w
+    (c0, 1, 5), src0 is the (B, 1, T0) waveform and its c0 channels are Conv1d(1, c0, 5, "same") of it.  film (1 | B, c0 + c1);
+    w_first (c_out, c0 + c1, 1); w_gated (n, c_out, c_out, 5), layer l at dilation 2^l; w_res (c_out, c0 + c1, 1) or None (identity).
+    form "auto" | "whole" (one workgroup per stream, T <= 1024) | "tiled".  -> (B, c_out, frames)."""
+    _require_hip("resblock_forward", src0, src1, film, w_first, w_gated, w_res, init_w)
+    B, T0 = src0.shape[0], src0.shape[2]
+    c0 = init_w.shape[0] if init_w is not None else src0.shape[1]
+    T = int(frames) if frames is not None else (src1.shape[2] if src1 is not None else T0 - off0)
+    c1 = 0 if src1 is None else src1.shape[1]
+    spec = BlockSpec(c0, c1, w_first.shape[0], w_gated.shape[0], T, T0, off0, 0 if src1 is None else src1.shape[2], 0,
+                     int(init_w is not None), FORMS[form])
+    L = _lib.lib()
+    n = L.ntm_unet_resblock_workspace_floats(B, _lib.ctypes.byref(spec))
+    if n < 0:
+        raise _lib.NtmError(f"ntm_unet_resblock_workspace_floats refused: {L.ntm_last_error().decode()}")
+    ws = torch.empty(max(n, 1), dtype=torch.float32, device=src0.device)
+    out = torch.empty(B, spec.c_out, T, dtype=torch.float32, device=src0.device)
+    assert src0.is_contiguous() and (src1 is None or src1.is_contiguous()) and film.stride(-1) == 1
+    _lib.check(L.ntm_unet_resblock_forward(_lib.ptr(src0), _lib.ptr(src1), _lib.ptr(init_w), _lib.ptr(film),
+                                           0 if film.shape[0] == 1 else film.stride(0), _lib.ptr(w_first), _lib.ptr(w_gated),
+                                           _lib.ptr(w_res), B, _lib.ctypes.byref(spec), _lib.ptr(ws), _lib.ptr(out),
+                                           _lib.current_stream()), "ntm_unet_resblock_forward")
+    return out
+
+
+def down_combine(x, pyr, kernel, wc, S, width):
+    """Downsample(S) of x (B, C, F) and pyr (B, 1, F) with the (1, 1, 2 width + S) filter, then CombinerDown:
+    -> ((conv1x1(pyr_d) + x_d) / sqrt 2, pyr_d), both ceil(F / S) frames (ntm_unet_down_combine)."""
+    _require_hip("down_combine", x, pyr, kernel, wc)
+    B, C, Fr = x.shape
+    Fo = -(-Fr // S)
+    xo = torch.empty(B, C, Fo, dtype=torch.float32, device=x.device)
+    po = torch.empty(B, 1, Fo, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().ntm_unet_down_combine(_lib.ptr(x.contiguous()), _lib.ptr(pyr.contiguous()), _lib.ptr(kernel), _lib.ptr(wc),
+                                                B, C, Fr, S, width, kernel.shape[-1], _lib.ptr(xo), _lib.ptr(po),
+                                                _lib.current_stream()), "ntm_unet_down_combine")
+    return xo, po
+
+
+def up_combine(x, pyr, kernel, wc, S, width):
+    """CombinerUp then Upsample(S): p = conv1x1(x), or (pyr[..., :F] + conv1x1(x)) / sqrt 2 with a pyramid (B, 1, >= F);
+    -> (x, p) both upsampled to S F frames with the (S, 1, 2 width + 1) filter bank.  S = 1 (kernel None): -> (None, p), no
+    resampling -- the last level (ntm_unet_up_combine)."""
+    _require_hip("up_combine", x, pyr, kernel, wc)
+    B, C, Fr = x.shape
+    xo = torch.empty(B, C, S * Fr, dtype=torch.float32, device=x.device) if S > 1 else None
+    po = torch.empty(B, 1, S * Fr, dtype=torch.float32, device=x.device)
+    if pyr is not None:
+        pyr = pyr.contiguous()
+    _lib.check(_lib.lib().ntm_unet_up_combine(_lib.ptr(x.contiguous()), _lib.ptr(pyr), 0 if pyr is None else pyr.shape[-1],
+                                              _lib.ptr(kernel), _lib.ptr(wc), B, C, Fr, S, width,
+                                              0 if kernel is None else kernel.shape[-1], _lib.ptr(xo), _lib.ptr(po),
+                                              _lib.current_stream()), "ntm_unet_up_combine")
+    return xo, po
+
+
+class UNet1D(nn.Module):
+    """The reference's UNet1D: same tree, same state_dict keys (load_state_dict(checkpoint["ema"], strict=True) works and
+    replaces the recomputed resample filters with the checkpoint's own).  Up-path factors come from Ss[i] as in the reference."""
+
+    def __init__(self, args, device):
+        super().__init__()
+        net = args.network
+        if net.use_norm:
+            raise ValueError("UNet1D: use_norm=True is not supported (no shipped configuration uses the GroupNorm); "
+                             f"supported: {SUPPORTED}")
+        if net.Nin != 1:
+            raise ValueError(f"UNet1D: Nin = {net.Nin}; supported: {SUPPORTED}")
+        self.args, self.device = args, device
+        self.depth, self.emb_dim, self.use_norm = net.depth, net.emb_dim, False
+        self.Ns, self.Ss = list(net.Ns), list(net.Ss)
+        Ns, Ss, depth, E = self.Ns, self.Ss, self.depth, self.emb_dim
+        self.embedding = RFF_MLP_Block(E)
+        self.init_conv = nn.Conv1d(1, Ns[0], 5, padding="same", padding_mode="zeros", bias=False)
+        self.downs, self.middle, self.ups = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
+        for i in range(depth):
+            dim_in, dim_out = Ns[max(i - 1, 0)], Ns[i]
+            mods = [ResnetBlock(dim_in, dim_out, E)]
+            if i < depth - 1:
+                mods += [Downsample(Ss[i]), CombinerDown(1, dim_out)]
+            self.downs.append(nn.ModuleList(mods))
+        self.middle.append(nn.ModuleList([ResnetBlock(Ns[depth], Ns[depth], E)]))
+        for i in range(depth - 1, -1, -1):
+            dim_in, dim_out = Ns[i] * 2, Ns[max(i - 1, 0)]
+            mods = [ResnetBlock(dim_in, dim_out, E)]
+            if i > 0:
+                mods += [Upsample(Ss[i]), CombinerUp(1, dim_out)]
+            self.ups.append(nn.ModuleList(mods))
+        self.to(device)
+        self._packed = self._plans = None
+
+    def setup_CQT_len(self, len):
+        pass
+
+    def _apply(self, fn, *a, **k):
+        self._packed = self._plans = None
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, *a, **k):
+        self._packed = self._plans = None
+        return super().load_state_dict(*a, **k)
+
+    # -- the torch path --
+    def forward_torch(self, inputs, sigma, record=None):
+        """The network in torch ops.  record(name, tensor), if given, sees every ResnetBlock's and combiner's output under
+        its module name ("downs.0.0", "downs.0.2", ..., "ups.3.0", "final")."""
+        rec = record or (lambda n, t: None)
+        emb = self.embedding(sigma)
+        x = inputs.unsqueeze(1)
+        pyr = x
+        x = self.init_conv(x)
+        hs = []
+        for i, mods in enumerate(self.downs):
+            x = mods[0](x, emb)
+            rec(f"downs.{i}.0", x)
+            hs.append(x)
+            if len(mods) == 3:
+                x, pyr = mods[1](x), mods[1](pyr)
+                x = mods[2](pyr, x)
+                rec(f"downs.{i}.2", x)
+        x = self.middle[0][0](x, emb)
+        rec("middle.0.0", x)
+        pyr = None
+        for i, mods in enumerate(self.ups):
+            skip = hs.pop()
+            x = torch.cat((_crop(x, skip.shape[2])[1], skip), 1)
+            x = mods[0](x, emb)
+            rec(f"ups.{i}.0", x)
+            if len(mods) == 3:
+                pyr = mods[2](pyr, x)
+                rec(f"ups.{i}.2", pyr)
+                x, pyr = mods[1](x), mods[1](pyr)
+            else:
+                pyr = self._final_combiner()(pyr, x)
+        pred = pyr.squeeze(1)
+        rec("final", pred)
+        assert pred.shape == inputs.shape, "bad shapes"
+        return pred
+
+    # The reference's last level calls `combiner(pyr, x)` with the combiner left over from the level before (the loop variable
+    # of code/networks/unet_1d.py:163-183): ups[depth - 2][2].
+    def _final_combiner(self):
+        if self.depth < 2:
+            raise ValueError("UNet1D: depth >= 2 (the last level reuses the combiner of the level before, as the reference does)")
+        return self.ups[self.depth - 2][2]
+
+    # -- the HIP path --
+    def _pack(self):
+        """The parameters in the layouts the kernels read, gathered once: per block the stacked gated weights; all FiLM
+        matrices as one so that one matmul gives every block's vector."""
+        if self._packed is None:
+            blocks = [m[0] for m in self.downs] + [self.middle[0][0]] + [m[0] for m in self.ups]
+            films = (torch.cat([b.film.output_layer.weight for b in blocks], 0).float().contiguous(),
+                     torch.cat([b.film.output_layer.bias for b in blocks], 0).float().contiguous())
+            offs, o = [], 0
+            for b in blocks:
+                offs.append(o)
+                o += b.dim
+            gated = [torch.stack([h.conv.weight for h in b.H]).float().contiguous() for b in blocks]
+            self._packed = (blocks, films, offs, gated)
+        return self._packed
+
+    def films(self, sigma):
+        """Every block's FiLM vector for this sigma, in torch as the reference computes it: (rows of sigma, sum of dims)."""
+        _, (w, b), _, _ = self._pack()
+        return F.linear(self.embedding(sigma), w, b)
+
+    def _build_plan(self, B, T, per_stream, dev):
+        """The launches of one evaluation for (B, T) with their arguments bound once: every intermediate tensor, block
+        description and pointer is made here, so that an evaluation is a loop over ready calls (the sampler runs 4 to 16 of
+        them per sample and a launch is ~10 us: the host must not be the slow side).  Per call only the input, the FiLM
+        vectors, the output and the stream are patched in."""
+        L, by = _lib.lib(), _lib.ctypes.byref
+        blocks, _, offs, gated = self._pack()
+        total = sum(b.dim for b in blocks)
+        keep, calls, p_in, p_film = [], [], [], []
+
+        def new(*shape):
+            keep.append(torch.empty(*shape, dtype=torch.float32, device=dev))
+            return keep[-1]
+
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+
+        def block(k, src0, c0, T0, src1=None, off0=0, frames=None, init_w=None):
+            b = blocks[k]
+            Tb = frames if frames is not None else T0 - off0
+            c1 = 0 if src1 is None else src1.shape[1]
+            spec = BlockSpec(c0, c1, b.dim_out, len(b.H), Tb, T0, off0, 0 if src1 is None else src1.shape[2], 0, int(init_w is not None), 0)
+            n = L.ntm_unet_resblock_workspace_floats(B, by(spec))
+            if n < 0:
+                raise _lib.NtmError(f"ntm_unet_resblock_workspace_floats refused: {L.ntm_last_error().decode()}")
+            res = None if isinstance(b.res_conv, nn.Identity) else b.res_conv.weight
+            out = new(B, b.dim_out, Tb)
+            keep.append(spec)
+            calls.append(("ntm_unet_resblock_forward", L.ntm_unet_resblock_forward,
+                          [ptr(src0), ptr(src1), ptr(init_w), None, total if per_stream else 0, ptr(b.first_conv[1].weight), ptr(gated[k]),
+                           ptr(res), B, by(spec), ptr(new(max(n, 1))), ptr(out), None]))
+            p_film.append((len(calls) - 1, 3, 4 * offs[k]))
+            return out
+
+        k, hs, Tl = 0, [], T
+        x = pyr = None                                   # level 0 reads the caller's input
+        for i, mods in enumerate(self.downs):
+            if i == 0:
+                x = block(k, None, self.Ns[0], T, init_w=self.init_conv.weight)
+                p_in.append((len(calls) - 1, 0))
+            else:
+                x = block(k, x, x.shape[1], x.shape[2])
+            k += 1
+            hs.append(x)
+            if len(mods) == 3:
+                r = mods[1].resample
+                Fo = -(-Tl // r.orig)
+                xo, po = new(B, x.shape[1], Fo), new(B, 1, Fo)
+                calls.append(("ntm_unet_down_combine", L.ntm_unet_down_combine,
+                              [ptr(x), ptr(pyr), ptr(r.kernel), ptr(mods[2].conv1x1.weight), B, x.shape[1], Tl, r.orig, r.width,
+                               r.kernel.shape[-1], ptr(xo), ptr(po), None]))
+                if i == 0:
+                    p_in.append((len(calls) - 1, 1))
+                x, pyr, Tl = xo, po, Fo
+        x = block(k, x, x.shape[1], x.shape[2])
+        k += 1
+        pyr = None
+        for i, mods in enumerate(self.ups):
+            skip = hs.pop()
+            off = (x.shape[2] - skip.shape[2]) // 2
+            if off < 0:
+                raise ValueError(f"UNet1D: the up path carries {x.shape[2]} frames into a skip of {skip.shape[2]}")
+            x = block(k, x, x.shape[1], x.shape[2], skip, off0=off, frames=skip.shape[2])
+            k += 1
+            Fr, C = x.shape[2], x.shape[1]
+            if len(mods) == 3:
+                r = mods[1].resample
+                xo, po = new(B, C, r.new * Fr), new(B, 1, r.new * Fr)
+                calls.append(("ntm_unet_up_combine", L.ntm_unet_up_combine,
+                              [ptr(x), ptr(pyr), 0 if pyr is None else pyr.shape[-1], ptr(r.kernel), ptr(mods[2].conv1x1.weight), B, C,
+                               Fr, r.new, r.width, r.kernel.shape[-1], ptr(xo), ptr(po), None]))
+                x, pyr = xo, po
+            else:
+                if Fr != T:
+                    raise AssertionError("bad shapes")
+                calls.append(("ntm_unet_up_combine", L.ntm_unet_up_combine,
+                              [ptr(x), ptr(pyr), 0 if pyr is None else pyr.shape[-1], None, ptr(self._final_combiner().conv1x1.weight), B,
+                               C, Fr, 1, 0, 0, None, None, None]))
+        return {"calls": calls, "in": p_in, "film": p_film, "keep": keep}
+
+    def _run_plan(self, inputs, films):
+        B, T = inputs.shape
+        key = (B, T, films.shape[0] != 1, inputs.device)
+        if self._plans is None:
+            self._plans = {}
+        plan = self._plans.get(key)
+        if plan is None:
+            if films.shape[0] not in (1, B):
+                raise ValueError(f"UNet1D.forward: sigma has {films.shape[0]} rows for a batch of {B}")
+            plan = self._plans[key] = self._build_plan(B, T, key[2], inputs.device)
+        out = torch.empty(B, T, dtype=torch.float32, device=inputs.device)
+        calls, stream = plan["calls"], _lib.current_stream()
+        assert films.is_contiguous() or films.shape[0] == 1
+        src, fbase = inputs.data_ptr(), films.data_ptr()
+        for ci, ai in plan["in"]:
+            calls[ci][2][ai] = src
+        for ci, ai, off in plan["film"]:
+            calls[ci][2][ai] = fbase + off
+        calls[-1][2][12] = out.data_ptr()
+        for name, fn, args in calls:
+            args[-1] = stream
+            _lib.check(fn(*args), name)
+        return out
+
+    def forward(self, inputs, sigma, films=None, record=None):
+        """The network on the HIP path: inputs (B, T), sigma (1 | B, 1) (or `films` from self.films(sigma), which the sampler
+        computes once per step at construction).  -> (B, T)."""
+        if not inputs.is_cuda:
+            raise RuntimeError(f"UNet1D.forward: HIP device only (no CPU fallback); use forward_torch.  Supported: {SUPPORTED}")
+        rec = record or (lambda n, t: None)
+        blocks, _, offs, gated = self._pack()
+        if films is None:
+            films = self.films(sigma.reshape(-1, 1).float())
+        inputs = inputs.float().contiguous()
+        if record is None:
+            return self._run_plan(inputs, films)
+
+        def run(k, src0, src1=None, off0=0, frames=None, init_w=None):
+            b = blocks[k]
+            res = None if isinstance(b.res_conv, nn.Identity) else b.res_conv.weight
+            return resblock_forward(src0, films[:, offs[k]:offs[k] + b.dim], b.first_conv[1].weight, gated[k], res, src1, off0,
+                                    frames, init_w)
+
+        x = pyr = inputs.unsqueeze(1)
+        hs, k = [], 0
+        for i, mods in enumerate(self.downs):
+            x = run(k, x, init_w=self.init_conv.weight if i == 0 else None)
+            k += 1
+            rec(f"downs.{i}.0", x)
+            hs.append(x)
+            if len(mods) == 3:
+                r = mods[1].resample
+                x, pyr = down_combine(x, pyr, r.kernel, mods[2].conv1x1.weight, r.orig, r.width)
+                rec(f"downs.{i}.2", x)
+        x = run(k, x)
+        k += 1
+        rec("middle.0.0", x)
+        pyr = None
+        for i, mods in enumerate(self.ups):
+            skip = hs.pop()
+            off = (x.shape[2] - skip.shape[2]) // 2
+            if off < 0:
+                raise ValueError(f"UNet1D: the up path carries {x.shape[2]} frames into a skip of {skip.shape[2]}")
+            x = run(k, x, skip, off0=off, frames=skip.shape[2])
+            k += 1
+            rec(f"ups.{i}.0", x)
+            if len(mods) == 3:
+                r = mods[1].resample
+                if record is not None:
+                    rec(f"ups.{i}.2", up_combine(x, pyr, None, mods[2].conv1x1.weight, 1, 0)[1])
+                x, pyr = up_combine(x, pyr, r.kernel, mods[2].conv1x1.weight, r.new, r.width)
+            else:
+                pyr = up_combine(x, pyr, None, self._final_combiner().conv1x1.weight, 1, 0)[1]
+        pred = pyr.squeeze(1)
+        rec("final", pred)
+        assert pred.shape == inputs.shape, "bad shapes"
+        return pred
+
+
+# ---- checkpoints -----------------------------------------------------------------------------------------------------------------------
+
+class _TolerantUnpickler(pickle.Unpickler):
+    """The reference's checkpoints pickle their OmegaConf configuration next to the tensors: classes that are not installed
+    here unpickle as empty stand-ins, everything else as usual."""
+
+    def find_class(self, module, name):
+        try:
+            return super().find_class(module, name)
+        except (ImportError, AttributeError):
+            return type(name, (), {"__init__": lambda self, *a, **k: None, "__setstate__": lambda self, s: None,
+                                   "__module__": module})
+
+
+_tolerant_pickle = types.ModuleType("ntm_tolerant_pickle")
+_tolerant_pickle.Unpickler = _TolerantUnpickler
+_tolerant_pickle.load = lambda f, **k: _TolerantUnpickler(f, **k).load()
+_tolerant_pickle.__name__ = "pickle"
+
+
+def load_checkpoint(path, device="cpu"):
+    """A reference `.pt` (its "ema" dict) or an `.npz` export of one -> a state dict of tensors."""
+    if str(path).endswith(".npz"):
+        with np.load(path) as z:
+            return {k: torch.from_numpy(z[k].copy()).to(device) for k in z.files}
+    ck = torch.load(path, map_location=device, pickle_module=_tolerant_pickle, weights_only=False)
+    return ck["ema"]
+
+
+# ---- the sampler -------------------------------------------------------------------------------------------------------------------------
+
+class DiffusionGenerator:
+    """The reference's DiffusionGenerator.  On a HIP device every method runs the HIP path (network and EDM step kernels); with
+    hip=False, or on the CPU, the torch path -- the reference's expressions on forward_torch."""
+
+    def __init__(self, args, device, hip=None):
+        self.args, self.device = args, torch.device(device)
+        self.hip = self.device.type == "cuda" if hip is None else bool(hip)
+        self.network = UNet1D(args, self.device)
+        if args.network.get("checkpoint"):
+            sd = load_checkpoint(args.network.checkpoint, self.device)
+            levels = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("downs."))
+            if levels != args.network.depth:
+                # conf_noise.yaml says depth 8, the checkpoint it names (weights/83) holds 6 levels: say so by name
+                raise ValueError(f"DiffusionGenerator: {args.network.checkpoint} holds a network of depth {levels}, "
+                                 f"args.network.depth is {args.network.depth}: set args.network.depth = {levels}")
+            self.network.load_state_dict(sd)
+        self.network.eval()
+        dp = args.diff_params
+        self.sigma_min, self.sigma_max, self.ro, self.sigma_data = dp.sigma_min, dp.sigma_max, dp.ro, dp.sigma_data
+        self.Schurn, self.Snoise = dp.Schurn, dp.Snoise
+        self.seg_len, self.sample_rate, self.out_sample_rate = args.exp.seg_len, args.exp.sample_rate, args.exp.out_sample_rate
+        # the schedule and gamma are computed on the host in float32, as the reference's expressions do, and copied
+        self._schedule = self.create_schedule(dp.T)
+        self._gamma = self.get_gamma(self._schedule)
+        self.schedule, self.gamma = self._schedule.to(self.device), self._gamma.to(self.device)
+        self._steps = self._bufs = None
+        self._rs_kernel = None
+
+    def create_schedule(self, nb_steps):
+        i = torch.arange(0, nb_steps + 1)
+        t = (self.sigma_max ** (1 / self.ro) + i / (nb_steps - 1) *
+             (self.sigma_min ** (1 / self.ro) - self.sigma_max ** (1 / self.ro))) ** self.ro
+        t[-1] = 0
+        return t
+
+    def cskip(self, sigma):
+        return self.sigma_data ** 2 * (sigma ** 2 + self.sigma_data ** 2) ** -1
+
+    def cout(self, sigma):
+        return sigma * self.sigma_data * (self.sigma_data ** 2 + sigma ** 2) ** (-0.5)
+
+    def cin(self, sigma):
+        return (self.sigma_data ** 2 + sigma ** 2) ** (-0.5)
+
+    def cnoise(self, sigma):
+        return (1 / 4) * torch.log(sigma)
+
+    def get_gamma(self, t):
+        N = t.shape[0]
+        gamma = torch.zeros(t.shape).to(t.device)
+        return gamma + torch.min(torch.Tensor([self.Schurn / N, 2 ** (1 / 2) - 1])).to(t.dtype)
+
+    def _net(self, x, cnoise, films=None):
+        if self.hip:
+            return self.network(x, cnoise, films=films)
+        return self.network.forward_torch(x, cnoise.reshape(-1, 1) if cnoise.dim() < 2 else cnoise)
+
+    def denoiser(self, xn, sigma):
+        if len(sigma.shape) == 1:
+            sigma = sigma.unsqueeze(-1)
+        with torch.no_grad():
+            return self.cskip(sigma) * xn + self.cout(sigma) * self._net(self.cin(sigma) * xn, self.cnoise(sigma))
+
+    def ode_update(self, x, sigma_0, sigma_1):
+        x_0_hat = self.denoiser(x, sigma_1)
+        score = (x_0_hat - x) / sigma_1 ** 2
+        return x - (sigma_0 - sigma_1) * sigma_1 * score
+
+    # -- the per-step constants: fixed at construction of the schedule, computed once --
+    def _plan(self):
+        """Per step: the reference's scalars as float32 host tensors (its own expressions on the host schedule) and, on the HIP
+        path, every block's FiLM vector for that step's cnoise."""
+        if self._steps is None:
+            sch = torch.flip(self._schedule, (0,))
+            steps = []
+            for i in range(len(sch) - 1):
+                s0 = sch[-i - 1]
+                if self._gamma[i] == 0:
+                    s1, eps = sch[-i - 2], None
+                else:
+                    s1 = sch[-i - 2] + self._gamma[i] * sch[-i - 2]
+                    eps = (s1 ** 2 - sch[-i - 2] ** 2) ** (1 / 2)
+                st = {"s0": s0, "s1": s1, "eps": eps, "cskip": self.cskip(s0), "cout": self.cout(s0), "cin": self.cin(s0),
+                      "cnoise": self.cnoise(s0), "b2": s0 ** 2, "k": (s1 - s0) * s0}
+                if self.hip:
+                    with torch.no_grad():
+                        st["films"] = self.network.films(st["cnoise"].reshape(1, 1).to(self.device)).contiguous()
+                    st["f"] = {n: float(st[n]) for n in ("s0", "cskip", "cout", "cin", "b2", "k")}
+                    st["f"]["eps"] = 0.0 if eps is None else float(eps)
+                steps.append(st)
+            self._steps = steps
+        return self._steps
+
+    def _draw(self, draws, B):
+        if draws is None:
+            return torch.randn((B, self.seg_len), device=self.device)
+        d = next(draws).to(self.device)
+        assert d.shape == (B, self.seg_len), f"draws: expected {(B, self.seg_len)}, got {tuple(d.shape)}"
+        return d
+
+    def _sample(self, B, x_outpaint=None, mask=None, draws=None):
+        steps = self._plan()
+        z = self._draw(draws, B) * self.schedule[0]
+        for st in steps:
+            eps = self._draw(draws, B) if st["eps"] is not None else None
+            n = self._draw(draws, B) if mask is not None else None
+            if self.hip:
+                z = self._hip_step(z, st, eps, x_outpaint, mask, n)
+                continue
+            s0, s1 = st["s0"].to(z), st["s1"].to(z)
+            if eps is not None:
+                z = z + st["eps"].to(z) * (eps.to(z) * self.Snoise)
+            if mask is not None:
+                z = mask * (x_outpaint + n.to(z) * s0) + (1 - mask) * z
+            z = self.ode_update(z, s1, s0)
+        return z
+
+    def _hip_step(self, z, st, eps, x_outpaint, mask, n):
+        """One sampler step on the device: ntm_edm_pre, the network, ntm_edm_post."""
+        L, f = _lib.lib(), st["f"]
+        z = z.float().contiguous()
+        B, T = z.shape
+        if self._bufs is None or self._bufs[0].shape != z.shape:
+            self._bufs = (torch.empty_like(z), torch.empty_like(z))       # the step's two intermediates, reused by every step
+        zin, net_in = self._bufs
+        if mask is not None:
+            mask = mask.float().expand(-1, T).contiguous() if mask.shape[0] != 1 else mask.float().contiguous()
+            x_outpaint = x_outpaint.float().expand(B, T).contiguous()
+            n = n.float().contiguous()
+        if eps is not None:
+            eps = eps.float().contiguous()
+        _lib.check(L.ntm_edm_pre(_lib.ptr(z), _lib.ptr(eps), f["eps"], float(self.Snoise), _lib.ptr(mask),
+                                 0 if mask is None or mask.shape[0] == 1 else T, _lib.ptr(x_outpaint), _lib.ptr(n), f["s0"],
+                                 f["cin"], B, T, _lib.ptr(zin), _lib.ptr(net_in), _lib.current_stream()), "ntm_edm_pre")
+        with torch.no_grad():
+            Fx = self.network(net_in, None, films=st["films"]).contiguous()
+        out = torch.empty_like(z)
+        _lib.check(L.ntm_edm_post(_lib.ptr(zin), _lib.ptr(Fx), f["cskip"], f["cout"], f["b2"], f["k"], B * T, _lib.ptr(out),
+                                  _lib.current_stream()), "ntm_edm_post")
+        return out
+
+    def sample(self, draws=None):
+        return self._sample(1, draws=draws)
+
+    def outpaint_sample(self, x_oupaint, mask, draws=None):
+        return self._sample(x_oupaint.shape[0], x_oupaint, mask, draws=draws)
+
+    def sample_batch(self, batch_size, draws=None):
+        """B independent samples through every launch together (the reference loops over sample())."""
+        return self._sample(batch_size, draws=draws)
+
+    def sample_long(self, Length, batch=1, draws=None):
+        """The reference's sample_long; batch=B: B independent long samples side by side -> (B, ...).  self.segments counts the
+        sampler runs of the last call."""
+        Length_samples = int(Length * self.sample_rate)
+        output = torch.zeros((batch, Length_samples), device=self.device)
+        first = self._sample(batch, draws=draws)
+        self.segments = 1
+        if first.shape[-1] > Length_samples:
+            output = first[:, :Length_samples]
+        else:
+            output[..., 0:first.shape[-1]] = first
+            mask = torch.zeros_like(first[:1])
+            samples_ov = int(self.args.outpainting.overlap * self.sample_rate)
+            hop = self.seg_len - samples_ov
+            mask[..., 0:samples_ov] = 1
+            pointer = hop
+            while (pointer + self.seg_len) < Length_samples:
+                pred = self._sample(batch, output[..., pointer:(pointer + self.seg_len)], mask, draws=draws)
+                output[..., pointer:(pointer + self.seg_len)] = pred
+                pointer += hop
+                self.segments += 1
+            if pointer + samples_ov < Length_samples:
+                x_pred = output[..., pointer::]
+                x_pred = torch.cat((x_pred, torch.zeros(batch, self.seg_len - x_pred.shape[-1], device=self.device)), -1)
+                pred = self._sample(batch, x_pred, mask, draws=draws)
+                output[..., pointer::] = pred[..., 0:output.shape[-1] - pointer]
+                self.segments += 1
+        return self.resampler(output)
+
+    def resampler(self, x):
+        """torchaudio.functional.resample(x, sample_rate, out_sample_rate): equal rates return x; otherwise the polyphase filter
+        bank of the reduced ratio (100 -> 44 100: 441 phases of 15 taps).  On the HIP path with an integer ratio, the
+        upsampling kernel of the network (ntm_unet_up_combine's resampling half)."""
+        o, n = int(self.sample_rate), int(self.out_sample_rate)
+        if o == n:
+            return x
+        if self._rs_kernel is None:
+            k, w = sinc_resample_kernel(o, n)
+            g = math.gcd(o, n)
+            self._rs_kernel = (k.to(self.device), w, o // g, n // g)
+        k, w, o, n = self._rs_kernel
+        if self.hip and o == 1 and x.is_cuda:
+            out = torch.empty(x.shape[0], 1, n * x.shape[-1], dtype=torch.float32, device=x.device)
+            _lib.check(_lib.lib().ntm_unet_upsample(_lib.ptr(x.float().contiguous()), _lib.ptr(k), x.shape[0], x.shape[-1], n, w,
+                                                    k.shape[-1], _lib.ptr(out), _lib.current_stream()), "ntm_unet_upsample")
+            return out.squeeze(1)
+        return apply_resample_kernel(x, k, o, n, w)
