@@ -77,24 +77,6 @@ _SIGNATURES = {
     "ntm_spectrogram": (_int, [_vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "ntm_spectrogram_grad": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _int, _vp]),
     "ntm_stft_grad": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, ctypes.c_float, _vp, _vp, _vp, _int, _vp]),
-    # the conv stack of the spectral critics (additions within ABI version 9); layers: ConvLayer[n], g / v / bias / dg / dv / dbias:
-    # host arrays of n device pointers (ptr_array)
-    "ntm_speccrit_saved_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
-    "ntm_speccrit_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
-    "ntm_speccrit_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ntm_speccrit_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    # the dilated conv stack of the time-domain critic (additions within ABI version 9); layers: ConvLayerD[n], the float is the
-    # LeakyReLU slope
-    "ntm_convstack_saved_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
-    "ntm_convstack_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
-    "ntm_convstack_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ntm_convstack_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    # the strided conv stack of the MelGAN critic (additions within ABI version 9); layers: ConvLayerS[n]; outs / gouts: host
-    # arrays of n device pointers, one tensor per layer (a gouts entry may be null)
-    "ntm_sconvstack_saved_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
-    "ntm_sconvstack_workspace_floats": (_i64, [_i64, _i64, _i64, _int, _vp]),
-    "ntm_sconvstack_forward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ntm_sconvstack_backward": (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # the hinge / mean heads of the adversarial losses (additions within ABI version 9); outs / grads: host arrays of K device
     # pointers (ptr_array), elems: host int64 array (i64_array)
     "ntm_adv_head_forward": (_int, [_vp, _vp, _int, _i64, _i64, _int, _vp, _i64, _vp, _vp]),
@@ -110,6 +92,14 @@ _SIGNATURES = {
     "ntm_edm_pre": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64, _vp, _vp, _vp]),
     "ntm_edm_post": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i64, _vp, _vp]),
 }
+# the three critic conv stacks (additions within ABI version 9): the spectral critics (layers: ConvLayer[n], the float is the log
+# floor), the dilated stack of the time-domain critic (ConvLayerD[n]) and the strided stack of the MelGAN critic (ConvLayerS[n]; for
+# both the float is the LeakyReLU slope).  g / v / bias / dg / dv / dbias: host arrays of n device pointers (ptr_array); the
+# strided family's outs / gouts likewise, one tensor per layer (a gouts entry may be null): one pointer more in its backward
+for _p in ("speccrit", "convstack", "sconvstack"):
+    _SIGNATURES[f"ntm_{_p}_saved_floats"] = _SIGNATURES[f"ntm_{_p}_workspace_floats"] = (_i64, [_i64, _i64, _i64, _int, _vp])
+    _SIGNATURES[f"ntm_{_p}_forward"] = (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int] + [_vp] * 7)
+    _SIGNATURES[f"ntm_{_p}_backward"] = (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int] + [_vp] * (12 if _p == "sconvstack" else 11))
 ADV_HEAD_MODES = {"crit": 0, "gen": 1}      # include/ntm.h NTM_ADV_HEAD_CRIT / NTM_ADV_HEAD_GEN
 ADV_HEAD_MAX_K, ADV_HEAD_CHUNK = 8, 4096    # include/ntm.h NTM_ADV_HEAD_MAX_K, NTM_ADV_HEAD_CHUNK
 

@@ -1,24 +1,21 @@
 // The conv stack of the reference's time-domain critic (DilatedConvDisc, code/critics.py:262-331) and of any stack like it: n
 // weight-normed Conv1d(c_in, c_out, k, groups, dilation) layers, stride 1, no padding, LeakyReLU(slope) after every layer but the
-// last -- forward, data gradient, weight gradient and the weight-norm adjoint, fp32 in and fp32 accumulate on
-// v_mfma_f32_16x16x4_f32 (exact fp32: the matrix pipe's fmaf chain).  The family of critic_kernels.hip with three differences: a
-// dilation per layer (up to 2^20, so no slab of tile + (K - 1) d frames can sit in LDS), up to 16 layers, and the slope an argument.
+// last.  What it shares with the spectral and the MelGAN family (the plan, weight preparation, weight-norm adjoint) is
+// convstack_common.h; this file holds its GEMM kernels: a dilation per layer (up to 2^20, so no slab of tile + (K - 1) d frames
+// can sit in LDS) and with it the PER-TAP fetch form of the conv kernel, the two-level weight gradient, and the chunk rule.
 //
-// cs_prep_kernel      one launch for all layers, one workgroup per output channel: |v| over (c_in/groups, k), w = v * (g / |v|) in
-//                     the two layouts the conv kernel reads, and 1/|v| for the adjoint.
-//                       wF[k][ci][CO]   (ci within the group, CO every output channel)          -- forward
-//                       wB[j][co][CI]   (co within the group, CI every input channel) = w[co][ci][K-1-j]   -- data gradient
 // cs_conv_kernel      the implicit GEMM along the frames: out[b][m][f] = sum_{c,j} W[j][c][m] in[b][c][f + j d + off], one workgroup
 //                     per (stream, group, tile of output channels, tile of frames).  One step = (slab of 16 input channels, 4
 //                     taps): the LDS operand is PER-TAP WINDOWS, 4 taps x 16 channels x tile frames, tap j's window starting at
 //                     frame n0 + off + j d -- one form for every dilation (at d >= tile the windows do not overlap and nothing is
 //                     read twice; at small d the overlap is read again from L2, up to K times the slab form's traffic, against
 //                     64 MFMAs per wave and step).  A wave's MFMA takes 4 consecutive input channels of one tap as its K = 4.
-//                       forward        off = 0,  W = wF, epilogue bias -> LeakyReLU(slope) (the last layer: bias)
+//                       forward        off = 0,  W = wF (TapMajorLayout)
 //                       data gradient  the same sum with the roles of the channels swapped: in = gz (the gradient at the layer's
-//                                      pre-activation), off = -(K-1) d with zeros outside, W = wB; epilogue: times the LeakyReLU
-//                                      slope of the layer below, recovered from the sign of its saved output (y > 0 <=> pre > 0 as
-//                                      slope > 0; y == 0 takes the slope, torch's choice)
+//                                      pre-activation), off = -(K-1) d with zeros outside, W = wB
+//                     Epilogues: forward, bias -> LeakyReLU(slope) (the last layer: bias).  Data gradient: times the LeakyReLU
+//                     slope of the layer below, recovered from the sign of its saved output (y > 0 <=> pre > 0 as slope > 0;
+//                     y == 0 takes the slope, torch's choice), so every stored gz is already a pre-activation gradient.
 //                     Order of addition of one output: per slab of 16 input channels a sum from 0, taps ascending and per tap
 //                     the channels in fours (one MFMA each, its K = 4 an fmaf chain); the slab sums are then added in ascending
 //                     order -- a function of the layer alone, so a stream's result does not depend on its batch.  The loads of
@@ -30,116 +27,34 @@
 //                     flop even at 1/16 use of the pipe, and a second kernel would be a second order of addition to pin.
 // cs_wgrad_kernel     dW[co][ci][k] = sum_{b,f} gz[b][co][f] in[b][ci][f + k d]: GEMM with M = co, N = (ci, k) flattened as dW is
 //                     stored, reduction over the frames (64 per step, the MFMA's K = 4 consecutive frames).  The LDS operand is
-//                     per-column windows: column (ci, k) holds in[b][ci][f0 + k d .. + 63].  The reduction is cut into chunks of
-//                     (stream chunk, frame segment): the streams into at most 32 contiguous chunks (as the spectral family), the
-//                     output frames of a layer into segments of kCsSegFrames = 1024.  A workgroup walks the streams of its chunk in
-//                     order and the frames of its segment in order, adding 4 steps (256 frames) from 0 and then that sum to its
-//                     total, and stores ONE partial tile, no atomics.  The workgroups of the first N tile also add up the rows of
-//                     gz (the bias gradient), 64 frames from 0 at a time.
-// cs_wnorm_kernel     one launch for all layers, one workgroup per output channel: adds the partials of a layer in chunk order
-//                     (stream chunk major, segment minor) into the first one, then dg = sum(dW v) / |v|, dv = (g / |v|) (dW - v sum(dW v) / |v|^2),
-//                     dbias = the sum of the row partials.
+//                     per-column windows: column (ci, k) holds in[b][ci][f0 + k d .. + 63].  Chunk rule: the streams into at most
+//                     32 contiguous chunks (as the spectral family), the output frames of a layer into segments of kCsSegFrames =
+//                     1024.  A workgroup walks the streams of its chunk in order and the frames of its segment in order, adding
+//                     4 steps (256 frames) from 0 and then that sum to its total, and stores ONE partial tile, no atomics.  The
+//                     workgroups of the first N tile also add up the rows of gz (the bias gradient), 64 frames from 0 at a time.
 //
 // Two tile shapes per GEMM kernel: 64 output channels x 64 columns (2 x 2 waves of 32 x 32) where a group has more than 16
 // output channels, else 16 x 128 (16 x 64 for the weight gradient), four waves side by side.  Every valid layer runs on them:
 // edges are predicated, there is no second code path.
-#include "ntm.h"
-#include "ntm_common.h"
+#include "convstack_common.h"
 
 namespace ntm {
 
 constexpr int kCsMaxChunks = 32;      // stream chunks of the weight gradient
 constexpr int kCsSegFrames = 1024;    // output frames per segment of the weight gradient (include/ntm.h documents both)
 
-void convstack_plan(ConvStackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_d *L)
+void convstack_plan(StackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_d *L)
 {
-    p.n = n;
-    p.F[0] = F0;
-    p.w_total = 0;
-    p.rows = 0;
+    stack_plan_layers(p, B, F0, n, L, true, [&](int l, int64_t F) { return F - (int64_t)(L[l].k - 1) * L[l].dilation; });
     for (int l = 0; l < n; ++l) {
-        p.c_in[l] = L[l].c_in, p.c_out[l] = L[l].c_out, p.k[l] = L[l].k, p.groups[l] = L[l].groups, p.dil[l] = L[l].dilation;
-        p.F[l + 1] = p.F[l] - (int64_t)(L[l].k - 1) * L[l].dilation;
-        p.w_off[l] = p.w_total;
-        p.w_total += (int64_t)L[l].c_out * (L[l].c_in / L[l].groups) * L[l].k;
-        p.row0[l] = p.rows;
-        p.rows += L[l].c_out;
+        p.dil[l] = L[l].dilation;
+        stack_stream_chunks(B, kCsMaxChunks, p.nchunk[l], p.per[l]);
+        p.seg[l] = kCsSegFrames, p.nseg[l] = stack_cdiv(p.F[l + 1], kCsSegFrames);
     }
-    int64_t at = 2 * p.w_total + p.rows;
-    p.gz_size = 0;
-    for (int l = 0; l + 1 < n; ++l) {
-        p.act_off[l] = at;
-        const int64_t sz = B * p.c_out[l] * p.F[l + 1];
-        at += sz;
-        if (sz > p.gz_size) p.gz_size = sz;
-    }
-    p.saved_total = at;
-    p.nchunk = (int)(B < kCsMaxChunks ? (B > 0 ? B : 1) : kCsMaxChunks);
-    p.per = (int)((B + p.nchunk - 1) / p.nchunk);
-    if (p.per < 1) p.per = 1;
-    p.nchunk = (int)((B + p.per - 1) / p.per);
-    int64_t w = 2 * p.gz_size;
-    for (int l = 0; l < n; ++l) {
-        p.nseg[l] = (p.F[l + 1] + kCsSegFrames - 1) / kCsSegFrames;
-        const int64_t parts = (int64_t)p.nchunk * p.nseg[l];
-        p.part_off[l] = w;
-        w += parts * ((int64_t)L[l].c_out * (L[l].c_in / L[l].groups) * L[l].k);
-        p.bpart_off[l] = w;
-        w += parts * L[l].c_out;
-    }
-    p.ws_total = w;
+    stack_plan_partials(p);
 }
 
 namespace {
-
-// sum over the workgroup in a fixed tree order; every thread gets it
-template <int NT>
-__device__ __forceinline__ float block_sum(float x, float *red)
-{
-    const int tid = threadIdx.x;
-    red[tid] = x;
-    __syncthreads();
-#pragma unroll
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-struct PrepArgs {
-    const float *g[kConvStackMaxLayers], *v[kConvStackMaxLayers];
-    int c_in[kConvStackMaxLayers], c_out[kConvStackMaxLayers], k[kConvStackMaxLayers], groups[kConvStackMaxLayers],
-        row0[kConvStackMaxLayers];
-    int64_t w_off[kConvStackMaxLayers];
-    int n;
-    float *wF, *wB, *invn;
-};
-
-__global__ __launch_bounds__(256) void cs_prep_kernel(PrepArgs a)
-{
-    __shared__ float red[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    int l = 0;
-    while (l + 1 < a.n && row >= a.row0[l + 1]) ++l;
-    const int co = row - a.row0[l], K = a.k[l], cin_g = a.c_in[l] / a.groups[l], cout_g = a.c_out[l] / a.groups[l];
-    const int n = cin_g * K, grp = co / cout_g, co_l = co - grp * cout_g;
-    const float *v = a.v[l] + (int64_t)co * n;
-    float s = 0.0f;
-    for (int j = tid; j < n; j += 256) s = fmaf(v[j], v[j], s);
-    const float norm = sqrtf(block_sum<256>(s, red));
-    const float scale = a.g[l][co] / norm;
-    float *wF = a.wF + a.w_off[l], *wB = a.wB + a.w_off[l];
-    for (int j = tid; j < n; j += 256) {
-        const int ci = j / K, k = j - ci * K;
-        const float w = v[j] * scale;
-        wF[((int64_t)k * cin_g + ci) * a.c_out[l] + co] = w;
-        wB[((int64_t)(K - 1 - k) * cout_g + co_l) * a.c_in[l] + grp * cin_g + ci] = w;
-    }
-    if (tid == 0) a.invn[row] = 1.0f / norm;
-}
 
 enum { EPI_BIAS_LRELU = 0, EPI_BIAS = 1, EPI_MASK = 2, EPI_NONE = 3 };
 
@@ -416,51 +331,6 @@ __global__ __launch_bounds__(256) void cs_wgrad_kernel(WgradArgs a)
         a.bpart[part_i * a.Cout + grp * a.cout_g + m0 + tid] = bsum;
 }
 
-struct WnormArgs {
-    const float *g[kConvStackMaxLayers], *v[kConvStackMaxLayers];
-    float *dg[kConvStackMaxLayers], *dv[kConvStackMaxLayers], *db[kConvStackMaxLayers];
-    float *part[kConvStackMaxLayers];         // the sum of a row's partials is left in its first partial
-    const float *bpart[kConvStackMaxLayers];
-    int c_out[kConvStackMaxLayers], rowlen[kConvStackMaxLayers], row0[kConvStackMaxLayers];
-    int64_t nparts[kConvStackMaxLayers];
-    int n;
-    const float *invn;
-};
-
-__global__ __launch_bounds__(256) void cs_wnorm_kernel(WnormArgs a)
-{
-    __shared__ float red[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    int l = 0;
-    while (l + 1 < a.n && row >= a.row0[l + 1]) ++l;
-    const int co = row - a.row0[l], n = a.rowlen[l];
-    const int64_t cstride = (int64_t)a.c_out[l] * n, np = a.nparts[l];
-    const float *v = a.v[l] + (int64_t)co * n;
-    float *p = a.part[l] + (int64_t)co * n;
-    float s = 0.0f;
-    for (int j = tid; j < n; j += 256) {
-        float dw = p[j];
-        int64_t c = 1;
-        for (; c + 4 <= np; c += 4) {           // four loads in flight, added in chunk order
-            const float p0 = p[c * cstride + j], p1 = p[(c + 1) * cstride + j], p2 = p[(c + 2) * cstride + j], p3 = p[(c + 3) * cstride + j];
-            dw = (((dw + p0) + p1) + p2) + p3;
-        }
-        for (; c < np; ++c) dw += p[c * cstride + j];
-        p[j] = dw;
-        s = fmaf(dw, v[j], s);
-    }
-    const float dot = block_sum<256>(s, red);
-    const float inv = a.invn[row], scale = a.g[l][co] * inv, proj = dot * inv * inv;
-    float *dv = a.dv[l] + (int64_t)co * n;
-    for (int j = tid; j < n; j += 256) dv[j] = scale * (p[j] - v[j] * proj);
-    if (tid == 0) {
-        a.dg[l][co] = dot * inv;
-        float sb = a.bpart[l][co];
-        for (int64_t c = 1; c < np; ++c) sb += a.bpart[l][c * a.c_out[l] + co];
-        a.db[l][co] = sb;
-    }
-}
-
 hipError_t launch_conv(ConvArgs a, int64_t B, int groups, hipStream_t stream)
 {
     const bool narrow = a.cout_g <= 16;
@@ -492,19 +362,10 @@ hipError_t launch_wgrad(WgradArgs a, int groups, int nchunk, hipStream_t stream)
 
 }  // namespace
 
-hipError_t launch_convstack_forward(const ConvStackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_convstack_forward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                     const float *const *v, const float *const *bias, float *saved, float *out, hipStream_t stream)
 {
-    PrepArgs pa{};
-    for (int l = 0; l < p.n; ++l) {
-        pa.g[l] = g[l], pa.v[l] = v[l];
-        pa.c_in[l] = p.c_in[l], pa.c_out[l] = p.c_out[l], pa.k[l] = p.k[l], pa.groups[l] = p.groups[l], pa.row0[l] = p.row0[l];
-        pa.w_off[l] = p.w_off[l];
-    }
-    pa.n = p.n;
-    pa.wF = saved, pa.wB = saved + p.w_total, pa.invn = saved + 2 * p.w_total;
-    hipLaunchKernelGGL(cs_prep_kernel, dim3((unsigned)p.rows), dim3(256), 0, stream, pa);
-    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = launch_stack_prep<TapMajorLayout>(p, g, v, saved, stream)) return e;
     for (int l = 0; l < p.n; ++l) {
         const bool last = l == p.n - 1;
         ConvArgs a{};
@@ -521,7 +382,7 @@ hipError_t launch_convstack_forward(const ConvStackPlan &p, const float *x, int6
     return hipSuccess;
 }
 
-hipError_t launch_convstack_backward(const ConvStackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_convstack_backward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                      const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
                                      float *const *dv, float *const *dbias, float *ws, hipStream_t stream)
 {
@@ -533,8 +394,8 @@ hipError_t launch_convstack_backward(const ConvStackPlan &p, const float *x, int
             WgradArgs a{};
             a.gz = gz, a.in = in, a.part = ws + p.part_off[l], a.bpart = ws + p.bpart_off[l];
             a.Cin = p.c_in[l], a.Cout = p.c_out[l], a.cin_g = cin_g, a.cout_g = cout_g, a.K = p.k[l], a.dil = p.dil[l];
-            a.Fin = (int)p.F[l], a.Fout = (int)p.F[l + 1], a.per = p.per, a.B = B, a.nseg = p.nseg[l];
-            if (hipError_t e = launch_wgrad(a, p.groups[l], p.nchunk, stream)) return e;
+            a.Fin = (int)p.F[l], a.Fout = (int)p.F[l + 1], a.per = p.per[l], a.B = B, a.nseg = p.nseg[l];
+            if (hipError_t e = launch_wgrad(a, p.groups[l], p.nchunk[l], stream)) return e;
         }
         if (l == 0 && !gx) break;
         float *dst = l ? ws + ((p.n - 1 - l) & 1) * p.gz_size : gx;
@@ -549,19 +410,7 @@ hipError_t launch_convstack_backward(const ConvStackPlan &p, const float *x, int
         if (hipError_t e = launch_conv(a, B, p.groups[l], stream)) return e;
         gz = dst;
     }
-    if (dg) {
-        WnormArgs a{};
-        for (int l = 0; l < p.n; ++l) {
-            a.g[l] = g[l], a.v[l] = v[l], a.dg[l] = dg[l], a.dv[l] = dv[l], a.db[l] = dbias[l];
-            a.part[l] = ws + p.part_off[l], a.bpart[l] = ws + p.bpart_off[l];
-            a.c_out[l] = p.c_out[l], a.rowlen[l] = (p.c_in[l] / p.groups[l]) * p.k[l], a.row0[l] = p.row0[l];
-            a.nparts[l] = (int64_t)p.nchunk * p.nseg[l];
-        }
-        a.n = p.n, a.invn = saved + 2 * p.w_total;
-        hipLaunchKernelGGL(cs_wnorm_kernel, dim3((unsigned)p.rows), dim3(256), 0, stream, a);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    return dg ? launch_stack_wnorm(p, p.n, g, v, dg, dv, dbias, saved, ws, stream) : hipSuccess;
 }
 
 }  // namespace ntm

@@ -1,132 +1,50 @@
 // The conv stack of the reference's spectral critics (SpecCrit, code/critics.py:181-259) behind the spectrogram: n weight-normed
-// Conv1d(c_in, c_out, k, groups) layers, stride 1, dilation 1, no padding, LeakyReLU(0.2) after every layer but the last -- forward,
-// data gradient, weight gradient and the weight-norm adjoint, fp32 in and fp32 accumulate on v_mfma_f32_16x16x4_f32 (exact fp32:
-// the matrix pipe's fmaf chain).
+// Conv1d(c_in, c_out, k, groups) layers, stride 1, dilation 1, no padding, LeakyReLU(0.2) after every layer but the last.  What it
+// shares with the dilated and the MelGAN family (the plan, weight preparation, weight-norm adjoint) is convstack_common.h; this
+// file holds its GEMM kernels: the SLAB fetch form of the conv kernel with the log head, its weight gradient, and the chunk rule.
+// Tile shapes as in convstack_kernels.hip.
 //
-// crit_prep_kernel     one launch for all layers, one workgroup per output channel: |v| over (c_in/groups, k), w = v * (g / |v|) in
-//                      the two layouts the conv kernel reads, and 1/|v| for the adjoint.
-//                        wF[k][ci][CO]   (ci within the group, CO every output channel)          -- forward
-//                        wB[j][co][CI]   (co within the group, CI every input channel) = w[co][ci][K-1-j]   -- data gradient
 // crit_conv_kernel     the implicit GEMM along the frames: out[b][m][f] = sum_{c,j} W[j][c][m] in[b][c][f + j + off], one workgroup
 //                      per (stream, group, tile of output channels, tile of frames).  A slab of 16 input channels x (tile + K - 1)
 //                      frames sits in LDS once and every tap reads it shifted (the im2col matrix never exists); the weights follow
-//                      4 taps at a time.  A wave's MFMA takes 4 consecutive input channels of one tap as its K = 4.
-//                        forward        off = 0,  W = wF, epilogue bias -> LeakyReLU (the last layer: bias); the HEAD form reads
-//                                       log10(max(x, floor)) as it fills the slab
+//                      4 taps at a time (TapMajorLayout).  A wave's MFMA takes 4 consecutive input channels of one tap as its K = 4.
+//                        forward        off = 0,  W = wF; the HEAD form reads log10(max(x, floor)) as it fills the slab
 //                        data gradient  the same sum with the roles of the channels swapped: in = gz (the gradient at the layer's
-//                                       pre-activation), off = -(K-1) with zeros outside, W = wB; epilogue: times the LeakyReLU
-//                                       slope of the layer below, recovered from the sign of its saved output (so every stored gz is
-//                                       already a pre-activation gradient), or the HEAD's 1 / (x ln 10) where x >= floor
+//                                       pre-activation), off = -(K-1) with zeros outside, W = wB; the epilogue of the first layer
+//                                       under a log head is EPI_HEAD
+//                      Epilogues: forward, bias -> LeakyReLU(0.2) (the last layer: bias).  Data gradient: times the LeakyReLU
+//                      slope of the layer below, recovered from the sign of its saved output (y > 0 <=> pre > 0 as slope > 0;
+//                      y == 0 takes the slope, torch's choice), so every stored gz is already a pre-activation gradient;
+//                      EPI_HEAD, the first layer under the log head: 1 / (x ln 10) where x >= floor, else 0.
 //                      Order of addition of one output: per slab of 16 input channels a sum from 0, taps ascending and per tap
 //                      the channels in fours (one MFMA each, its K = 4 an fmaf chain); the slab sums are then added in ascending
 //                      order -- a function of the layer alone, so a stream's result does not depend on its batch.  The loads of
 //                      the next step (slab, 4 taps) are in flight during the MFMAs of the current one.
 // crit_wgrad_kernel    dW[co][ci][k] = sum_{b,f} gz[b][co][f] in[b][ci][f + k]: GEMM with M = co, N = (ci, k) flattened as dW is
-//                      stored, reduction over the frames (64 per step, the MFMA's K = 4 consecutive frames).  The streams are cut
-//                      into at most 32 contiguous chunks; a workgroup adds the streams of its chunk in order and stores ONE partial
-//                      tile, no atomics.  The workgroups of the first N tile also add up the rows of gz (the bias gradient).
-// crit_wnorm_kernel    one launch for all layers, one workgroup per output channel: adds the chunk partials in chunk order, then
-//                      dg = sum(dW v) / |v|, dv = (g / |v|) (dW - v sum(dW v) / |v|^2), dbias = the sum of the row partials.
-//
-// Two tile shapes per GEMM kernel: 64 output channels x 64 columns (2 x 2 waves of 32 x 32) where a group has more than 16
-// output channels, else 16 x 128 (16 x 64 for the weight gradient), four waves side by side.  Every valid (c_in, c_out, k,
-// groups) runs on them: edges are predicated, there is no second code path.
-#include "ntm.h"
-#include "ntm_common.h"
+//                      stored, reduction over the frames (64 per step, the MFMA's K = 4 consecutive frames), the X operand a slab
+//                      in LDS (every column a shifted read of it) and a SINGLE-level sum over the frames.
+//                      Chunk rule: the streams in at most 32 contiguous chunks, one segment; a workgroup adds the streams of its
+//                      chunk in order and stores ONE partial tile, no atomics.
+#include "convstack_common.h"
 
 namespace ntm {
 
 constexpr int kCritMaxChunks = 32;
 
-void crit_plan(CritPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer *L)
+void crit_plan(StackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer *L)
 {
-    p.n = n;
-    p.F[0] = F0;
-    p.w_total = 0;
-    p.rows = 0;
+    stack_plan_layers(p, B, F0, n, L, true, [&](int l, int64_t F) { return F - L[l].k + 1; });
     for (int l = 0; l < n; ++l) {
-        p.c_in[l] = L[l].c_in, p.c_out[l] = L[l].c_out, p.k[l] = L[l].k, p.groups[l] = L[l].groups;
-        p.F[l + 1] = p.F[l] - L[l].k + 1;
-        p.w_off[l] = p.w_total;
-        p.w_total += (int64_t)L[l].c_out * (L[l].c_in / L[l].groups) * L[l].k;
-        p.row0[l] = p.rows;
-        p.rows += L[l].c_out;
+        stack_stream_chunks(B, kCritMaxChunks, p.nchunk[l], p.per[l]);
+        p.seg[l] = p.F[l + 1], p.nseg[l] = 1;
     }
-    int64_t at = 2 * p.w_total + p.rows;
-    p.gz_size = 0;
-    for (int l = 0; l + 1 < n; ++l) {
-        p.act_off[l] = at;
-        const int64_t sz = B * p.c_out[l] * p.F[l + 1];
-        at += sz;
-        if (sz > p.gz_size) p.gz_size = sz;
-    }
-    p.saved_total = at;
-    p.nchunk = (int)(B < kCritMaxChunks ? (B > 0 ? B : 1) : kCritMaxChunks);
-    p.per = (int)((B + p.nchunk - 1) / p.nchunk);
-    if (p.per < 1) p.per = 1;
-    p.nchunk = (int)((B + p.per - 1) / p.per);
-    int64_t w = 2 * p.gz_size;
-    for (int l = 0; l < n; ++l) {
-        p.part_off[l] = w;
-        w += (int64_t)p.nchunk * ((int64_t)L[l].c_out * (L[l].c_in / L[l].groups) * L[l].k);
-        p.bpart_off[l] = w;
-        w += (int64_t)p.nchunk * L[l].c_out;
-    }
-    p.ws_total = w;
+    stack_plan_partials(p);
 }
 
 namespace {
 
 constexpr float kSlope = 0.2f;
 constexpr float kLn10 = 2.302585092994046f;
-
-// sum over the workgroup in a fixed tree order; every thread gets it
-template <int NT>
-__device__ __forceinline__ float block_sum(float x, float *red)
-{
-    const int tid = threadIdx.x;
-    red[tid] = x;
-    __syncthreads();
-#pragma unroll
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-struct PrepArgs {
-    const float *g[kCritMaxLayers], *v[kCritMaxLayers];
-    int c_in[kCritMaxLayers], c_out[kCritMaxLayers], k[kCritMaxLayers], groups[kCritMaxLayers], row0[kCritMaxLayers];
-    int64_t w_off[kCritMaxLayers];
-    int n;
-    float *wF, *wB, *invn;
-};
-
-__global__ __launch_bounds__(256) void crit_prep_kernel(PrepArgs a)
-{
-    __shared__ float red[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    int l = 0;
-    while (l + 1 < a.n && row >= a.row0[l + 1]) ++l;
-    const int co = row - a.row0[l], K = a.k[l], cin_g = a.c_in[l] / a.groups[l], cout_g = a.c_out[l] / a.groups[l];
-    const int n = cin_g * K, grp = co / cout_g, co_l = co - grp * cout_g;
-    const float *v = a.v[l] + (int64_t)co * n;
-    float s = 0.0f;
-    for (int j = tid; j < n; j += 256) s = fmaf(v[j], v[j], s);
-    const float norm = sqrtf(block_sum<256>(s, red));
-    const float scale = a.g[l][co] / norm;
-    float *wF = a.wF + a.w_off[l], *wB = a.wB + a.w_off[l];
-    for (int j = tid; j < n; j += 256) {
-        const int ci = j / K, k = j - ci * K;
-        const float w = v[j] * scale;
-        wF[((int64_t)k * cin_g + ci) * a.c_out[l] + co] = w;
-        wB[((int64_t)(K - 1 - k) * cout_g + co_l) * a.c_in[l] + grp * cin_g + ci] = w;
-    }
-    if (tid == 0) a.invn[row] = 1.0f / norm;
-}
 
 enum { EPI_BIAS_LRELU = 0, EPI_BIAS = 1, EPI_MASK = 2, EPI_HEAD = 3, EPI_NONE = 4 };
 
@@ -381,46 +299,6 @@ __global__ __launch_bounds__(256) void crit_wgrad_kernel(WgradArgs a)
         a.bpart[(int64_t)chunk * a.Cout + grp * a.cout_g + m0 + tid] = bsum;
 }
 
-struct WnormArgs {
-    const float *g[kCritMaxLayers], *v[kCritMaxLayers];
-    float *dg[kCritMaxLayers], *dv[kCritMaxLayers], *db[kCritMaxLayers];
-    const float *part[kCritMaxLayers], *bpart[kCritMaxLayers];
-    int c_out[kCritMaxLayers], rowlen[kCritMaxLayers], row0[kCritMaxLayers];
-    int n, nchunk;
-    const float *invn;
-};
-
-__global__ __launch_bounds__(256) void crit_wnorm_kernel(WnormArgs a)
-{
-    __shared__ float red[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    int l = 0;
-    while (l + 1 < a.n && row >= a.row0[l + 1]) ++l;
-    const int co = row - a.row0[l], n = a.rowlen[l];
-    const int64_t cstride = (int64_t)a.c_out[l] * n;
-    const float *v = a.v[l] + (int64_t)co * n, *p = a.part[l] + (int64_t)co * n;
-    float s = 0.0f;
-    for (int j = tid; j < n; j += 256) {
-        float dw = p[j];
-        for (int c = 1; c < a.nchunk; ++c) dw += p[c * cstride + j];
-        s = fmaf(dw, v[j], s);
-    }
-    const float dot = block_sum<256>(s, red);
-    const float inv = a.invn[row], scale = a.g[l][co] * inv, proj = dot * inv * inv;
-    float *dv = a.dv[l] + (int64_t)co * n;
-    for (int j = tid; j < n; j += 256) {
-        float dw = p[j];
-        for (int c = 1; c < a.nchunk; ++c) dw += p[c * cstride + j];
-        dv[j] = scale * (dw - v[j] * proj);
-    }
-    if (tid == 0) {
-        a.dg[l][co] = dot * inv;
-        float sb = a.bpart[l][co];
-        for (int c = 1; c < a.nchunk; ++c) sb += a.bpart[l][(int64_t)c * a.c_out[l] + co];
-        a.db[l][co] = sb;
-    }
-}
-
 hipError_t launch_conv(ConvArgs a, int64_t B, int groups, hipStream_t stream)
 {
     const bool narrow = a.cout_g <= 16;
@@ -455,19 +333,10 @@ hipError_t launch_wgrad(WgradArgs a, int groups, int nchunk, hipStream_t stream)
 
 }  // namespace
 
-hipError_t launch_speccrit_forward(const CritPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
+hipError_t launch_speccrit_forward(const StackPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
                                    const float *const *v, const float *const *bias, float *saved, float *out, hipStream_t stream)
 {
-    PrepArgs pa{};
-    for (int l = 0; l < p.n; ++l) {
-        pa.g[l] = g[l], pa.v[l] = v[l];
-        pa.c_in[l] = p.c_in[l], pa.c_out[l] = p.c_out[l], pa.k[l] = p.k[l], pa.groups[l] = p.groups[l], pa.row0[l] = p.row0[l];
-        pa.w_off[l] = p.w_off[l];
-    }
-    pa.n = p.n;
-    pa.wF = saved, pa.wB = saved + p.w_total, pa.invn = saved + 2 * p.w_total;
-    hipLaunchKernelGGL(crit_prep_kernel, dim3((unsigned)p.rows), dim3(256), 0, stream, pa);
-    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = launch_stack_prep<TapMajorLayout>(p, g, v, saved, stream)) return e;
     for (int l = 0; l < p.n; ++l) {
         const bool last = l == p.n - 1;
         ConvArgs a{};
@@ -484,7 +353,7 @@ hipError_t launch_speccrit_forward(const CritPlan &p, const float *x, int64_t B,
     return hipSuccess;
 }
 
-hipError_t launch_speccrit_backward(const CritPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
+hipError_t launch_speccrit_backward(const StackPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
                                     const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
                                     float *const *dv, float *const *dbias, float *ws, hipStream_t stream)
 {
@@ -497,8 +366,8 @@ hipError_t launch_speccrit_backward(const CritPlan &p, const float *x, int64_t B
             WgradArgs a{};
             a.gz = gz, a.in = in, a.part = ws + p.part_off[l], a.bpart = ws + p.bpart_off[l];
             a.Cin = p.c_in[l], a.Cout = p.c_out[l], a.cin_g = cin_g, a.cout_g = cout_g, a.K = p.k[l];
-            a.Fin = (int)p.F[l], a.Fout = (int)p.F[l + 1], a.in_log = in_log, a.floor_ = log_floor, a.per = p.per, a.B = B;
-            if (hipError_t e = launch_wgrad(a, p.groups[l], p.nchunk, stream)) return e;
+            a.Fin = (int)p.F[l], a.Fout = (int)p.F[l + 1], a.in_log = in_log, a.floor_ = log_floor, a.per = p.per[l], a.B = B;
+            if (hipError_t e = launch_wgrad(a, p.groups[l], p.nchunk[l], stream)) return e;
         }
         if (l == 0 && !gx) break;
         float *dst = l ? ws + ((p.n - 1 - l) & 1) * p.gz_size : gx;
@@ -512,18 +381,7 @@ hipError_t launch_speccrit_backward(const CritPlan &p, const float *x, int64_t B
         if (hipError_t e = launch_conv(a, B, p.groups[l], stream)) return e;
         gz = dst;
     }
-    if (dg) {
-        WnormArgs a{};
-        for (int l = 0; l < p.n; ++l) {
-            a.g[l] = g[l], a.v[l] = v[l], a.dg[l] = dg[l], a.dv[l] = dv[l], a.db[l] = dbias[l];
-            a.part[l] = ws + p.part_off[l], a.bpart[l] = ws + p.bpart_off[l];
-            a.c_out[l] = p.c_out[l], a.rowlen[l] = (p.c_in[l] / p.groups[l]) * p.k[l], a.row0[l] = p.row0[l];
-        }
-        a.n = p.n, a.nchunk = p.nchunk, a.invn = saved + 2 * p.w_total;
-        hipLaunchKernelGGL(crit_wnorm_kernel, dim3((unsigned)p.rows), dim3(256), 0, stream, a);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    return dg ? launch_stack_wnorm(p, p.n, g, v, dg, dv, dbias, saved, ws, stream) : hipSuccess;
 }
 
 }  // namespace ntm

@@ -53,6 +53,36 @@ int hip_fail(hipError_t e, const char *where)
 {
     return fail(NTM_EHIP, std::string(where) + ": " + hipGetErrorString(e));
 }
+
+// The size checks every entry point of a critic conv stack makes (ntm_speccrit, ntm_convstack, ntm_sconvstack).  Shared: sizes, n_layers, channel range, k, groups, chaining and, after
+// the last layer, B * C * F < 2^31.  A family adds `params` (what it checks between k and groups: dilation; stride and pad) and
+// `frames` (what it checks of the frames that reach the layer, and how the layer changes them).  spectral: the first layer
+// reads the bins of the largest transform, so C0 and its c_in may be 1025; every other channel count is at most 1024.
+template <class Layer, class Params, class Frames>
+int stack_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const Layer *layers, int max_layers,
+                bool spectral, Params params, Frames frames)
+{
+    if (B < 0 || C0 < 1 || F0 < 1) return fail(NTM_EINVAL, w + ": bad size");
+    if (n_layers < 1 || n_layers > max_layers)
+        return fail(NTM_EINVAL, w + ": n_layers must lie in [1, " + std::to_string(max_layers) + "]");
+    if (!layers) return fail(NTM_EINVAL, w + ": null pointer");
+    const int max_c0 = spectral ? 1025 : 1024;
+    if (spectral && C0 > 1025) return fail(NTM_EINVAL, w + ": C0 must lie in [1, 1025] (the bins of the largest transform)");
+    int64_t c = C0, F = F0;
+    for (int l = 0; l < n_layers; ++l) {
+        const Layer &y = layers[l];
+        if (c > max_c0 || y.c_in < 1 || y.c_in > (l ? 1024 : max_c0) || y.c_out < 1 || y.c_out > 1024)
+            return fail(NTM_EINVAL, w + ": channel counts must lie in [1, 1024]");
+        if (y.k < 1 || y.k > 64) return fail(NTM_EINVAL, w + ": k must lie in [1, 64]");
+        if (int rc = params(l, y, F)) return rc;
+        if (y.groups < 1 || y.c_in % y.groups || y.c_out % y.groups) return fail(NTM_EINVAL, w + ": groups must divide both channel counts");
+        if (y.c_in != c) return fail(NTM_EINVAL, w + ": c_in of a layer must be c_out of the layer before it (C0 for the first)");
+        if (int rc = frames(l, y, c, F)) return rc;
+        c = y.c_out;
+    }
+    if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+    return NTM_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -620,44 +650,126 @@ int ntm_spectrogram_grad(const float *y, const float *gP, int64_t B, int64_t T, 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_spectrogram_grad");
 }
 
-// the argument checks the four ntm_speccrit entry points share, then the plan
+// ---- the three critic conv stacks (the size checks they share: stack_sizes, above) ----
 static int speccrit_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers,
-                          ntm::CritPlan &p)
+                          ntm::StackPlan &p)
 {
-    if (B < 0 || C0 < 1 || F0 < 1) return fail(NTM_EINVAL, w + ": bad size");
-    if (n_layers < 1 || n_layers > 8) return fail(NTM_EINVAL, w + ": n_layers must lie in [1, 8]");
-    if (!layers) return fail(NTM_EINVAL, w + ": null pointer");
-    if (C0 > 1025) return fail(NTM_EINVAL, w + ": C0 must lie in [1, 1025] (the bins of the largest transform)");
-    int64_t c = C0, F = F0;
-    for (int l = 0; l < n_layers; ++l) {
-        const ntm_conv1d_layer &y = layers[l];
-        if (y.c_in < 1 || y.c_in > (l ? 1024 : 1025) || y.c_out < 1 || y.c_out > 1024)
-            return fail(NTM_EINVAL, w + ": channel counts must lie in [1, 1024]");
-        if (y.k < 1 || y.k > 64) return fail(NTM_EINVAL, w + ": k must lie in [1, 64]");
-        if (y.groups < 1 || y.c_in % y.groups || y.c_out % y.groups) return fail(NTM_EINVAL, w + ": groups must divide both channel counts");
-        if (y.c_in != c) return fail(NTM_EINVAL, w + ": c_in of a layer must be c_out of the layer before it (C0 for the first)");
-        if (y.k > F) return fail(NTM_EINVAL, w + ": k is larger than the frames that reach the layer");
-        if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
-        F -= y.k - 1;
-        c = y.c_out;
-    }
-    if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
-    ntm::crit_plan(p, B, C0, F0, n_layers, layers);
+    const int rc = stack_sizes(
+        w, B, C0, F0, n_layers, layers, 8, true, [](int, const ntm_conv1d_layer &, int64_t) { return NTM_OK; },
+        [&](int, const ntm_conv1d_layer &y, int64_t c, int64_t &F) {
+            if (y.k > F) return fail(NTM_EINVAL, w + ": k is larger than the frames that reach the layer");
+            if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+            F -= y.k - 1;
+            return NTM_OK;
+        });
+    if (rc == NTM_OK) ntm::crit_plan(p, B, C0, F0, n_layers, layers);
+    return rc;
+}
+
+static int convstack_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers,
+                           ntm::StackPlan &p)
+{
+    const int rc = stack_sizes(
+        w, B, C0, F0, n_layers, layers, ntm::kStackMaxLayers, false,
+        [&](int, const ntm_conv1d_layer_d &y, int64_t) {
+            if (y.dilation < 1 || y.dilation > (1 << 20)) return fail(NTM_EINVAL, w + ": dilation must lie in [1, 2^20]");
+            return NTM_OK;
+        },
+        [&](int, const ntm_conv1d_layer_d &y, int64_t c, int64_t &F) {
+            const int64_t span = (int64_t)(y.k - 1) * y.dilation;
+            if (span + 1 > F) return fail(NTM_EINVAL, w + ": (k - 1) * dilation + 1 is larger than the frames that reach the layer");
+            if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+            F -= span;
+            return NTM_OK;
+        });
+    if (rc == NTM_OK) ntm::convstack_plan(p, B, C0, F0, n_layers, layers);
+    return rc;
+}
+
+static int sconvstack_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers,
+                            ntm::StackPlan &p)
+{
+    const int rc = stack_sizes(
+        w, B, C0, F0, n_layers, layers, ntm::kStackMaxLayers, false,
+        [&](int l, const ntm_conv1d_layer_s &y, int64_t F) {
+            if (y.stride < 1 || y.stride > 64) return fail(NTM_EINVAL, w + ": stride must lie in [1, 64]");
+            if (y.pad < 0 || y.pad > y.k - 1) return fail(NTM_EINVAL, w + ": pad must lie in [0, k - 1]");
+            if (y.pad_mode != 0 && y.pad_mode != 1) return fail(NTM_EINVAL, w + ": pad_mode must be 0 (zeros) or 1 (reflect)");
+            if (y.pad_mode == 1 && l != 0) return fail(NTM_EINVAL, w + ": pad_mode 1 (reflect) is built for the first layer only");
+            if (y.pad_mode == 1 && y.pad >= F) return fail(NTM_EINVAL, w + ": a reflected pad must be smaller than F0");
+            return NTM_OK;
+        },
+        [&](int l, const ntm_conv1d_layer_s &y, int64_t c, int64_t &F) {
+            if (F + 2 * (int64_t)y.pad < y.k) return fail(NTM_EINVAL, w + ": a layer has no output frame (F + 2 pad < k)");
+            if (B * c * (F + (l == 0 ? 2 * (int64_t)y.pad : 0)) > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+            // one workgroup of 256 threads per (stream, 64 output frames) forward, per (stream, phase, 64 columns) in the data
+            // gradient, whose columns are the frames of the (padded) input over the stride: both below 2^24 workgroups (2^32
+            // threads per launch)
+            const int64_t Fin = F + (y.pad_mode == 1 ? 2 * (int64_t)y.pad : 0), pad_eff = y.pad_mode == 1 ? 0 : y.pad;
+            F = (F + 2 * (int64_t)y.pad - y.k) / y.stride + 1;
+            if (B * y.c_out * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
+            const int64_t cols = (Fin - 1 + pad_eff) / y.stride + 1;
+            if (B * ((F + 63) / 64) >= (1 << 24) || B * y.stride * ((cols + 63) / 64) >= (1 << 24))
+                return fail(NTM_EINVAL, w + ": B * stride * ceil(frames / (64 stride)) must be below 2^24 (workgroups of one launch)");
+            return NTM_OK;
+        });
+    if (rc == NTM_OK) ntm::sconv_plan(p, B, C0, F0, n_layers, layers);
+    return rc;
+}
+
+// the pointer checks of a forward entry point; out: the output, or the strided family's array of them, outs (else null)
+static int stack_forward_ptrs(const std::string &w, int n_layers, const float *x, const float *const *g, const float *const *v,
+                              const float *const *bias, const float *saved, const void *out, float *const *outs)
+{
+    if (!x || !g || !v || !bias || !saved || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int l = 0; l < n_layers; ++l)
+        if (!g[l] || !v[l] || !bias[l] || (outs && !outs[l])) return fail(NTM_EINVAL, w + ": null pointer");
     return NTM_OK;
+}
+
+// ... of a backward entry point: the gradient arrives at the output (gout), or per_layer (the strided family) at the outputs of
+// the layers: outs and gouts, one tensor per layer, of which at least one gouts entry is not null; gx aliases none of them
+static int stack_backward_ptrs(const std::string &w, int n_layers, const float *x, const float *const *g, const float *const *v,
+                               const float *saved, const float *gx, float *const *dg, float *const *dv, float *const *dbias,
+                               const float *ws, const float *gout, bool per_layer, const float *const *outs,
+                               const float *const *gouts)
+{
+    if (!x || !g || !v || !saved || (per_layer ? !outs || !gouts : !gout) || !ws) return fail(NTM_EINVAL, w + ": null pointer");
+    if (dg && (!dv || !dbias)) return fail(NTM_EINVAL, w + ": null pointer (dg, dv and dbias come together)");
+    const std::string alias = w + (per_layer ? ": gx must not alias x, outs or gouts" : ": gx must not alias x or gout");
+    bool any = !per_layer;
+    for (int l = 0; l < n_layers; ++l) {
+        if (!g[l] || !v[l] || (per_layer && !outs[l]) || (dg && (!dg[l] || !dv[l] || !dbias[l])))
+            return fail(NTM_EINVAL, w + ": null pointer");
+        if (!per_layer) continue;
+        any = any || gouts[l];
+        if (gx && (gx == outs[l] || gx == gouts[l])) return fail(NTM_EINVAL, alias);
+    }
+    if (!any) return fail(NTM_EINVAL, w + ": every entry of gouts is null (at least one gradient must arrive)");
+    if (gx && (gx == x || gx == gout)) return fail(NTM_EINVAL, alias);
+    return NTM_OK;
+}
+
+static int speccrit_floor(const std::string &w, float log_floor)
+{
+    return log_floor >= 0.0f ? NTM_OK : fail(NTM_EINVAL, w + ": log_floor must be positive, or 0 for no log");
+}
+
+static int stack_slope(const std::string &w, float slope)
+{
+    return slope > 0.0f && slope < 1.0f ? NTM_OK : fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
 }
 
 int64_t ntm_speccrit_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers)
 {
-    ntm::CritPlan p;
-    if (speccrit_sizes("ntm_speccrit_saved_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
-    return p.saved_total;
+    ntm::StackPlan p;
+    return speccrit_sizes("ntm_speccrit_saved_floats", B, C0, F0, n_layers, layers, p) == NTM_OK ? p.saved_total : -1;
 }
 
 int64_t ntm_speccrit_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer *layers)
 {
-    ntm::CritPlan p;
-    if (speccrit_sizes("ntm_speccrit_workspace_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
-    return p.ws_total;
+    ntm::StackPlan p;
+    return speccrit_sizes("ntm_speccrit_workspace_floats", B, C0, F0, n_layers, layers, p) == NTM_OK ? p.ws_total : -1;
 }
 
 int ntm_speccrit_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float log_floor, int n_layers,
@@ -665,13 +777,11 @@ int ntm_speccrit_forward(const float *x, int64_t B, int64_t C0, int64_t F0, floa
                          float *saved, float *out, void *stream)
 {
     const std::string w("ntm_speccrit_forward");
-    ntm::CritPlan p;
+    ntm::StackPlan p;
     if (int rc = speccrit_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
-    if (!(log_floor >= 0.0f)) return fail(NTM_EINVAL, w + ": log_floor must be positive, or 0 for no log");
+    if (int rc = speccrit_floor(w, log_floor)) return rc;
     if (B == 0) return NTM_OK;
-    if (!x || !g || !v || !bias || !saved || !out) return fail(NTM_EINVAL, w + ": null pointer");
-    for (int l = 0; l < n_layers; ++l)
-        if (!g[l] || !v[l] || !bias[l]) return fail(NTM_EINVAL, w + ": null pointer");
+    if (int rc = stack_forward_ptrs(w, n_layers, x, g, v, bias, saved, out, nullptr)) return rc;
     hipError_t e = ntm::launch_speccrit_forward(p, x, B, log_floor, g, v, bias, saved, out, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_speccrit_forward");
 }
@@ -682,58 +792,25 @@ int ntm_speccrit_backward(const float *x, int64_t B, int64_t C0, int64_t F0, flo
                           void *stream)
 {
     const std::string w("ntm_speccrit_backward");
-    ntm::CritPlan p;
+    ntm::StackPlan p;
     if (int rc = speccrit_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
-    if (!(log_floor >= 0.0f)) return fail(NTM_EINVAL, w + ": log_floor must be positive, or 0 for no log");
+    if (int rc = speccrit_floor(w, log_floor)) return rc;
     if (B == 0) return NTM_OK;
-    if (!x || !g || !v || !saved || !gout || !ws) return fail(NTM_EINVAL, w + ": null pointer");
-    if (dg && (!dv || !dbias)) return fail(NTM_EINVAL, w + ": null pointer (dg, dv and dbias come together)");
-    for (int l = 0; l < n_layers; ++l)
-        if (!g[l] || !v[l] || (dg && (!dg[l] || !dv[l] || !dbias[l]))) return fail(NTM_EINVAL, w + ": null pointer");
-    if (gx && (gx == x || gx == gout)) return fail(NTM_EINVAL, w + ": gx must not alias x or gout");
+    if (int rc = stack_backward_ptrs(w, n_layers, x, g, v, saved, gx, dg, dv, dbias, ws, gout, false, nullptr, nullptr)) return rc;
     hipError_t e = ntm::launch_speccrit_backward(p, x, B, log_floor, g, v, saved, gout, gx, dg, dv, dbias, ws, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_speccrit_backward");
 }
 
-// the argument checks the four ntm_convstack entry points share, then the plan
-static int convstack_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers,
-                           ntm::ConvStackPlan &p)
-{
-    if (B < 0 || C0 < 1 || F0 < 1) return fail(NTM_EINVAL, w + ": bad size");
-    if (n_layers < 1 || n_layers > ntm::kConvStackMaxLayers) return fail(NTM_EINVAL, w + ": n_layers must lie in [1, 16]");
-    if (!layers) return fail(NTM_EINVAL, w + ": null pointer");
-    int64_t c = C0, F = F0;
-    for (int l = 0; l < n_layers; ++l) {
-        const ntm_conv1d_layer_d &y = layers[l];
-        if (c > 1024 || y.c_in < 1 || y.c_in > 1024 || y.c_out < 1 || y.c_out > 1024)
-            return fail(NTM_EINVAL, w + ": channel counts must lie in [1, 1024]");
-        if (y.k < 1 || y.k > 64) return fail(NTM_EINVAL, w + ": k must lie in [1, 64]");
-        if (y.dilation < 1 || y.dilation > (1 << 20)) return fail(NTM_EINVAL, w + ": dilation must lie in [1, 2^20]");
-        if (y.groups < 1 || y.c_in % y.groups || y.c_out % y.groups) return fail(NTM_EINVAL, w + ": groups must divide both channel counts");
-        if (y.c_in != c) return fail(NTM_EINVAL, w + ": c_in of a layer must be c_out of the layer before it (C0 for the first)");
-        const int64_t span = (int64_t)(y.k - 1) * y.dilation;
-        if (span + 1 > F) return fail(NTM_EINVAL, w + ": (k - 1) * dilation + 1 is larger than the frames that reach the layer");
-        if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
-        F -= span;
-        c = y.c_out;
-    }
-    if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
-    ntm::convstack_plan(p, B, C0, F0, n_layers, layers);
-    return NTM_OK;
-}
-
 int64_t ntm_convstack_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers)
 {
-    ntm::ConvStackPlan p;
-    if (convstack_sizes("ntm_convstack_saved_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
-    return p.saved_total;
+    ntm::StackPlan p;
+    return convstack_sizes("ntm_convstack_saved_floats", B, C0, F0, n_layers, layers, p) == NTM_OK ? p.saved_total : -1;
 }
 
 int64_t ntm_convstack_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_d *layers)
 {
-    ntm::ConvStackPlan p;
-    if (convstack_sizes("ntm_convstack_workspace_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
-    return p.ws_total;
+    ntm::StackPlan p;
+    return convstack_sizes("ntm_convstack_workspace_floats", B, C0, F0, n_layers, layers, p) == NTM_OK ? p.ws_total : -1;
 }
 
 int ntm_convstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
@@ -741,13 +818,11 @@ int ntm_convstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, flo
                           float *saved, float *out, void *stream)
 {
     const std::string w("ntm_convstack_forward");
-    ntm::ConvStackPlan p;
+    ntm::StackPlan p;
     if (int rc = convstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
-    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (int rc = stack_slope(w, slope)) return rc;
     if (B == 0) return NTM_OK;
-    if (!x || !g || !v || !bias || !saved || !out) return fail(NTM_EINVAL, w + ": null pointer");
-    for (int l = 0; l < n_layers; ++l)
-        if (!g[l] || !v[l] || !bias[l]) return fail(NTM_EINVAL, w + ": null pointer");
+    if (int rc = stack_forward_ptrs(w, n_layers, x, g, v, bias, saved, out, nullptr)) return rc;
     hipError_t e = ntm::launch_convstack_forward(p, x, B, slope, g, v, bias, saved, out, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_convstack_forward");
 }
@@ -758,67 +833,25 @@ int ntm_convstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, fl
                            void *stream)
 {
     const std::string w("ntm_convstack_backward");
-    ntm::ConvStackPlan p;
+    ntm::StackPlan p;
     if (int rc = convstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
-    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (int rc = stack_slope(w, slope)) return rc;
     if (B == 0) return NTM_OK;
-    if (!x || !g || !v || !saved || !gout || !ws) return fail(NTM_EINVAL, w + ": null pointer");
-    if (dg && (!dv || !dbias)) return fail(NTM_EINVAL, w + ": null pointer (dg, dv and dbias come together)");
-    for (int l = 0; l < n_layers; ++l)
-        if (!g[l] || !v[l] || (dg && (!dg[l] || !dv[l] || !dbias[l]))) return fail(NTM_EINVAL, w + ": null pointer");
-    if (gx && (gx == x || gx == gout)) return fail(NTM_EINVAL, w + ": gx must not alias x or gout");
+    if (int rc = stack_backward_ptrs(w, n_layers, x, g, v, saved, gx, dg, dv, dbias, ws, gout, false, nullptr, nullptr)) return rc;
     hipError_t e = ntm::launch_convstack_backward(p, x, B, slope, g, v, saved, gout, gx, dg, dv, dbias, ws, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_convstack_backward");
 }
 
-// the argument checks the four ntm_sconvstack entry points share, then the plan
-static int sconvstack_sizes(const std::string &w, int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers,
-                            ntm::SConvPlan &p)
-{
-    if (B < 0 || C0 < 1 || F0 < 1) return fail(NTM_EINVAL, w + ": bad size");
-    if (n_layers < 1 || n_layers > ntm::kConvStackMaxLayers) return fail(NTM_EINVAL, w + ": n_layers must lie in [1, 16]");
-    if (!layers) return fail(NTM_EINVAL, w + ": null pointer");
-    int64_t c = C0, F = F0;
-    for (int l = 0; l < n_layers; ++l) {
-        const ntm_conv1d_layer_s &y = layers[l];
-        if (c > 1024 || y.c_in < 1 || y.c_in > 1024 || y.c_out < 1 || y.c_out > 1024)
-            return fail(NTM_EINVAL, w + ": channel counts must lie in [1, 1024]");
-        if (y.k < 1 || y.k > 64) return fail(NTM_EINVAL, w + ": k must lie in [1, 64]");
-        if (y.stride < 1 || y.stride > 64) return fail(NTM_EINVAL, w + ": stride must lie in [1, 64]");
-        if (y.pad < 0 || y.pad > y.k - 1) return fail(NTM_EINVAL, w + ": pad must lie in [0, k - 1]");
-        if (y.pad_mode != 0 && y.pad_mode != 1) return fail(NTM_EINVAL, w + ": pad_mode must be 0 (zeros) or 1 (reflect)");
-        if (y.pad_mode == 1 && l != 0) return fail(NTM_EINVAL, w + ": pad_mode 1 (reflect) is built for the first layer only");
-        if (y.pad_mode == 1 && y.pad >= F) return fail(NTM_EINVAL, w + ": a reflected pad must be smaller than F0");
-        if (y.groups < 1 || y.c_in % y.groups || y.c_out % y.groups) return fail(NTM_EINVAL, w + ": groups must divide both channel counts");
-        if (y.c_in != c) return fail(NTM_EINVAL, w + ": c_in of a layer must be c_out of the layer before it (C0 for the first)");
-        if (F + 2 * (int64_t)y.pad < y.k) return fail(NTM_EINVAL, w + ": a layer has no output frame (F + 2 pad < k)");
-        if (B * c * (F + (l == 0 ? 2 * (int64_t)y.pad : 0)) > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
-        // one workgroup of 256 threads per (stream, 64 output frames) forward, per (stream, phase, 64 columns) in the data gradient,
-        // whose columns are the frames of the (padded) input over the stride: both below 2^24 workgroups (2^32 threads per launch)
-        const int64_t Fin = F + (y.pad_mode == 1 ? 2 * (int64_t)y.pad : 0), pad_eff = y.pad_mode == 1 ? 0 : y.pad;
-        F = (F + 2 * (int64_t)y.pad - y.k) / y.stride + 1;
-        c = y.c_out;
-        if (B * c * F > 0x7fffffff) return fail(NTM_EINVAL, w + ": B * C * F must be below 2^31");
-        const int64_t cols = (Fin - 1 + pad_eff) / y.stride + 1;
-        if (B * ((F + 63) / 64) >= (1 << 24) || B * y.stride * ((cols + 63) / 64) >= (1 << 24))
-            return fail(NTM_EINVAL, w + ": B * stride * ceil(frames / (64 stride)) must be below 2^24 (workgroups of one launch)");
-    }
-    ntm::sconv_plan(p, B, C0, F0, n_layers, layers);
-    return NTM_OK;
-}
-
 int64_t ntm_sconvstack_saved_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers)
 {
-    ntm::SConvPlan p;
-    if (sconvstack_sizes("ntm_sconvstack_saved_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
-    return p.saved_total;
+    ntm::StackPlan p;
+    return sconvstack_sizes("ntm_sconvstack_saved_floats", B, C0, F0, n_layers, layers, p) == NTM_OK ? p.saved_total : -1;
 }
 
 int64_t ntm_sconvstack_workspace_floats(int64_t B, int64_t C0, int64_t F0, int n_layers, const ntm_conv1d_layer_s *layers)
 {
-    ntm::SConvPlan p;
-    if (sconvstack_sizes("ntm_sconvstack_workspace_floats", B, C0, F0, n_layers, layers, p) != NTM_OK) return -1;
-    return p.ws_total;
+    ntm::StackPlan p;
+    return sconvstack_sizes("ntm_sconvstack_workspace_floats", B, C0, F0, n_layers, layers, p) == NTM_OK ? p.ws_total : -1;
 }
 
 int ntm_sconvstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, float slope, int n_layers,
@@ -826,13 +859,11 @@ int ntm_sconvstack_forward(const float *x, int64_t B, int64_t C0, int64_t F0, fl
                            const float *const *bias, float *saved, float *const *outs, void *stream)
 {
     const std::string w("ntm_sconvstack_forward");
-    ntm::SConvPlan p;
+    ntm::StackPlan p;
     if (int rc = sconvstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
-    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (int rc = stack_slope(w, slope)) return rc;
     if (B == 0) return NTM_OK;
-    if (!x || !g || !v || !bias || !saved || !outs) return fail(NTM_EINVAL, w + ": null pointer");
-    for (int l = 0; l < n_layers; ++l)
-        if (!g[l] || !v[l] || !bias[l] || !outs[l]) return fail(NTM_EINVAL, w + ": null pointer");
+    if (int rc = stack_forward_ptrs(w, n_layers, x, g, v, bias, saved, outs, outs)) return rc;
     hipError_t e = ntm::launch_sconvstack_forward(p, x, B, slope, g, v, bias, saved, outs, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_sconvstack_forward");
 }
@@ -843,20 +874,11 @@ int ntm_sconvstack_backward(const float *x, int64_t B, int64_t C0, int64_t F0, f
                             float *const *dg, float *const *dv, float *const *dbias, float *ws, void *stream)
 {
     const std::string w("ntm_sconvstack_backward");
-    ntm::SConvPlan p;
+    ntm::StackPlan p;
     if (int rc = sconvstack_sizes(w, B, C0, F0, n_layers, layers, p)) return rc;
-    if (!(slope > 0.0f && slope < 1.0f)) return fail(NTM_EINVAL, w + ": slope must lie in (0, 1)");
+    if (int rc = stack_slope(w, slope)) return rc;
     if (B == 0) return NTM_OK;
-    if (!x || !g || !v || !saved || !outs || !gouts || !ws) return fail(NTM_EINVAL, w + ": null pointer");
-    if (dg && (!dv || !dbias)) return fail(NTM_EINVAL, w + ": null pointer (dg, dv and dbias come together)");
-    bool any = false;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!g[l] || !v[l] || !outs[l] || (dg && (!dg[l] || !dv[l] || !dbias[l]))) return fail(NTM_EINVAL, w + ": null pointer");
-        any = any || gouts[l];
-        if (gx && (gx == outs[l] || gx == gouts[l])) return fail(NTM_EINVAL, w + ": gx must not alias x, outs or gouts");
-    }
-    if (!any) return fail(NTM_EINVAL, w + ": every entry of gouts is null (at least one gradient must arrive)");
-    if (gx && gx == x) return fail(NTM_EINVAL, w + ": gx must not alias x, outs or gouts");
+    if (int rc = stack_backward_ptrs(w, n_layers, x, g, v, saved, gx, dg, dv, dbias, ws, nullptr, true, outs, gouts)) return rc;
     hipError_t e = ntm::launch_sconvstack_backward(p, x, B, slope, g, v, saved, outs, gouts, gx, dg, dv, dbias, ws, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_sconvstack_backward");
 }

@@ -104,70 +104,46 @@ hipError_t launch_esr_grad_replicas(const float *y, const float *t, int64_t R, i
 hipError_t launch_esr_dcpre_grad_replicas(const float *y, const float *t, int64_t R, int64_t bper, int64_t T, float pole,
                                           const double *sums2, const float *gout, double eps, float *dy, hipStream_t stream);
 hipError_t launch_loss_sums_replicas(const double *rows, int64_t R, int64_t bper, int splits, double *out, hipStream_t stream);
-// the conv stack of the spectral critics (critic_kernels.hip): where everything lies in `saved` and `ws`, filled by crit_plan
-// from sizes ntm_api.hip has checked
-constexpr int kCritMaxLayers = 8;   // include/ntm.h: n_layers in [1, 8]
-struct CritPlan {
+// the three critic conv stacks: the spectral critics (critic_kernels.hip), the dilated stack of the time-domain critic
+// (convstack_kernels.hip) and the strided stack of the MelGAN critic (sconv_kernels.hip).  One record says where everything lies in
+// `saved` and `ws`; each family's planner fills it from sizes ntm_api.hip has checked (the shared part and the kernels the families
+// have in common: convstack_common.h)
+constexpr int kStackMaxLayers = 16;   // include/ntm.h: n_layers in [1, 16] (the spectral family: [1, 8], checked by ntm_api.hip)
+struct StackPlan {
     int n;
-    int c_in[kCritMaxLayers], c_out[kCritMaxLayers], k[kCritMaxLayers], groups[kCritMaxLayers];
-    int64_t F[kCritMaxLayers + 1];           // frames entering layer l; F[n]: frames of the output
-    int64_t w_off[kCritMaxLayers], w_total;  // floats of layer l's weights within wF / wB
-    int row0[kCritMaxLayers], rows;          // output channels counted through the layers
-    int64_t act_off[kCritMaxLayers];         // saved: wF | wB | 1/|v| | outputs of layers 0 .. n-2
-    int64_t saved_total;
-    int nchunk, per;                         // weight gradient: chunks of `per` streams
-    int64_t gz_size;                         // ws: gz ping | gz pong | per layer the chunk partials of dW, then of dbias
-    int64_t part_off[kCritMaxLayers], bpart_off[kCritMaxLayers], ws_total;
+    int c_in[kStackMaxLayers], c_out[kStackMaxLayers], k[kStackMaxLayers], groups[kStackMaxLayers];
+    int dil[kStackMaxLayers];                                                       // the dilated family, else 1
+    int stride[kStackMaxLayers], pad[kStackMaxLayers], reflect[kStackMaxLayers];    // the strided family, else 1, 0, 0
+    int64_t F[kStackMaxLayers + 1];           // frames entering layer l; F[n]: frames of the (last) output
+    int64_t w_off[kStackMaxLayers], w_total;  // floats of layer l's weights within wF / wB
+    int row0[kStackMaxLayers], rows;          // output channels counted through the layers
+    int64_t act_off[kStackMaxLayers];         // saved: wF | wB | 1/|v| | outputs of layers 0 .. n-2 (the strided family: the
+    int64_t saved_total;                      //        outputs are tensors of the caller's, `saved` ends after 1/|v|)
+    int nchunk[kStackMaxLayers], per[kStackMaxLayers];    // weight gradient of layer l: chunks of `per` streams ...
+    int64_t seg[kStackMaxLayers], nseg[kStackMaxLayers];  // ... times segments of `seg` output frames (the family's chunk rule)
+    int64_t gz_size, fold_size;               // ws: gz ping | gz pong | padded gx of a reflected first layer | per layer the
+    int64_t part_off[kStackMaxLayers], bpart_off[kStackMaxLayers], ws_total;   // partials of dW, then of dbias
+    int cin_g(int l) const { return c_in[l] / groups[l]; }
+    int cout_g(int l) const { return c_out[l] / groups[l]; }
+    int64_t w_size(int l) const { return (int64_t)c_out[l] * cin_g(l) * k[l]; }
 };
-void crit_plan(CritPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer *L);
-hipError_t launch_speccrit_forward(const CritPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
+void crit_plan(StackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer *L);
+void convstack_plan(StackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_d *L);
+void sconv_plan(StackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_s *L);
+hipError_t launch_speccrit_forward(const StackPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
                                    const float *const *v, const float *const *bias, float *saved, float *out, hipStream_t stream);
-hipError_t launch_speccrit_backward(const CritPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
+hipError_t launch_speccrit_backward(const StackPlan &p, const float *x, int64_t B, float log_floor, const float *const *g,
                                     const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
                                     float *const *dv, float *const *dbias, float *ws, hipStream_t stream);
-// the dilated conv stack of the time-domain critic (convstack_kernels.hip): the same record with a dilation per layer, up to
-// 16 layers, and a weight-gradient reduction cut over (stream chunk, frame segment)
-constexpr int kConvStackMaxLayers = 16;   // include/ntm.h: n_layers in [1, 16]
-struct ConvStackPlan {
-    int n;
-    int c_in[kConvStackMaxLayers], c_out[kConvStackMaxLayers], k[kConvStackMaxLayers], groups[kConvStackMaxLayers],
-        dil[kConvStackMaxLayers];
-    int64_t F[kConvStackMaxLayers + 1];           // frames entering layer l; F[n]: frames of the output
-    int64_t w_off[kConvStackMaxLayers], w_total;  // floats of layer l's weights within wF / wB
-    int row0[kConvStackMaxLayers], rows;          // output channels counted through the layers
-    int64_t act_off[kConvStackMaxLayers];         // saved: wF | wB | 1/|v| | outputs of layers 0 .. n-2
-    int64_t saved_total;
-    int nchunk, per;                              // weight gradient: chunks of `per` streams ...
-    int64_t nseg[kConvStackMaxLayers];            // ... times segments of 1024 output frames of layer l
-    int64_t gz_size;                              // ws: gz ping | gz pong | per layer the partials of dW, then of dbias
-    int64_t part_off[kConvStackMaxLayers], bpart_off[kConvStackMaxLayers], ws_total;
-};
-void convstack_plan(ConvStackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_d *L);
-hipError_t launch_convstack_forward(const ConvStackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_convstack_forward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                     const float *const *v, const float *const *bias, float *saved, float *out, hipStream_t stream);
-hipError_t launch_convstack_backward(const ConvStackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_convstack_backward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                      const float *const *v, const float *saved, const float *gout, float *gx, float *const *dg,
                                      float *const *dv, float *const *dbias, float *ws, hipStream_t stream);
-// the strided conv stack of the MelGAN critic (sconv_kernels.hip): stride, zero padding and a reflection pad on the first layer;
-// every layer's output is a tensor of the caller's, so `saved` holds the weights alone
-struct SConvPlan {
-    int n;
-    int c_in[kConvStackMaxLayers], c_out[kConvStackMaxLayers], k[kConvStackMaxLayers], groups[kConvStackMaxLayers],
-        stride[kConvStackMaxLayers], pad[kConvStackMaxLayers], reflect[kConvStackMaxLayers];
-    int64_t F[kConvStackMaxLayers + 1];           // frames entering layer l; F[n]: frames of the last output
-    int64_t w_off[kConvStackMaxLayers], w_total;  // floats of layer l's weights within wF / wB
-    int row0[kConvStackMaxLayers], rows;          // output channels counted through the layers
-    int64_t saved_total;                          // saved: wF | wB | 1/|v|
-    int nchunk[kConvStackMaxLayers], per[kConvStackMaxLayers];   // weight gradient of layer l: chunks of `per` streams ...
-    int64_t seg[kConvStackMaxLayers], nseg[kConvStackMaxLayers]; // ... times segments of `seg` output frames
-    int64_t gz_size, fold_size;                   // ws: gz ping | gz pong | padded gx of a reflected first layer | partials
-    int64_t part_off[kConvStackMaxLayers], bpart_off[kConvStackMaxLayers], ws_total;
-};
-void sconv_plan(SConvPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_s *L);
-hipError_t launch_sconvstack_forward(const SConvPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_sconvstack_forward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                      const float *const *v, const float *const *bias, float *saved, float *const *outs,
                                      hipStream_t stream);
-hipError_t launch_sconvstack_backward(const SConvPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_sconvstack_backward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                       const float *const *v, const float *saved, const float *const *outs,
                                       const float *const *gouts, float *gx, float *const *dg, float *const *dv,
                                       float *const *dbias, float *ws, hipStream_t stream);

@@ -1,14 +1,13 @@
 // The conv stack of the reference's MelGAN critic (MelGCrit / NLayerDiscriminator, code/critics.py:18-122) and of any stack like
 // it: n weight-normed Conv1d(c_in, c_out, k, groups, stride, pad) layers, dilation 1, LeakyReLU(slope) after every layer but the
-// last, zero padding, or a reflection pad on the first layer -- forward, data gradient, weight gradient and the weight-norm
-// adjoint, fp32 in and fp32 accumulate on v_mfma_f32_16x16x4_f32 (exact fp32: the matrix pipe's fmaf chain).  The family of
-// convstack_kernels.hip with four differences: a stride and a pad per layer instead of a dilation, the reflected first layer, the
-// output of EVERY layer a tensor of the caller's (they are the saved activations: there is no second copy), and a gradient that
-// may arrive at every one of them.
+// last, zero padding, or a reflection pad on the first layer.  What it shares with the spectral and the dilated family (the plan,
+// weight preparation, weight-norm adjoint) is convstack_common.h; this file holds its GEMM kernels and what differs:
+// a stride and a pad per layer instead of a dilation, the reflected first layer, the output of EVERY layer a tensor of the caller's
+// (they are the saved activations: there is no second copy), a gradient that may arrive at every one of them -- and with them the
+// PER-INDEX fetch form of the conv kernel, the weight layouts it reads, the dot, mask and fold kernels and the chunk rule.
 //
-// sc_prep_kernel      one launch for all layers, one workgroup per output channel: |v| over (c_in/groups, k), w = v * (g / |v|) in
-//                     the two layouts the conv kernel reads, and 1/|v| for the adjoint.
-//                     Both are [reduction index][every channel of the other side], so a step's weights are 64 consecutive rows:
+// PhaseLayout         both weight layouts are [reduction index][every channel of the other side], so a step's weights are 64
+//                     consecutive rows:
 //                       wF[ci K + k][CO]            (ci within the group, CO every output channel)   -- forward
 //                       wB[phase][co Kph + i][CI]   (co within the group, CI every input channel; tap k = phase + stride i, the
 //                                                   phases one after the other, Kph taps each)         -- data gradient
@@ -21,39 +20,34 @@
 //                       forward        column n = output frame, tap i = weight tap, window frame n s + i - pad: a read strided
 //                                      by s (the lanes of a load s floats apart; the s - 1 floats between them are the next taps'
 //                                      and come from the same lines).  Frames outside read 0, or on a reflected layer the
-//                                      mirrored sample.  Epilogue bias -> LeakyReLU(slope) (the last layer: bias) into the
-//                                      layer's output tensor.
+//                                      mirrored sample.  The epilogue stores into the layer's output tensor.
 //                       data gradient  PER PHASE, the exact work: the input frames t with (t + pad) mod s = r take the taps
 //                                      j = r + s i only, gin[c][s u + r - pad] = sum_{m,i} w[m][c][r + s i] gz[m][u - i] -- a
 //                                      stride-1 correlation over u per phase, the windows contiguous; the s phases are s
 //                                      workgroups, the store is strided by s.  A phase with no tap (k < s) stores the epilogue
-//                                      of 0.  Epilogue: + the caller's gradient at that tensor where there is one, then times the
-//                                      LeakyReLU slope recovered from the sign of the saved output (y > 0 <=> pre > 0 as slope >
-//                                      0; y == 0 takes the slope, torch's choice).  Under a reflected first layer the kernel
-//                                      writes the gradient of the PADDED input (F0 + 2 pad frames) and sc_fold_kernel adds the
-//                                      border terms back: gx[t] = P[t] + P[-t] (1 <= t <= pad) + P[2 (F0 - 1) - t] (F0 - 1 - pad
-//                                      <= t <= F0 - 2), in that order.
+//                                      of 0.  The epilogue adds the caller's gradient at that tensor where there is one.  Under a
+//                                      reflected first layer the kernel writes the gradient of the PADDED input (F0 + 2 pad
+//                                      frames) and sc_fold_kernel adds the border terms back: gx[t] = P[t] + P[-t] (1 <= t <=
+//                                      pad) + P[2 (F0 - 1) - t] (F0 - 1 - pad <= t <= F0 - 2), in that order.
+//                     Epilogues: forward, bias -> LeakyReLU(slope) (the last layer: bias).  Data gradient: + the caller's
+//                     gradient at that tensor where there is one, then times the LeakyReLU slope of the layer below, recovered
+//                     from the sign of its saved output (y > 0 <=> pre > 0 as slope > 0; y == 0 takes the slope, torch's choice).
 //                     Order of addition of one output: the reduction indices ascending in fours (one MFMA each, its K = 4 an
 //                     fmaf chain, for the data gradient over the taps of its phase), 4 steps (256 indices) from 0, and those sums
 //                     added in ascending order -- a function of the layer alone.
-// sc_wgrad_kernel     dW[co][ci][k] = sum_{b,f} gz[b][co][f] in[b][ci][f s + k - pad]: GEMM with M = co, N = (ci, k) flattened as dW
-//                     is stored, reduction over the output frames (64 per step).  Column (ci, k) holds in[b][ci][(f0 + t) s + k -
-//                     pad], zero or mirrored outside.  The reduction is cut by the chunk rule of include/ntm.h (sconv_plan): per
-//                     layer, stream chunks x frame segments; a workgroup walks the streams of its chunk and the frames of its
-//                     segment in order, adds 4 steps from 0 and then that sum to its total, and stores ONE partial tile, no atomics.
+// sc_wgrad_kernel     cs_wgrad_kernel with the X window at frame f s + k - pad, zero or mirrored outside, cut by the chunk rule of
+//                     include/ntm.h (sconv_plan): per layer, stream chunks x frame segments of `seg` frames.
 // sc_dot_kernel       the same sum and epilogue for a layer with one output channel per group and >= 128 reduction indices per
 //                     phase (the last layer, 1024 x 3 -> 1; the first layer's data gradient): 64 columns of one channel per
 //                     workgroup, the reduction in four contiguous quarters (one per wave, an fmaf chain from 0 each) added
 //                     in order.  Which kernel a layer runs on is a function of the layer alone.
 // sc_mask_kernel      gz = gout * LeakyReLU'(y) for the highest layer a gradient arrives at when it is not the last.
-// sc_wnorm_kernel     one launch for the layers a gradient reaches: adds the partials in chunk order (stream chunk major, segment
-//                     minor), then dg, dv, dbias as in cs_wnorm_kernel.  Layers above them get zeros from a memset.
+// weight-norm adjoint stack_wnorm_kernel over the layers a gradient reaches; layers above them get zeros from a memset.
 //
 // Two tile shapes per GEMM kernel, as in convstack_kernels.hip: 64 x 64 where a group has more than 16 rows, else 16 x 128
 // (16 x 64 for the weight gradient) with predicated edges -- the grouped layers' 4-channel groups (four real rows of sixteen) run
 // on the narrow tile.
-#include "ntm.h"
-#include "ntm_common.h"
+#include "convstack_common.h"
 
 namespace ntm {
 
@@ -62,107 +56,44 @@ constexpr int64_t kScSegFrames = 1024;           // ... times segments of this m
 constexpr int64_t kScMinFrames = 2048;           // a partial sums at least this many frames (where the layer has them)
 constexpr int64_t kScCapFloats = (int64_t)1 << 24;   // ... and the partials of one layer stay within 2^24 floats (64 MiB)
 
-static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-void sconv_plan(SConvPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_s *L)
+void sconv_plan(StackPlan &p, int64_t B, int64_t C0, int64_t F0, int n, const ntm_conv1d_layer_s *L)
 {
-    p.n = n;
-    p.F[0] = F0;
-    p.w_total = 0;
-    p.rows = 0;
-    p.gz_size = 0;
+    stack_plan_layers(p, B, F0, n, L, false, [&](int l, int64_t F) { return (F + 2 * (int64_t)L[l].pad - L[l].k) / L[l].stride + 1; });
     for (int l = 0; l < n; ++l) {
-        p.c_in[l] = L[l].c_in, p.c_out[l] = L[l].c_out, p.k[l] = L[l].k, p.groups[l] = L[l].groups, p.stride[l] = L[l].stride;
-        p.pad[l] = L[l].pad, p.reflect[l] = L[l].pad_mode == 1 && L[l].pad > 0;
-        p.F[l + 1] = (p.F[l] + 2 * (int64_t)L[l].pad - L[l].k) / L[l].stride + 1;
-        p.w_off[l] = p.w_total;
-        p.w_total += (int64_t)L[l].c_out * (L[l].c_in / L[l].groups) * L[l].k;
-        p.row0[l] = p.rows;
-        p.rows += L[l].c_out;
-        const int64_t sz = B * p.c_out[l] * p.F[l + 1];
-        if (sz > p.gz_size) p.gz_size = sz;
-    }
-    p.saved_total = 2 * p.w_total + p.rows;
-    p.fold_size = p.reflect[0] ? B * C0 * (F0 + 2 * (int64_t)p.pad[0]) : 0;
-    int64_t w = 2 * p.gz_size + p.fold_size;
-    for (int l = 0; l < n; ++l) {
-        const int64_t W = (int64_t)L[l].c_out * (L[l].c_in / L[l].groups) * L[l].k, Fo = p.F[l + 1];
+        p.stride[l] = L[l].stride, p.pad[l] = L[l].pad, p.reflect[l] = L[l].pad_mode == 1 && L[l].pad > 0;
+        const int64_t W = p.w_size(l), Fo = p.F[l + 1];
         int64_t seg = kScSegFrames;
-        while (cdiv(Fo, seg) > 1 && cdiv(Fo, seg) * W > kScCapFloats) seg *= 2;
-        const int64_t nseg = cdiv(Fo, seg);
+        while (stack_cdiv(Fo, seg) > 1 && stack_cdiv(Fo, seg) * W > kScCapFloats) seg *= 2;
+        const int64_t nseg = stack_cdiv(Fo, seg);
         int64_t per = 1, nchunk = 0;
         if (B > 0) {
-            per = cdiv(B, kScMaxChunks);
-            const int64_t need = cdiv(kScMinFrames, Fo < seg ? Fo : seg);
+            per = stack_cdiv(B, kScMaxChunks);
+            const int64_t need = stack_cdiv(kScMinFrames, Fo < seg ? Fo : seg);
             if (need > per) per = need;
             int64_t maxparts = kScCapFloats / (nseg * W);
             if (maxparts < 1) maxparts = 1;
-            if (cdiv(B, maxparts) > per) per = cdiv(B, maxparts);
+            if (stack_cdiv(B, maxparts) > per) per = stack_cdiv(B, maxparts);
             if (per > B) per = B;
-            nchunk = cdiv(B, per);
+            nchunk = stack_cdiv(B, per);
         }
         p.seg[l] = seg, p.nseg[l] = nseg, p.per[l] = (int)per, p.nchunk[l] = (int)nchunk;
-        p.part_off[l] = w;
-        w += nchunk * nseg * W;
-        p.bpart_off[l] = w;
-        w += nchunk * nseg * L[l].c_out;
     }
-    p.ws_total = w;
+    p.fold_size = p.reflect[0] ? B * C0 * (F0 + 2 * (int64_t)p.pad[0]) : 0;
+    stack_plan_partials(p);
 }
 
 namespace {
 
-// sum over the workgroup in a fixed tree order; every thread gets it
-template <int NT>
-__device__ __forceinline__ float block_sum(float x, float *red)
-{
-    const int tid = threadIdx.x;
-    red[tid] = x;
-    __syncthreads();
-#pragma unroll
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-struct PrepArgs {
-    const float *g[kConvStackMaxLayers], *v[kConvStackMaxLayers];
-    int c_in[kConvStackMaxLayers], c_out[kConvStackMaxLayers], k[kConvStackMaxLayers], groups[kConvStackMaxLayers],
-        stride[kConvStackMaxLayers], row0[kConvStackMaxLayers];
-    int64_t w_off[kConvStackMaxLayers];
-    int n;
-    float *wF, *wB, *invn;
-};
-
-__global__ __launch_bounds__(256) void sc_prep_kernel(PrepArgs a)
-{
-    __shared__ float red[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    int l = 0;
-    while (l + 1 < a.n && row >= a.row0[l + 1]) ++l;
-    const int co = row - a.row0[l], K = a.k[l], cin_g = a.c_in[l] / a.groups[l], cout_g = a.c_out[l] / a.groups[l];
-    const int n = cin_g * K, grp = co / cout_g, co_l = co - grp * cout_g;
-    const float *v = a.v[l] + (int64_t)co * n;
-    float s = 0.0f;
-    for (int j = tid; j < n; j += 256) s = fmaf(v[j], v[j], s);
-    const float norm = sqrtf(block_sum<256>(s, red));
-    const float scale = a.g[l][co] / norm;
-    float *wF = a.wF + a.w_off[l], *wB = a.wB + a.w_off[l];
-    const int st = a.stride[l], kq = K / st, krem = K % st;
-    for (int j = tid; j < n; j += 256) {
-        const int ci = j / K, k = j - ci * K;
-        const float w = v[j] * scale;
-        wF[(int64_t)j * a.c_out[l] + co] = w;
+struct PhaseLayout {
+    static __device__ __forceinline__ void put(const PrepRow &r, float *wF, float *wB, int j, int ci, int k, float w)
+    {
+        wF[(int64_t)j * r.c_out + r.co] = w;
         // tap k is tap i = k / stride of phase ph = k mod stride, which has Kph taps; the phases before it hold `before`
-        const int ph = k % st, i = k / st, Kph = kq + (ph < krem), before = ph * kq + min(ph, krem);
-        wB[((int64_t)before * cout_g + co_l * Kph + i) * a.c_in[l] + grp * cin_g + ci] = w;
+        const int kq = r.K / r.stride, krem = r.K % r.stride;
+        const int ph = k % r.stride, i = k / r.stride, Kph = kq + (ph < krem), before = ph * kq + min(ph, krem);
+        wB[((int64_t)before * r.cout_g + r.co_l * Kph + i) * r.c_in + r.grp * r.cin_g + ci] = w;
     }
-    if (tid == 0) a.invn[row] = 1.0f / norm;
-}
+};
 
 enum { EPI_BIAS_LRELU = 0, EPI_BIAS = 1, EPI_MASK = 2, EPI_NONE = 3 };
 
@@ -525,51 +456,6 @@ __global__ __launch_bounds__(256) void sc_wgrad_kernel(WgradArgs a)
         a.bpart[part_i * a.Cout + grp * a.cout_g + m0 + tid] = bsum;
 }
 
-struct WnormArgs {
-    const float *g[kConvStackMaxLayers], *v[kConvStackMaxLayers];
-    float *dg[kConvStackMaxLayers], *dv[kConvStackMaxLayers], *db[kConvStackMaxLayers];
-    float *part[kConvStackMaxLayers];         // the sum of a row's partials is left in its first partial
-    const float *bpart[kConvStackMaxLayers];
-    int c_out[kConvStackMaxLayers], rowlen[kConvStackMaxLayers], row0[kConvStackMaxLayers];
-    int64_t nparts[kConvStackMaxLayers];
-    int n;
-    const float *invn;
-};
-
-__global__ __launch_bounds__(256) void sc_wnorm_kernel(WnormArgs a)
-{
-    __shared__ float red[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    int l = 0;
-    while (l + 1 < a.n && row >= a.row0[l + 1]) ++l;
-    const int co = row - a.row0[l], n = a.rowlen[l];
-    const int64_t cstride = (int64_t)a.c_out[l] * n, np = a.nparts[l];
-    const float *v = a.v[l] + (int64_t)co * n;
-    float *p = a.part[l] + (int64_t)co * n;
-    float s = 0.0f;
-    for (int j = tid; j < n; j += 256) {
-        float dw = p[j];
-        int64_t c = 1;
-        for (; c + 4 <= np; c += 4) {           // four loads in flight, added in chunk order
-            const float p0 = p[c * cstride + j], p1 = p[(c + 1) * cstride + j], p2 = p[(c + 2) * cstride + j], p3 = p[(c + 3) * cstride + j];
-            dw = (((dw + p0) + p1) + p2) + p3;
-        }
-        for (; c < np; ++c) dw += p[c * cstride + j];
-        p[j] = dw;
-        s = fmaf(dw, v[j], s);
-    }
-    const float dot = block_sum<256>(s, red);
-    const float inv = a.invn[row], scale = a.g[l][co] * inv, proj = dot * inv * inv;
-    float *dv = a.dv[l] + (int64_t)co * n;
-    for (int j = tid; j < n; j += 256) dv[j] = scale * (p[j] - v[j] * proj);
-    if (tid == 0) {
-        a.dg[l][co] = dot * inv;
-        float sb = a.bpart[l][co];
-        for (int64_t c = 1; c < np; ++c) sb += a.bpart[l][c * a.c_out[l] + co];
-        a.db[l][co] = sb;
-    }
-}
-
 hipError_t launch_conv(ConvArgs a, int64_t B, int groups, hipStream_t stream)
 {
     // one output channel per group and at least kDotMin reduction indices per phase: the dot kernel
@@ -608,20 +494,11 @@ hipError_t launch_wgrad(WgradArgs a, int groups, int nchunk, hipStream_t stream)
 
 }  // namespace
 
-hipError_t launch_sconvstack_forward(const SConvPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_sconvstack_forward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                      const float *const *v, const float *const *bias, float *saved, float *const *outs,
                                      hipStream_t stream)
 {
-    PrepArgs pa{};
-    for (int l = 0; l < p.n; ++l) {
-        pa.g[l] = g[l], pa.v[l] = v[l];
-        pa.c_in[l] = p.c_in[l], pa.c_out[l] = p.c_out[l], pa.k[l] = p.k[l], pa.groups[l] = p.groups[l], pa.stride[l] = p.stride[l], pa.row0[l] = p.row0[l];
-        pa.w_off[l] = p.w_off[l];
-    }
-    pa.n = p.n;
-    pa.wF = saved, pa.wB = saved + p.w_total, pa.invn = saved + 2 * p.w_total;
-    hipLaunchKernelGGL(sc_prep_kernel, dim3((unsigned)p.rows), dim3(256), 0, stream, pa);
-    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = launch_stack_prep<PhaseLayout>(p, g, v, saved, stream)) return e;
     for (int l = 0; l < p.n; ++l) {
         const bool last = l == p.n - 1;
         ConvArgs a{};
@@ -640,7 +517,7 @@ hipError_t launch_sconvstack_forward(const SConvPlan &p, const float *x, int64_t
     return hipSuccess;
 }
 
-hipError_t launch_sconvstack_backward(const SConvPlan &p, const float *x, int64_t B, float slope, const float *const *g,
+hipError_t launch_sconvstack_backward(const StackPlan &p, const float *x, int64_t B, float slope, const float *const *g,
                                       const float *const *v, const float *saved, const float *const *outs,
                                       const float *const *gouts, float *gx, float *const *dg, float *const *dv,
                                       float *const *dbias, float *ws, hipStream_t stream)
@@ -700,19 +577,7 @@ hipError_t launch_sconvstack_backward(const SConvPlan &p, const float *x, int64_
         }
         gz = dst;
     }
-    if (dg) {
-        WnormArgs a{};
-        for (int l = 0; l <= top; ++l) {
-            a.g[l] = g[l], a.v[l] = v[l], a.dg[l] = dg[l], a.dv[l] = dv[l], a.db[l] = dbias[l];
-            a.part[l] = ws + p.part_off[l], a.bpart[l] = ws + p.bpart_off[l];
-            a.c_out[l] = p.c_out[l], a.rowlen[l] = (p.c_in[l] / p.groups[l]) * p.k[l], a.row0[l] = p.row0[l];
-            a.nparts[l] = (int64_t)p.nchunk[l] * p.nseg[l];
-        }
-        a.n = top + 1, a.invn = saved + 2 * p.w_total;
-        hipLaunchKernelGGL(sc_wnorm_kernel, dim3((unsigned)(p.row0[top] + p.c_out[top])), dim3(256), 0, stream, a);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    return dg ? launch_stack_wnorm(p, top + 1, g, v, dg, dv, dbias, saved, ws, stream) : hipSuccess;
 }
 
 }  // namespace ntm

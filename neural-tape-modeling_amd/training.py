@@ -259,10 +259,62 @@ class SpectrogramFn(torch.autograd.Function):
         return dy, None, None, None
 
 
-def _speccrit_sizes(x, spec):
+# The three critic conv stacks (SpecCritFn, ConvStackFn, StridedConvStackFn) differ in their layer records, in the scalar beside
+# them and in where the outputs live; the rest is these helpers.  `name` is the class, `prefix` the entry points' (ntm_<prefix>_*),
+# `make_layers` the _lib builder of the layer array.
+
+def _stack_begin(name, prefix, make_layers, x, spec, params):
+    """The preamble of a forward: checks, fp32 contiguous copies, the layer array and the `saved` buffer at its size.
+    -> (x, ps, spec, layers, saved)"""
+    spec = tuple(tuple(int(q) for q in s) for s in spec)
+    n = len(spec)
+    if len(params) != 3 * n:
+        raise RuntimeError(f"{name}: {n} layers need {3 * n} parameters (weight_g, weight_v, bias each), got {len(params)}")
+    if not x.is_cuda:
+        raise RuntimeError(f"{name}: HIP device only (no CPU fallback)")
+    x = x.detach().to(torch.float32).contiguous()
+    ps = [p.detach().to(torch.float32).contiguous() for p in params]
     B, C0, F0 = x.shape
-    F_out = F0 - sum(k - 1 for _, _, k, _ in spec)
-    return B, C0, F0, F_out
+    L = _lib.lib()
+    layers = make_layers(spec)
+    n_saved = int(getattr(L, f"ntm_{prefix}_saved_floats")(B, C0, F0, n, layers))
+    if n_saved < 0:
+        raise _lib.NtmError(f"ntm_{prefix}_forward refused the sizes: {L.ntm_last_error().decode()}")
+    return x, ps, spec, layers, torch.empty(max(n_saved, 1), device=x.device, dtype=torch.float32)
+
+
+def _stack_forward(prefix, x, scalar, spec, layers, ps, saved, out):
+    """ntm_<prefix>_forward; out: the output tensor, or the list of every layer's."""
+    B, C0, F0 = x.shape
+    _lib.check(getattr(_lib.lib(), f"ntm_{prefix}_forward")(
+        ptr(x), B, C0, F0, scalar, len(spec), layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]), _lib.ptr_array(ps[2::3]),
+        ptr(saved), _lib.ptr_array(out) if isinstance(out, list) else ptr(out), _lib.current_stream()), f"ntm_{prefix}_forward")
+
+
+def _stack_backward(ctx, prefix, make_layers, x, saved, ps, arriving, call=True):
+    """ntm_<prefix>_backward and the bookkeeping around it: gx and the parameter gradients only where needs_input_grad asks,
+    zeros where B == 0 or nothing is to be computed (call False).  arriving: the tensors that stand between `saved` and gx in the
+    entry point's arguments -- the gradient at the output, or the lists outs and gouts.  -> backward's return value"""
+    scalar, spec = ctx.res
+    n = len(spec)
+    B, C0, F0 = x.shape
+    gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+    want = any(ctx.needs_input_grad[3:])
+    grads = [torch.empty_like(p) for p in ps] if want else []
+    if call:
+        L = _lib.lib()
+        layers = make_layers(spec)
+        ws = torch.empty(max(int(getattr(L, f"ntm_{prefix}_workspace_floats")(B, C0, F0, n, layers)), 1), device=x.device,
+                         dtype=torch.float32)
+        arr = (lambda q: _lib.ptr_array(q) if want else None)
+        _lib.check(getattr(L, f"ntm_{prefix}_backward")(
+            ptr(x), B, C0, F0, scalar, n, layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]), ptr(saved), *[_lib.ptr_array(t) if isinstance(t, list) else ptr(t) for t in arriving], ptr(gx),
+            arr(grads[0::3]), arr(grads[1::3]), arr(grads[2::3]), ptr(ws), _lib.current_stream()), f"ntm_{prefix}_backward")
+    if B == 0 or not call:
+        gx = None if gx is None else gx.zero_()
+        grads = [g.zero_() for g in grads]
+    pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
+    return (gx, None, None, *pg)
 
 
 class SpecCritFn(torch.autograd.Function):
@@ -274,25 +326,10 @@ class SpecCritFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, log_floor, spec, *params):
-        spec = tuple(tuple(int(q) for q in s) for s in spec)
-        n = len(spec)
-        if len(params) != 3 * n:
-            raise RuntimeError(f"SpecCritFn: {n} layers need {3 * n} parameters (weight_g, weight_v, bias each), got {len(params)}")
-        if not x.is_cuda:
-            raise RuntimeError("SpecCritFn: HIP device only (no CPU fallback)")
-        x = x.detach().to(torch.float32).contiguous()
-        ps = [p.detach().to(torch.float32).contiguous() for p in params]
-        B, C0, F0, F_out = _speccrit_sizes(x, spec)
-        L = _lib.lib()
-        layers = _lib.conv_layers(spec)
-        n_saved = int(L.ntm_speccrit_saved_floats(B, C0, F0, n, layers))
-        if n_saved < 0:
-            raise _lib.NtmError(f"ntm_speccrit_forward refused the sizes: {L.ntm_last_error().decode()}")
-        saved = torch.empty(max(n_saved, 1), device=x.device, dtype=torch.float32)
-        out = torch.empty(B, spec[-1][1], F_out, device=x.device, dtype=torch.float32)
-        _lib.check(L.ntm_speccrit_forward(ptr(x), B, C0, F0, float(log_floor), n, layers, _lib.ptr_array(ps[0::3]),
-                                          _lib.ptr_array(ps[1::3]), _lib.ptr_array(ps[2::3]), ptr(saved), ptr(out),
-                                          _lib.current_stream()), "ntm_speccrit_forward")
+        x, ps, spec, layers, saved = _stack_begin("SpecCritFn", "speccrit", _lib.conv_layers, x, spec, params)
+        F_out = x.shape[2] - sum(k - 1 for _, _, k, _ in spec)
+        out = torch.empty(x.shape[0], spec[-1][1], F_out, device=x.device, dtype=torch.float32)
+        _stack_forward("speccrit", x, float(log_floor), spec, layers, ps, saved, out)
         ctx.save_for_backward(x, saved, *ps)
         ctx.res = (float(log_floor), spec)
         return out
@@ -301,31 +338,8 @@ class SpecCritFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
         x, saved, *ps = ctx.saved_tensors
-        log_floor, spec = ctx.res
-        n = len(spec)
-        B, C0, F0, _ = _speccrit_sizes(x, spec)
         gout = gout.to(torch.float32).contiguous()
-        L = _lib.lib()
-        layers = _lib.conv_layers(spec)
-        ws = torch.empty(max(int(L.ntm_speccrit_workspace_floats(B, C0, F0, n, layers)), 1), device=x.device, dtype=torch.float32)
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        want = any(ctx.needs_input_grad[3:])
-        grads = [torch.empty_like(p) for p in ps] if want else []
-        arr = (lambda q: _lib.ptr_array(q) if want else None)
-        _lib.check(L.ntm_speccrit_backward(ptr(x), B, C0, F0, log_floor, n, layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]),
-                                           ptr(saved), ptr(gout), ptr(gx), arr(grads[0::3]), arr(grads[1::3]), arr(grads[2::3]),
-                                           ptr(ws), _lib.current_stream()), "ntm_speccrit_backward")
-        if B == 0:
-            gx = None if gx is None else gx.zero_()
-            grads = [g.zero_() for g in grads]
-        pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
-        return (gx, None, None, *pg)
-
-
-def _convstack_sizes(x, spec):
-    B, C0, F0 = x.shape
-    F_out = F0 - sum((k - 1) * d for _, _, k, _, d in spec)
-    return B, C0, F0, F_out
+        return _stack_backward(ctx, "speccrit", _lib.conv_layers, x, saved, ps, [gout])
 
 
 class ConvStackFn(torch.autograd.Function):
@@ -338,25 +352,10 @@ class ConvStackFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, slope, spec, *params):
-        spec = tuple(tuple(int(q) for q in s) for s in spec)
-        n = len(spec)
-        if len(params) != 3 * n:
-            raise RuntimeError(f"ConvStackFn: {n} layers need {3 * n} parameters (weight_g, weight_v, bias each), got {len(params)}")
-        if not x.is_cuda:
-            raise RuntimeError("ConvStackFn: HIP device only (no CPU fallback)")
-        x = x.detach().to(torch.float32).contiguous()
-        ps = [p.detach().to(torch.float32).contiguous() for p in params]
-        B, C0, F0, F_out = _convstack_sizes(x, spec)
-        L = _lib.lib()
-        layers = _lib.conv_layers_d(spec)
-        n_saved = int(L.ntm_convstack_saved_floats(B, C0, F0, n, layers))
-        if n_saved < 0:
-            raise _lib.NtmError(f"ntm_convstack_forward refused the sizes: {L.ntm_last_error().decode()}")
-        saved = torch.empty(max(n_saved, 1), device=x.device, dtype=torch.float32)
-        out = torch.empty(B, spec[-1][1], F_out, device=x.device, dtype=torch.float32)
-        _lib.check(L.ntm_convstack_forward(ptr(x), B, C0, F0, float(slope), n, layers, _lib.ptr_array(ps[0::3]),
-                                           _lib.ptr_array(ps[1::3]), _lib.ptr_array(ps[2::3]), ptr(saved), ptr(out),
-                                           _lib.current_stream()), "ntm_convstack_forward")
+        x, ps, spec, layers, saved = _stack_begin("ConvStackFn", "convstack", _lib.conv_layers_d, x, spec, params)
+        F_out = x.shape[2] - sum((k - 1) * d for _, _, k, _, d in spec)
+        out = torch.empty(x.shape[0], spec[-1][1], F_out, device=x.device, dtype=torch.float32)
+        _stack_forward("convstack", x, float(slope), spec, layers, ps, saved, out)
         ctx.save_for_backward(x, saved, *ps)
         ctx.res = (float(slope), spec)
         return out
@@ -365,25 +364,8 @@ class ConvStackFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
         x, saved, *ps = ctx.saved_tensors
-        slope, spec = ctx.res
-        n = len(spec)
-        B, C0, F0, _ = _convstack_sizes(x, spec)
         gout = gout.to(torch.float32).contiguous()
-        L = _lib.lib()
-        layers = _lib.conv_layers_d(spec)
-        ws = torch.empty(max(int(L.ntm_convstack_workspace_floats(B, C0, F0, n, layers)), 1), device=x.device, dtype=torch.float32)
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        want = any(ctx.needs_input_grad[3:])
-        grads = [torch.empty_like(p) for p in ps] if want else []
-        arr = (lambda q: _lib.ptr_array(q) if want else None)
-        _lib.check(L.ntm_convstack_backward(ptr(x), B, C0, F0, slope, n, layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]),
-                                            ptr(saved), ptr(gout), ptr(gx), arr(grads[0::3]), arr(grads[1::3]), arr(grads[2::3]),
-                                            ptr(ws), _lib.current_stream()), "ntm_convstack_backward")
-        if B == 0:
-            gx = None if gx is None else gx.zero_()
-            grads = [g.zero_() for g in grads]
-        pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
-        return (gx, None, None, *pg)
+        return _stack_backward(ctx, "convstack", _lib.conv_layers_d, x, saved, ps, [gout])
 
 
 def _sconvstack_frames(F0, spec):
@@ -406,26 +388,10 @@ class StridedConvStackFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, slope, spec, *params):
-        spec = tuple(tuple(int(q) for q in s) for s in spec)
-        n = len(spec)
-        if len(params) != 3 * n:
-            raise RuntimeError(f"StridedConvStackFn: {n} layers need {3 * n} parameters (weight_g, weight_v, bias each), got {len(params)}")
-        if not x.is_cuda:
-            raise RuntimeError("StridedConvStackFn: HIP device only (no CPU fallback)")
-        x = x.detach().to(torch.float32).contiguous()
-        ps = [p.detach().to(torch.float32).contiguous() for p in params]
-        B, C0, F0 = x.shape
-        L = _lib.lib()
-        layers = _lib.conv_layers_s(spec)
-        n_saved = int(L.ntm_sconvstack_saved_floats(B, C0, F0, n, layers))
-        if n_saved < 0:
-            raise _lib.NtmError(f"ntm_sconvstack_forward refused the sizes: {L.ntm_last_error().decode()}")
-        F = _sconvstack_frames(F0, spec)
-        saved = torch.empty(max(n_saved, 1), device=x.device, dtype=torch.float32)
-        outs = [torch.empty(B, spec[l][1], F[l + 1], device=x.device, dtype=torch.float32) for l in range(n)]
-        _lib.check(L.ntm_sconvstack_forward(ptr(x), B, C0, F0, float(slope), n, layers, _lib.ptr_array(ps[0::3]),
-                                            _lib.ptr_array(ps[1::3]), _lib.ptr_array(ps[2::3]), ptr(saved), _lib.ptr_array(outs),
-                                            _lib.current_stream()), "ntm_sconvstack_forward")
+        x, ps, spec, layers, saved = _stack_begin("StridedConvStackFn", "sconvstack", _lib.conv_layers_s, x, spec, params)
+        F = _sconvstack_frames(x.shape[2], spec)
+        outs = [torch.empty(x.shape[0], spec[l][1], F[l + 1], device=x.device, dtype=torch.float32) for l in range(len(spec))]
+        _stack_forward("sconvstack", x, float(slope), spec, layers, ps, saved, outs)
         ctx.save_for_backward(x, saved, *ps, *outs)
         ctx.res = (float(slope), spec)
         ctx.set_materialize_grads(False)        # an output no gradient arrives at stays None: a NULL gouts entry, no zero tensor
@@ -434,29 +400,12 @@ class StridedConvStackFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *gouts):
-        slope, spec = ctx.res
-        n = len(spec)
+        n = len(ctx.res[1])
         x, saved, *rest = ctx.saved_tensors
         ps, outs = rest[:3 * n], rest[3 * n:]
-        B, C0, F0 = x.shape
         gouts = [None if g is None else g.to(torch.float32).contiguous() for g in gouts]
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        want = any(ctx.needs_input_grad[3:])
-        grads = [torch.empty_like(p) for p in ps] if want else []
-        if all(g is None for g in gouts) or B == 0:
-            gx = None if gx is None else gx.zero_()
-            grads = [g.zero_() for g in grads]
-        else:
-            L = _lib.lib()
-            layers = _lib.conv_layers_s(spec)
-            ws = torch.empty(max(int(L.ntm_sconvstack_workspace_floats(B, C0, F0, n, layers)), 1), device=x.device, dtype=torch.float32)
-            arr = (lambda q: _lib.ptr_array(q) if want else None)
-            _lib.check(L.ntm_sconvstack_backward(ptr(x), B, C0, F0, slope, n, layers, _lib.ptr_array(ps[0::3]), _lib.ptr_array(ps[1::3]),
-                                                 ptr(saved), _lib.ptr_array(outs), _lib.ptr_array(gouts), ptr(gx), arr(grads[0::3]),
-                                                 arr(grads[1::3]), arr(grads[2::3]), ptr(ws), _lib.current_stream()),
-                       "ntm_sconvstack_backward")
-        pg = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])] if want else [None] * (3 * n)
-        return (gx, None, None, *pg)
+        return _stack_backward(ctx, "sconvstack", _lib.conv_layers_s, x, saved, ps, [list(outs), gouts],
+                               call=not all(g is None for g in gouts) and x.shape[0] != 0)
 
 
 class AdvHeadFn(torch.autograd.Function):
