@@ -3,8 +3,9 @@ code/networks/unet_1d.py): the wow-and-flutter delay trajectories that drive Dif
 
   load_config(name)            configs/conf_{noise,trajectories,toytrajectories}.yaml as plain data with attribute access
   UNet1D(args, device)         the reference's parameters and buffers under the reference's state_dict keys;
-                               forward_torch: this project's restatement in torch ops (any dtype, any device),
-                               forward: the HIP path (csrc/unet_kernels.hip), HIP device only
+                               _walk: the network's data flow, written once; forward_torch: it in torch ops (this project's
+                               restatement, any dtype, any device); forward: it as launches of csrc/unet_kernels.hip bound once
+                               per (B, T), HIP device only; record= of either reports the same names from the path that ran
   DiffusionGenerator(args, device)   the EDM sampler with the reference's attributes and methods
 
 Inference only: nothing here records a graph.  Two additions to the reference's protocol, both keyword arguments:
@@ -258,14 +259,6 @@ class CombinerDown(nn.Module):
         return (self.conv1x1(pyr) + x) / (2 ** 0.5)
 
 
-def _crop(x, frames):
-    """CropConcatBlock's centre crop of x to `frames` -> (first frame, x cropped)."""
-    off = (x.shape[2] - frames) // 2
-    if off < 0:
-        raise ValueError(f"UNet1D: the up path carries {x.shape[2]} frames into a skip of {frames}: nothing to crop")
-    return off, x[:, :, off:off + frames]
-
-
 class BlockSpec(_lib.ctypes.Structure):
     """include/ntm.h ntm_unet_block."""
     _fields_ = [("c0", _lib.ctypes.c_int32), ("c1", _lib.ctypes.c_int32), ("c_out", _lib.ctypes.c_int32),
@@ -280,6 +273,66 @@ def _require_hip(what, *tensors):
             raise RuntimeError(f"{what}: HIP device only (no CPU fallback), fp32; supported: {SUPPORTED}")
 
 
+class _Call:
+    """One C call with its arguments bound: `args` in the entry point's order with the stream last, `slot` the positions by name
+    of the pointers a plan patches, `out` what the call writes, `ws` its workspace, `launches` the kernels it starts."""
+
+    def __init__(self, name, args, slot, out, ws=None, launches=1):
+        self.name, self.fn, self.args, self.slot = name, getattr(_lib.lib(), name), args, slot
+        self.out, self.ws, self.launches = out, ws, launches
+
+    def __call__(self, stream):
+        self.args[-1] = stream
+        _lib.check(self.fn(*self.args), self.name)
+        return self.out
+
+
+def _addr(t):
+    """The pointer to bind for t.  A tensor on the meta device stands for an operand whose pointer comes per evaluation (it has
+    the shape and the strides, no storage): it binds as null, like no tensor, and a null left unpatched is refused by the C side."""
+    return None if t is None or t.device.type == "meta" else t.data_ptr()
+
+
+def _bind_resblock(dev, src0, film, w_first, w_gated, w_res=None, src1=None, off0=0, frames=None, init_w=None, form="auto"):
+    """ntm_unet_resblock_forward on resblock_forward's operands, with its block description, workspace and output made on dev."""
+    B, T0 = src0.shape[0], src0.shape[2]
+    c0 = init_w.shape[0] if init_w is not None else src0.shape[1]
+    T = int(frames) if frames is not None else (src1.shape[2] if src1 is not None else T0 - off0)
+    c1, T1 = (0, 0) if src1 is None else src1.shape[1:]
+    spec = BlockSpec(c0, c1, w_first.shape[0], w_gated.shape[0], T, T0, off0, T1, 0, int(init_w is not None), FORMS[form])
+    n = _lib.lib().ntm_unet_resblock_workspace_floats(B, _lib.ctypes.byref(spec))
+    if n < 0:
+        raise _lib.NtmError(f"ntm_unet_resblock_workspace_floats refused: {_lib.lib().ntm_last_error().decode()}")
+    ws = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    out = torch.empty(B, spec.c_out, T, dtype=torch.float32, device=dev)
+    assert src0.is_contiguous() and (src1 is None or src1.is_contiguous()) and film.stride(-1) == 1
+    args = [_addr(src0), _addr(src1), _addr(init_w), _addr(film), 0 if film.shape[0] == 1 else film.stride(0), _addr(w_first),
+            _addr(w_gated), _addr(w_res), B, _lib.ctypes.byref(spec), _addr(ws), _addr(out), None]
+    # above NTM_UNET_WHOLE_MAX_T the tiled form runs the eight dilations in two launches
+    return _Call("ntm_unet_resblock_forward", args, {"src0": 0, "film": 3}, out, ws, launches=2 if T > WHOLE_MAX_T else 1)
+
+
+def _bind_down(dev, x, pyr, kernel, wc, S, width):
+    """ntm_unet_down_combine on down_combine's operands, with its two outputs made on dev."""
+    B, C, Fr = x.shape
+    xo, po = (torch.empty(B, c, -(-Fr // S), dtype=torch.float32, device=dev) for c in (C, 1))
+    assert x.is_contiguous() and pyr.is_contiguous()
+    args = [_addr(x), _addr(pyr), _addr(kernel), _addr(wc), B, C, Fr, S, width, kernel.shape[-1], _addr(xo), _addr(po), None]
+    return _Call("ntm_unet_down_combine", args, {"pyr": 1}, (xo, po))
+
+
+def _bind_up(dev, x, pyr, kernel, wc, S, width, po=None):
+    """ntm_unet_up_combine on up_combine's operands, with its outputs made on dev; po: takes the pyramid instead of a new tensor."""
+    B, C, Fr = x.shape
+    xo = torch.empty(B, C, S * Fr, dtype=torch.float32, device=dev) if S > 1 else None
+    if po is None:
+        po = torch.empty(B, 1, S * Fr, dtype=torch.float32, device=dev)
+    assert x.is_contiguous() and (pyr is None or pyr.is_contiguous())
+    args = [_addr(x), _addr(pyr), 0 if pyr is None else pyr.shape[-1], _addr(kernel), _addr(wc), B, C, Fr, S, width,
+            0 if kernel is None else kernel.shape[-1], _addr(xo), _addr(po), None]
+    return _Call("ntm_unet_up_combine", args, {"po": 12}, (xo, po))
+
+
 def resblock_forward(src0, film, w_first, w_gated, w_res=None, src1=None, off0=0, frames=None, init_w=None, form="auto"):
     """One fused ResnetBlock on the device (ntm_unet_resblock_forward).
     src0 (B, c0, T0), read from frame off0; src1 (B, c1, frames) or None: the second half of the concatenation.  With init_w
@@ -287,38 +340,14 @@ def resblock_forward(src0, film, w_first, w_gated, w_res=None, src1=None, off0=0
     w_first (c_out, c0 + c1, 1); w_gated (n, c_out, c_out, 5), layer l at dilation 2^l; w_res (c_out, c0 + c1, 1) or None (identity).
     form "auto" | "whole" (one workgroup per stream, T <= 1024) | "tiled".  -> (B, c_out, frames)."""
     _require_hip("resblock_forward", src0, src1, film, w_first, w_gated, w_res, init_w)
-    B, T0 = src0.shape[0], src0.shape[2]
-    c0 = init_w.shape[0] if init_w is not None else src0.shape[1]
-    T = int(frames) if frames is not None else (src1.shape[2] if src1 is not None else T0 - off0)
-    c1 = 0 if src1 is None else src1.shape[1]
-    spec = BlockSpec(c0, c1, w_first.shape[0], w_gated.shape[0], T, T0, off0, 0 if src1 is None else src1.shape[2], 0,
-                     int(init_w is not None), FORMS[form])
-    L = _lib.lib()
-    n = L.ntm_unet_resblock_workspace_floats(B, _lib.ctypes.byref(spec))
-    if n < 0:
-        raise _lib.NtmError(f"ntm_unet_resblock_workspace_floats refused: {L.ntm_last_error().decode()}")
-    ws = torch.empty(max(n, 1), dtype=torch.float32, device=src0.device)
-    out = torch.empty(B, spec.c_out, T, dtype=torch.float32, device=src0.device)
-    assert src0.is_contiguous() and (src1 is None or src1.is_contiguous()) and film.stride(-1) == 1
-    _lib.check(L.ntm_unet_resblock_forward(_lib.ptr(src0), _lib.ptr(src1), _lib.ptr(init_w), _lib.ptr(film),
-                                           0 if film.shape[0] == 1 else film.stride(0), _lib.ptr(w_first), _lib.ptr(w_gated),
-                                           _lib.ptr(w_res), B, _lib.ctypes.byref(spec), _lib.ptr(ws), _lib.ptr(out),
-                                           _lib.current_stream()), "ntm_unet_resblock_forward")
-    return out
+    return _bind_resblock(src0.device, src0, film, w_first, w_gated, w_res, src1, off0, frames, init_w, form)(_lib.current_stream())
 
 
 def down_combine(x, pyr, kernel, wc, S, width):
     """Downsample(S) of x (B, C, F) and pyr (B, 1, F) with the (1, 1, 2 width + S) filter, then CombinerDown:
     -> ((conv1x1(pyr_d) + x_d) / sqrt 2, pyr_d), both ceil(F / S) frames (ntm_unet_down_combine)."""
     _require_hip("down_combine", x, pyr, kernel, wc)
-    B, C, Fr = x.shape
-    Fo = -(-Fr // S)
-    xo = torch.empty(B, C, Fo, dtype=torch.float32, device=x.device)
-    po = torch.empty(B, 1, Fo, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().ntm_unet_down_combine(_lib.ptr(x.contiguous()), _lib.ptr(pyr.contiguous()), _lib.ptr(kernel), _lib.ptr(wc),
-                                                B, C, Fr, S, width, kernel.shape[-1], _lib.ptr(xo), _lib.ptr(po),
-                                                _lib.current_stream()), "ntm_unet_down_combine")
-    return xo, po
+    return _bind_down(x.device, x.contiguous(), pyr.contiguous(), kernel, wc, S, width)(_lib.current_stream())
 
 
 def up_combine(x, pyr, kernel, wc, S, width):
@@ -326,16 +355,105 @@ def up_combine(x, pyr, kernel, wc, S, width):
     -> (x, p) both upsampled to S F frames with the (S, 1, 2 width + 1) filter bank.  S = 1 (kernel None): -> (None, p), no
     resampling -- the last level (ntm_unet_up_combine)."""
     _require_hip("up_combine", x, pyr, kernel, wc)
-    B, C, Fr = x.shape
-    xo = torch.empty(B, C, S * Fr, dtype=torch.float32, device=x.device) if S > 1 else None
-    po = torch.empty(B, 1, S * Fr, dtype=torch.float32, device=x.device)
-    if pyr is not None:
-        pyr = pyr.contiguous()
-    _lib.check(_lib.lib().ntm_unet_up_combine(_lib.ptr(x.contiguous()), _lib.ptr(pyr), 0 if pyr is None else pyr.shape[-1],
-                                              _lib.ptr(kernel), _lib.ptr(wc), B, C, Fr, S, width,
-                                              0 if kernel is None else kernel.shape[-1], _lib.ptr(xo), _lib.ptr(po),
-                                              _lib.current_stream()), "ntm_unet_up_combine")
-    return xo, po
+    return _bind_up(x.device, x.contiguous(), None if pyr is None else pyr.contiguous(), kernel, wc, S, width)(_lib.current_stream())
+
+
+class _TorchWalk:
+    """UNet1D._walk in torch ops: the module calls."""
+
+    def __init__(self, net, emb, record):
+        self.init_conv, self.emb, self.record = net.init_conv, emb, record or (lambda name, t: None)
+
+    def rec(self, name, t):
+        self.record(name, t)
+        return t
+
+    def block(self, k, name, blk, x, skip=None, off=0, first=False):
+        if first:
+            x = self.init_conv(x)
+        if skip is not None:
+            x = torch.cat((x[:, :, off:off + skip.shape[2]], skip), 1)
+        return self.rec(name, blk(x, self.emb))
+
+    def down(self, name, down, comb, x, pyr):
+        x, pyr = down(x), down(pyr)
+        return self.rec(name, comb(pyr, x)), pyr
+
+    def up(self, name, up, comb, x, pyr):
+        pyr = self.rec(name, comb(pyr, x))
+        return up(x), up(pyr)
+
+    def final(self, name, comb, x, pyr):
+        return self.rec(name, comb(pyr, x).squeeze(1))
+
+
+class _Plan:
+    """The launches of one evaluation for a (B, T), bound once: UNet1D._walk drives block / down / up / final, which allocate
+    every intermediate and bind every call, nothing runs.  run() then patches the pointers named here and loops over ready calls
+    (the sampler runs 4 to 16 evaluations per sample and a launch is ~10 us: the host must not be the slow side).  The input, the
+    FiLM rows and the output are meta tensors while binding (_addr).  Two streams running one plan would share its buffers."""
+
+    def __init__(self, net, B, T, per_stream, dev):
+        _, (w, _), self.offs, self.gated = net._pack()
+        self.init_w, self.dev = net.init_conv.weight, dev
+        self.x = torch.empty(B, 1, T, device="meta")
+        self.film = torch.empty(B if per_stream else 1, w.shape[0], device="meta")
+        self.calls = []                    # the evaluation, in launch order
+        self.inputs, self.films, self.output = [], [], None   # (args, position[, byte offset into the FiLM row]) to patch
+        self.buffers = {}                  # record name -> the tensor that holds it after a run, in network order
+        self.record_calls = []             # fill the buffers that the evaluation itself never materialises ("ups.i.2")
+
+    @property
+    def launches(self):
+        return sum(c.launches for c in self.calls)
+
+    def run(self, inputs, films, out, stream):
+        src, fbase = inputs.data_ptr(), films.data_ptr()
+        for args, pos in self.inputs:
+            args[pos] = src
+        for args, pos, off in self.films:
+            args[pos] = fbase + off
+        args, pos = self.output
+        args[pos] = out.data_ptr()
+        for call in self.calls:                                   # _Call.__call__ written out: no frame per launch
+            call.args[-1] = stream
+            _lib.check(call.fn(*call.args), call.name)
+
+    def add(self, name, call, buf):
+        self.calls.append(call)
+        self.buffers[name] = buf
+        return buf
+
+    def block(self, k, name, blk, x, skip=None, off=0, first=False):
+        o = self.offs[k]
+        res = None if isinstance(blk.res_conv, nn.Identity) else blk.res_conv.weight
+        call = _bind_resblock(self.dev, x, self.film[:, o:o + blk.dim], blk.first_conv[1].weight, self.gated[k], res, skip, off,
+                              init_w=self.init_w if first else None)
+        self.films.append((call.args, call.slot["film"], 4 * o))
+        if x is self.x:
+            self.inputs.append((call.args, call.slot["src0"]))
+        return self.add(name, call, call.out)
+
+    def down(self, name, down, comb, x, pyr):
+        r = down.resample
+        call = _bind_down(self.dev, x, pyr, r.kernel, comb.conv1x1.weight, r.orig, r.width)
+        if pyr is self.x:
+            self.inputs.append((call.args, call.slot["pyr"]))
+        return self.add(name, call, call.out[0]), call.out[1]
+
+    def up(self, name, up, comb, x, pyr):
+        r, wc = up.resample, comb.conv1x1.weight
+        # the CombinerUp output before upsampling: the fused call never materialises it, a combiner-only call does for record=
+        self.record_calls.append(_bind_up(self.dev, x, pyr, None, wc, 1, 0))
+        self.buffers[name] = self.record_calls[-1].out[1]
+        self.calls.append(_bind_up(self.dev, x, pyr, r.kernel, wc, r.new, r.width))
+        return self.calls[-1].out
+
+    def final(self, name, comb, x, pyr):
+        out = torch.empty(x.shape[0], x.shape[2], device="meta")
+        call = _bind_up(self.dev, x, pyr, None, comb.conv1x1.weight, 1, 0, po=out)
+        self.output = (call.args, call.slot["po"])
+        return self.add(name, call, out)
 
 
 class UNet1D(nn.Module):
@@ -371,55 +489,47 @@ class UNet1D(nn.Module):
                 mods += [Upsample(Ss[i]), CombinerUp(1, dim_out)]
             self.ups.append(nn.ModuleList(mods))
         self.to(device)
-        self._packed = self._plans = None
+        self._packed, self._plans = None, {}
 
     def setup_CQT_len(self, len):
         pass
 
     def _apply(self, fn, *a, **k):
-        self._packed = self._plans = None
+        self._packed, self._plans = None, {}
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
-        self._packed = self._plans = None
+        self._packed, self._plans = None, {}
         return super().load_state_dict(*a, **k)
 
-    # -- the torch path --
-    def forward_torch(self, inputs, sigma, record=None):
-        """The network in torch ops.  record(name, tensor), if given, sees every ResnetBlock's and combiner's output under
-        its module name ("downs.0.0", "downs.0.2", ..., "ups.3.0", "final")."""
-        rec = record or (lambda n, t: None)
-        emb = self.embedding(sigma)
-        x = inputs.unsqueeze(1)
+    def _walk(self, be, x):
+        """The data flow of the network, written once, over a backend `be` that says what a step is (_TorchWalk: module
+        calls; _Plan: bound launches).  x (B, 1, T) -> what be.final returns.  be.block(k, name, blk, x, skip, off, first):
+        ResnetBlock k of _pack()'s order on x -- through init_conv if first; with a skip, on x cropped to the skip's frames
+        from frame `off` (CropConcatBlock's centre crop) and concatenated with it; be.down / be.up(name, resampler, combiner,
+        x, pyr) -> (x, pyr) of the next level; `name` is the module name the result is recorded under."""
+        frames, hs, k = x.shape[2], [], 0
         pyr = x
-        x = self.init_conv(x)
-        hs = []
         for i, mods in enumerate(self.downs):
-            x = mods[0](x, emb)
-            rec(f"downs.{i}.0", x)
+            x = be.block(k, f"downs.{i}.0", mods[0], x, first=i == 0)
+            k += 1
             hs.append(x)
             if len(mods) == 3:
-                x, pyr = mods[1](x), mods[1](pyr)
-                x = mods[2](pyr, x)
-                rec(f"downs.{i}.2", x)
-        x = self.middle[0][0](x, emb)
-        rec("middle.0.0", x)
+                x, pyr = be.down(f"downs.{i}.2", mods[1], mods[2], x, pyr)
+        x = be.block(k, "middle.0.0", self.middle[0][0], x)
+        k += 1
         pyr = None
         for i, mods in enumerate(self.ups):
             skip = hs.pop()
-            x = torch.cat((_crop(x, skip.shape[2])[1], skip), 1)
-            x = mods[0](x, emb)
-            rec(f"ups.{i}.0", x)
+            off = (x.shape[2] - skip.shape[2]) // 2
+            if off < 0:
+                raise ValueError(f"UNet1D: the up path carries {x.shape[2]} frames into a skip of {skip.shape[2]}: nothing to crop")
+            x = be.block(k, f"ups.{i}.0", mods[0], x, skip, off)
+            k += 1
             if len(mods) == 3:
-                pyr = mods[2](pyr, x)
-                rec(f"ups.{i}.2", pyr)
-                x, pyr = mods[1](x), mods[1](pyr)
-            else:
-                pyr = self._final_combiner()(pyr, x)
-        pred = pyr.squeeze(1)
-        rec("final", pred)
-        assert pred.shape == inputs.shape, "bad shapes"
-        return pred
+                x, pyr = be.up(f"ups.{i}.2", mods[1], mods[2], x, pyr)
+        assert x.shape[2] == frames, "bad shapes"
+        return be.final("final", self._final_combiner(), x, pyr)
 
     # The reference's last level calls `combiner(pyr, x)` with the combiner left over from the level before (the loop variable
     # of code/networks/unet_1d.py:163-183): ups[depth - 2][2].
@@ -428,12 +538,18 @@ class UNet1D(nn.Module):
             raise ValueError("UNet1D: depth >= 2 (the last level reuses the combiner of the level before, as the reference does)")
         return self.ups[self.depth - 2][2]
 
+    # -- the torch path --
+    def forward_torch(self, inputs, sigma, record=None):
+        """The network in torch ops.  record(name, tensor), if given, sees every ResnetBlock's and combiner's output under
+        its module name ("downs.0.0", "downs.0.2", ..., "ups.3.0", "final")."""
+        return self._walk(_TorchWalk(self, self.embedding(sigma), record), inputs.unsqueeze(1))
+
     # -- the HIP path --
     def _pack(self):
         """The parameters in the layouts the kernels read, gathered once: per block the stacked gated weights; all FiLM
         matrices as one so that one matmul gives every block's vector."""
         if self._packed is None:
-            blocks = [m[0] for m in self.downs] + [self.middle[0][0]] + [m[0] for m in self.ups]
+            blocks = [m for m in self.modules() if isinstance(m, ResnetBlock)]      # registration order: the order of _walk
             films = (torch.cat([b.film.output_layer.weight for b in blocks], 0).float().contiguous(),
                      torch.cat([b.film.output_layer.bias for b in blocks], 0).float().contiguous())
             offs, o = [], 0
@@ -449,163 +565,37 @@ class UNet1D(nn.Module):
         _, (w, b), _, _ = self._pack()
         return F.linear(self.embedding(sigma), w, b)
 
-    def _build_plan(self, B, T, per_stream, dev):
-        """The launches of one evaluation for (B, T) with their arguments bound once: every intermediate tensor, block
-        description and pointer is made here, so that an evaluation is a loop over ready calls (the sampler runs 4 to 16 of
-        them per sample and a launch is ~10 us: the host must not be the slow side).  Per call only the input, the FiLM
-        vectors, the output and the stream are patched in."""
-        L, by = _lib.lib(), _lib.ctypes.byref
-        blocks, _, offs, gated = self._pack()
-        total = sum(b.dim for b in blocks)
-        keep, calls, p_in, p_film = [], [], [], []
-
-        def new(*shape):
-            keep.append(torch.empty(*shape, dtype=torch.float32, device=dev))
-            return keep[-1]
-
-        def ptr(t):
-            return None if t is None else t.data_ptr()
-
-        def block(k, src0, c0, T0, src1=None, off0=0, frames=None, init_w=None):
-            b = blocks[k]
-            Tb = frames if frames is not None else T0 - off0
-            c1 = 0 if src1 is None else src1.shape[1]
-            spec = BlockSpec(c0, c1, b.dim_out, len(b.H), Tb, T0, off0, 0 if src1 is None else src1.shape[2], 0, int(init_w is not None), 0)
-            n = L.ntm_unet_resblock_workspace_floats(B, by(spec))
-            if n < 0:
-                raise _lib.NtmError(f"ntm_unet_resblock_workspace_floats refused: {L.ntm_last_error().decode()}")
-            res = None if isinstance(b.res_conv, nn.Identity) else b.res_conv.weight
-            out = new(B, b.dim_out, Tb)
-            keep.append(spec)
-            calls.append(("ntm_unet_resblock_forward", L.ntm_unet_resblock_forward,
-                          [ptr(src0), ptr(src1), ptr(init_w), None, total if per_stream else 0, ptr(b.first_conv[1].weight), ptr(gated[k]),
-                           ptr(res), B, by(spec), ptr(new(max(n, 1))), ptr(out), None]))
-            p_film.append((len(calls) - 1, 3, 4 * offs[k]))
-            return out
-
-        k, hs, Tl = 0, [], T
-        x = pyr = None                                   # level 0 reads the caller's input
-        for i, mods in enumerate(self.downs):
-            if i == 0:
-                x = block(k, None, self.Ns[0], T, init_w=self.init_conv.weight)
-                p_in.append((len(calls) - 1, 0))
-            else:
-                x = block(k, x, x.shape[1], x.shape[2])
-            k += 1
-            hs.append(x)
-            if len(mods) == 3:
-                r = mods[1].resample
-                Fo = -(-Tl // r.orig)
-                xo, po = new(B, x.shape[1], Fo), new(B, 1, Fo)
-                calls.append(("ntm_unet_down_combine", L.ntm_unet_down_combine,
-                              [ptr(x), ptr(pyr), ptr(r.kernel), ptr(mods[2].conv1x1.weight), B, x.shape[1], Tl, r.orig, r.width,
-                               r.kernel.shape[-1], ptr(xo), ptr(po), None]))
-                if i == 0:
-                    p_in.append((len(calls) - 1, 1))
-                x, pyr, Tl = xo, po, Fo
-        x = block(k, x, x.shape[1], x.shape[2])
-        k += 1
-        pyr = None
-        for i, mods in enumerate(self.ups):
-            skip = hs.pop()
-            off = (x.shape[2] - skip.shape[2]) // 2
-            if off < 0:
-                raise ValueError(f"UNet1D: the up path carries {x.shape[2]} frames into a skip of {skip.shape[2]}")
-            x = block(k, x, x.shape[1], x.shape[2], skip, off0=off, frames=skip.shape[2])
-            k += 1
-            Fr, C = x.shape[2], x.shape[1]
-            if len(mods) == 3:
-                r = mods[1].resample
-                xo, po = new(B, C, r.new * Fr), new(B, 1, r.new * Fr)
-                calls.append(("ntm_unet_up_combine", L.ntm_unet_up_combine,
-                              [ptr(x), ptr(pyr), 0 if pyr is None else pyr.shape[-1], ptr(r.kernel), ptr(mods[2].conv1x1.weight), B, C,
-                               Fr, r.new, r.width, r.kernel.shape[-1], ptr(xo), ptr(po), None]))
-                x, pyr = xo, po
-            else:
-                if Fr != T:
-                    raise AssertionError("bad shapes")
-                calls.append(("ntm_unet_up_combine", L.ntm_unet_up_combine,
-                              [ptr(x), ptr(pyr), 0 if pyr is None else pyr.shape[-1], None, ptr(self._final_combiner().conv1x1.weight), B,
-                               C, Fr, 1, 0, 0, None, None, None]))
-        return {"calls": calls, "in": p_in, "film": p_film, "keep": keep}
-
-    def _run_plan(self, inputs, films):
-        B, T = inputs.shape
-        key = (B, T, films.shape[0] != 1, inputs.device)
-        if self._plans is None:
-            self._plans = {}
-        plan = self._plans.get(key)
-        if plan is None:
-            if films.shape[0] not in (1, B):
-                raise ValueError(f"UNet1D.forward: sigma has {films.shape[0]} rows for a batch of {B}")
-            plan = self._plans[key] = self._build_plan(B, T, key[2], inputs.device)
-        out = torch.empty(B, T, dtype=torch.float32, device=inputs.device)
-        calls, stream = plan["calls"], _lib.current_stream()
-        assert films.is_contiguous() or films.shape[0] == 1
-        src, fbase = inputs.data_ptr(), films.data_ptr()
-        for ci, ai in plan["in"]:
-            calls[ci][2][ai] = src
-        for ci, ai, off in plan["film"]:
-            calls[ci][2][ai] = fbase + off
-        calls[-1][2][12] = out.data_ptr()
-        for name, fn, args in calls:
-            args[-1] = stream
-            _lib.check(fn(*args), name)
-        return out
+    def _plan_for(self, B, T, per_stream, dev):
+        """The _Plan of one evaluation for (B, T) on dev, with one FiLM row per stream or one for all: built on first use."""
+        key = (B, T, per_stream, dev)
+        if key not in self._plans:
+            plan = _Plan(self, *key)
+            self._walk(plan, plan.x)
+            self._plans[key] = plan
+        return self._plans[key]
 
     def forward(self, inputs, sigma, films=None, record=None):
         """The network on the HIP path: inputs (B, T), sigma (1 | B, 1) (or `films` from self.films(sigma), which the sampler
-        computes once per step at construction).  -> (B, T)."""
+        computes once per step at construction).  -> (B, T).  record(name, tensor), if given, then sees what forward_torch's
+        sees, from this evaluation's own buffers (as clones: the next evaluation writes them again)."""
         if not inputs.is_cuda:
             raise RuntimeError(f"UNet1D.forward: HIP device only (no CPU fallback); use forward_torch.  Supported: {SUPPORTED}")
-        rec = record or (lambda n, t: None)
-        blocks, _, offs, gated = self._pack()
         if films is None:
             films = self.films(sigma.reshape(-1, 1).float())
         inputs = inputs.float().contiguous()
-        if record is None:
-            return self._run_plan(inputs, films)
-
-        def run(k, src0, src1=None, off0=0, frames=None, init_w=None):
-            b = blocks[k]
-            res = None if isinstance(b.res_conv, nn.Identity) else b.res_conv.weight
-            return resblock_forward(src0, films[:, offs[k]:offs[k] + b.dim], b.first_conv[1].weight, gated[k], res, src1, off0,
-                                    frames, init_w)
-
-        x = pyr = inputs.unsqueeze(1)
-        hs, k = [], 0
-        for i, mods in enumerate(self.downs):
-            x = run(k, x, init_w=self.init_conv.weight if i == 0 else None)
-            k += 1
-            rec(f"downs.{i}.0", x)
-            hs.append(x)
-            if len(mods) == 3:
-                r = mods[1].resample
-                x, pyr = down_combine(x, pyr, r.kernel, mods[2].conv1x1.weight, r.orig, r.width)
-                rec(f"downs.{i}.2", x)
-        x = run(k, x)
-        k += 1
-        rec("middle.0.0", x)
-        pyr = None
-        for i, mods in enumerate(self.ups):
-            skip = hs.pop()
-            off = (x.shape[2] - skip.shape[2]) // 2
-            if off < 0:
-                raise ValueError(f"UNet1D: the up path carries {x.shape[2]} frames into a skip of {skip.shape[2]}")
-            x = run(k, x, skip, off0=off, frames=skip.shape[2])
-            k += 1
-            rec(f"ups.{i}.0", x)
-            if len(mods) == 3:
-                r = mods[1].resample
-                if record is not None:
-                    rec(f"ups.{i}.2", up_combine(x, pyr, None, mods[2].conv1x1.weight, 1, 0)[1])
-                x, pyr = up_combine(x, pyr, r.kernel, mods[2].conv1x1.weight, r.new, r.width)
-            else:
-                pyr = up_combine(x, pyr, None, self._final_combiner().conv1x1.weight, 1, 0)[1]
-        pred = pyr.squeeze(1)
-        rec("final", pred)
-        assert pred.shape == inputs.shape, "bad shapes"
-        return pred
+        B, T = inputs.shape
+        if films.shape[0] not in (1, B):
+            raise ValueError(f"UNet1D.forward: sigma has {films.shape[0]} rows for a batch of {B}")
+        assert films.is_contiguous() or films.shape[0] == 1
+        plan = self._plan_for(B, T, films.shape[0] != 1, inputs.device)
+        out, stream = torch.empty(B, T, dtype=torch.float32, device=inputs.device), _lib.current_stream()
+        plan.run(inputs, films, out, stream)
+        if record is not None:
+            for call in plan.record_calls:
+                call(stream)
+            for name, buf in plan.buffers.items():
+                record(name, out if buf.device.type == "meta" else buf.clone())
+        return out
 
 
 # ---- checkpoints -----------------------------------------------------------------------------------------------------------------------
@@ -742,11 +732,13 @@ class DiffusionGenerator:
     def _sample(self, B, x_outpaint=None, mask=None, draws=None):
         steps = self._plan()
         z = self._draw(draws, B) * self.schedule[0]
+        if self.hip and mask is not None:                  # once per sample: every step reads the same two
+            x_outpaint, mask = self._outpaint_operands(B, self.seg_len, x_outpaint, mask)
         for st in steps:
             eps = self._draw(draws, B) if st["eps"] is not None else None
             n = self._draw(draws, B) if mask is not None else None
             if self.hip:
-                z = self._hip_step(z, st, eps, x_outpaint, mask, n)
+                z = self._hip_step(z, st, eps, x_outpaint, mask, n, prepared=True)
                 continue
             s0, s1 = st["s0"].to(z), st["s1"].to(z)
             if eps is not None:
@@ -756,8 +748,14 @@ class DiffusionGenerator:
             z = self.ode_update(z, s1, s0)
         return z
 
-    def _hip_step(self, z, st, eps, x_outpaint, mask, n):
-        """One sampler step on the device: ntm_edm_pre, the network, ntm_edm_post."""
+    @staticmethod
+    def _outpaint_operands(B, T, x_outpaint, mask):
+        """x_outpaint and mask as ntm_edm_pre reads them: fp32, contiguous, (B, T) and (1 | B, T)."""
+        mask = mask.float().expand(-1, T).contiguous() if mask.shape[0] != 1 else mask.float().contiguous()
+        return x_outpaint.float().expand(B, T).contiguous(), mask
+
+    def _hip_step(self, z, st, eps, x_outpaint, mask, n, prepared=False):
+        """One sampler step on the device: ntm_edm_pre, the network, ntm_edm_post (prepared: by _outpaint_operands already)."""
         L, f = _lib.lib(), st["f"]
         z = z.float().contiguous()
         B, T = z.shape
@@ -765,8 +763,8 @@ class DiffusionGenerator:
             self._bufs = (torch.empty_like(z), torch.empty_like(z))       # the step's two intermediates, reused by every step
         zin, net_in = self._bufs
         if mask is not None:
-            mask = mask.float().expand(-1, T).contiguous() if mask.shape[0] != 1 else mask.float().contiguous()
-            x_outpaint = x_outpaint.float().expand(B, T).contiguous()
+            if not prepared:
+                x_outpaint, mask = self._outpaint_operands(B, T, x_outpaint, mask)
             n = n.float().contiguous()
         if eps is not None:
             eps = eps.float().contiguous()

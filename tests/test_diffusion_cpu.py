@@ -200,6 +200,32 @@ def test_refusals_of_the_host_layer():
         diffusion.resblock_forward(torch.zeros(1, 8, 16), torch.zeros(1, 8), torch.zeros(8, 8, 1), torch.zeros(8, 8, 8, 5))
 
 
+# (B, T) -> bound calls, launches (a tiled block is two).  5000 -> 1250 -> 313 -> 79 -> 20 -> 5: tiled blocks and odd crops;
+# 1024: a bottom level of one frame; 65536: the shipped segment
+PLAN_CASES = [("trajectories", 2, 512, 16, 16), ("toytrajectories", 1, 512, 16, 16), ("noise", 1, 1024, 24, 24),
+              ("noise", 3, 5000, 24, 28), ("noise", 1, 65536, 24, 30)]
+
+
+@pytest.mark.parametrize("name,B,T,calls,launches", PLAN_CASES)
+def test_plan_binds_the_tensors_forward_torch_records(gens, name, B, T, calls, launches):
+    """The plan of the HIP path builds on CPU tensors (it allocates and asks the host-side workspace function): its named
+    buffers are forward_torch's recorded tensors, name by name and shape by shape, and its launch counts are pinned."""
+    net, cpu = gens[name].network, torch.device("cpu")
+    plan = net._plan_for(B, T, False, cpu)
+    rec = {}
+    with torch.no_grad():
+        net.forward_torch(torch.zeros(B, T), torch.tensor([[-1.5]]), record=rec.__setitem__)
+    assert tuple(plan.buffers) == tuple(rec)
+    for n, v in rec.items():
+        assert plan.buffers[n].shape == v.shape, n
+    assert len(plan.calls) == calls and plan.launches == launches
+    assert len(plan.record_calls) == net.depth - 1 and len(plan.inputs) == 2 and len(plan.films) == 2 * net.depth + 1
+    assert net._plan_for(B, T, False, cpu) is plan                       # served from the cache
+    assert net._plan_for(B, T, True, cpu) is not plan
+    net.load_state_dict(net.state_dict())
+    assert not net._plans and net._plan_for(B, T, False, cpu) is not plan
+
+
 def test_entry_points_are_in_the_header_and_the_binding():
     header = open(os.path.join(ROOT, "include", "ntm.h")).read()
     L = ntm_amd._lib.lib()

@@ -204,6 +204,27 @@ def test_network_batch_of_three_equals_three_calls_and_repeats(gens):
             assert torch.equal(y[i:i + 1], net(x[i:i + 1], s)), i
 
 
+@pytest.mark.parametrize("sigma", [[[-1.5]], [[-1.5], [-0.7], [-2.2]]], ids=["shared_sigma", "per_stream_sigma"])
+def test_recording_reports_the_plans_own_buffers(gens, sigma):
+    """record= on the shipped path, at a shape with tiled blocks and odd crops (5000 -> 1250 -> 313 -> 79 -> 20 -> 5): it
+    disturbs nothing, names what forward_torch names, and every tensor meets the bar of the kernel-level cases."""
+    net, cpu = gens["noise"].network, generator("noise", **NOISE_SMALL).network
+    x, s = normal(7, (3, 5000)), torch.tensor(sigma)
+    rec, refs = {}, ({}, {})
+    with torch.no_grad():
+        y = net(x.to(DEV), s.to(DEV), record=rec.__setitem__)
+        assert torch.equal(y, rec["final"]) and torch.equal(y, net(x.to(DEV), s.to(DEV)))
+        for r, dt in zip(refs, (torch.float64, torch.float32)):
+            cpu.to(dt).forward_torch(x.to(dt), s.to(dt), record=r.__setitem__)
+    assert tuple(rec) == tuple(refs[0])
+    for name, got in rec.items():
+        r64, r32 = refs[0][name], refs[1][name]
+        scale = float(r64.abs().max())
+        own, err = float((r32.double() - r64).abs().max()) / scale, float((got.cpu().double() - r64).abs().max()) / scale
+        print(f"{name}: error {err:.3e}, torch float32's own {own:.3e}, ratio {err / own:.2f}")
+        assert got.shape == r64.shape and err <= 3.0 * max(own, 2.0 ** -23), name
+
+
 def test_sample_batch_streams_equal_their_own_sample_bit_for_bit(gens):
     n = gens["noise"]                     # the epsilon branch: two draws per step
     streams = [[next(d) for _ in range(8)] for d in (draws(300 + i, 1, 16384) for i in range(3))]

@@ -36,12 +36,7 @@ def timed(fn, reps, warmup=2):
 
 def launches_per_evaluation(gen, T):
     """Kernel launches of one network evaluation on the HIP path: the calls of the bound plan, a tiled block counting two."""
-    plan = gen.network._build_plan(1, T, False, torch.device("cuda"))
-    n = 0
-    for name, _, args in plan["calls"]:
-        tiled = name == "ntm_unet_resblock_forward" and args[9]._obj.T > diffusion.WHOLE_MAX_T
-        n += 2 if tiled else 1
-    return n
+    return gen.network._plan_for(1, T, False, torch.device("cuda")).launches
 
 
 def main():
