@@ -805,6 +805,41 @@ int ntm_edm_pre(const float *z, const float *eps, float eps_scale, float snoise,
                 void *stream);
 int ntm_edm_post(const float *z, const float *F, float cskip, float cout, float b2, float k, int64_t N, float *out, void *stream);
 
+/*
+ * Training of that network (code/train-diffusion.py): the ResnetBlock in its whole form (T <= NTM_UNET_WHOLE_MAX_T, form AUTO or
+ * WHOLE) with its adjoint (csrc/unet_train.hip).  Additions within ABI version 9.  Operands and layouts are
+ * ntm_unet_resblock_forward's; with y_0 = W_first gelu(x) and y_{l+1} = (y_l + conv_l(gelu(y_l))) / sqrt 2:
+ *
+ * ntm_unet_resblock_forward_save: the forward, which also writes y_0 .. y_{n_layers - 1} to ysave [B][n_layers][c_out][T],
+ *   ntm_unet_resblock_save_floats(B, blk) floats.  out is bit-identical to ntm_unet_resblock_forward's whole form (one body).
+ * ntm_unet_resblock_backward: from gout [B][c_out][T] and ysave, one workgroup per stream, two launches (the gated layers,
+ *   last to first; then the 1x1s, FiLM and the sources) with gy_0 between them in ws [B][c_out][T] (B c_out T floats):
+ *     g_src0 [B][c0][T0], g_src1 [B][c1][T1]   the sources' gradients, 0 at frames the block did not read; either may be NULL
+ *                                              (not wanted); with init the waveform takes none and g_src0 must be NULL
+ *     gfilm [B][c0 + c1]                       per stream (the caller sums the rows of a shared FiLM vector)
+ *     partials [B][W][P]                       weight-gradient partials, one per stream and wave that owns frames:
+ *                                              W = min(8, ceil(T / 16)), P = ntm_unet_resblock_wgrad_floats(blk) =
+ *                                              n_layers c_out c_out 5 + 2 c_out (c0 + c1) + (init ? 5 c0 : 0), laid out as
+ *                                              dW_gated | dW_first | dW_res (zeros without W_res) | dinit_w;
+ *                                              ntm_unet_resblock_partial_floats(B, blk) = B W P floats
+ * ntm_unet_wgrad_reduce: out[e] = sum_{p < count} partials[p n + e], e < n, added in index order in fp64, rounded once.
+ *   No atomics anywhere: equal calls give equal bits, and a stream's g_src0, g_src1 and gfilm do not depend on its batch.
+ *   The three size queries return -1 on arguments the entry points refuse.  Refused (NTM_EINVAL, before anything touches a
+ *   device): what ntm_unet_resblock_forward refuses, T > NTM_UNET_WHOLE_MAX_T or the tiled form, null ysave / out / gout / ws /
+ *   gfilm / partials, g_src0 with init, g_src1 with c1 == 0, negative count or n.  B == 0 returns NTM_OK.
+ */
+int64_t ntm_unet_resblock_save_floats(int64_t B, const ntm_unet_block *blk);
+int64_t ntm_unet_resblock_wgrad_floats(const ntm_unet_block *blk);
+int64_t ntm_unet_resblock_partial_floats(int64_t B, const ntm_unet_block *blk);
+int ntm_unet_resblock_forward_save(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                                   const float *w_first, const float *w_gated, const float *w_res, int64_t B,
+                                   const ntm_unet_block *blk, float *ysave, float *out, void *stream);
+int ntm_unet_resblock_backward(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                               const float *w_first, const float *w_gated, const float *w_res, int64_t B, const ntm_unet_block *blk,
+                               const float *ysave, const float *gout, float *ws, float *g_src0, float *g_src1, float *gfilm,
+                               float *partials, void *stream);
+int ntm_unet_wgrad_reduce(const float *partials, int64_t count, int64_t n, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

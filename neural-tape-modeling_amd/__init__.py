@@ -16,8 +16,8 @@ from .tape import Tape, TapeMagnetization  # noqa: F401
 from .tcn import TCN  # noqa: F401
 from .utilities import nextpow2, parse_hidden_size, parse_loss, parse_model  # noqa: F401
 from . import adversarial, critics, diffusion, distributed, evaluation, feeder, harness, weights  # noqa: F401
-from .diffusion import DiffusionGenerator, UNet1D, load_config  # noqa: F401
+from .diffusion import DiffusionGenerator, EDMTrainer, UNet1D, load_config  # noqa: F401
 
 __all__ = ["RNN", "DiffDelRNN", "Replicas", "TimeVaryingDelayLine", "TCN", "Tape", "TapeMagnetization", "ESRLoss", "DCPreESR", "MRSTFTLoss", "ValLossSupervised", "TimeFreqConverter", "stft_sums", "spec_sums", "mel_sums", "esr_dcpre_sums", "esr_sums", "esr_per_segment",
            "parse_hidden_size", "parse_model", "parse_loss", "nextpow2", "weights", "critics", "adversarial", "evaluation", "build", "NtmError",
-           "diffusion", "UNet1D", "DiffusionGenerator", "load_config"]
+           "diffusion", "UNet1D", "DiffusionGenerator", "EDMTrainer", "load_config"]

@@ -86,6 +86,12 @@ _SIGNATURES = {
     # the diffusion generators (additions within ABI version 9): blk is a pointer to diffusion.BlockSpec (ntm_unet_block)
     "ntm_unet_resblock_workspace_floats": (_i64, [_i64, _vp]),
     "ntm_unet_resblock_forward": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ntm_unet_resblock_save_floats": (_i64, [_i64, _vp]),
+    "ntm_unet_resblock_wgrad_floats": (_i64, [_vp]),
+    "ntm_unet_resblock_partial_floats": (_i64, [_i64, _vp]),
+    "ntm_unet_resblock_forward_save": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ntm_unet_resblock_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ntm_unet_wgrad_reduce": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "ntm_unet_down_combine": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp]),
     "ntm_unet_up_combine": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp]),
     "ntm_unet_upsample": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),

@@ -314,6 +314,87 @@ int ntm_unet_resblock_forward(const float *src0, const float *src1, const float 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_forward");
 }
 
+// the argument checks the training entry points of the block share: the forward's, and the whole form only
+static int unet_train_check(const std::string &w, int64_t B, const ntm_unet_block *k)
+{
+    if (int rc = unet_block_check(w, B, k)) return rc;
+    if (k->T > NTM_UNET_WHOLE_MAX_T || k->form == NTM_UNET_TILED)
+        return fail(NTM_EINVAL, w + ": the whole form only, T <= 1024 (the adjoint of the tiled form is not built)");
+    return NTM_OK;
+}
+
+int64_t ntm_unet_resblock_save_floats(int64_t B, const ntm_unet_block *blk)
+{
+    if (unet_train_check("ntm_unet_resblock_save_floats", B, blk) != NTM_OK) return -1;
+    return B * blk->n_layers * blk->c_out * blk->T;
+}
+
+int64_t ntm_unet_resblock_wgrad_floats(const ntm_unet_block *blk)
+{
+    if (unet_train_check("ntm_unet_resblock_wgrad_floats", 0, blk) != NTM_OK) return -1;
+    return ntm::unet_block_wgrad_floats(*blk);
+}
+
+int64_t ntm_unet_resblock_partial_floats(int64_t B, const ntm_unet_block *blk)
+{
+    if (unet_train_check("ntm_unet_resblock_partial_floats", B, blk) != NTM_OK) return -1;
+    return B * ntm::unet_block_partials(*blk) * ntm::unet_block_wgrad_floats(*blk);
+}
+
+// what _forward_save and _backward check of the forward's operands
+static int unet_train_operands(const std::string &w, const float *src0, const float *src1, const float *init_w, const float *film,
+                               int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res, int64_t B,
+                               const ntm_unet_block *blk)
+{
+    if (int rc = unet_train_check(w, B, blk)) return rc;
+    const int cin = blk->c0 + blk->c1;
+    if (film_stride != 0 && film_stride < cin) return fail(NTM_EINVAL, w + ": film_stride must be 0 or at least c0 + c1");
+    if (!w_res && cin != blk->c_out) return fail(NTM_EINVAL, w + ": an identity residual (w_res == NULL) needs c0 + c1 == c_out");
+    if (B > 0 && (!src0 || !film || !w_first || !w_gated || (blk->c1 > 0 && !src1) || (blk->init && !init_w)))
+        return fail(NTM_EINVAL, w + ": null pointer");
+    return NTM_OK;
+}
+
+int ntm_unet_resblock_forward_save(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                                   const float *w_first, const float *w_gated, const float *w_res, int64_t B,
+                                   const ntm_unet_block *blk, float *ysave, float *out, void *stream)
+{
+    const std::string w("ntm_unet_resblock_forward_save");
+    if (int rc = unet_train_operands(w, src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, blk)) return rc;
+    if (B == 0) return NTM_OK;
+    if (!ysave || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    if (out == src0 || out == src1) return fail(NTM_EINVAL, w + ": out must not alias a source");
+    hipError_t e = ntm::launch_unet_block_save(src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, *blk, ysave, out,
+                                               (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_forward_save");
+}
+
+int ntm_unet_resblock_backward(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                               const float *w_first, const float *w_gated, const float *w_res, int64_t B, const ntm_unet_block *blk,
+                               const float *ysave, const float *gout, float *ws, float *g_src0, float *g_src1, float *gfilm,
+                               float *partials, void *stream)
+{
+    const std::string w("ntm_unet_resblock_backward");
+    if (int rc = unet_train_operands(w, src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, blk)) return rc;
+    if (blk->init && g_src0) return fail(NTM_EINVAL, w + ": with init the waveform takes no gradient (g_src0 must be NULL)");
+    if (blk->c1 == 0 && g_src1) return fail(NTM_EINVAL, w + ": g_src1 without a second source");
+    if (B == 0) return NTM_OK;
+    if (!ysave || !gout || !ws || !gfilm || !partials) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_unet_block_backward(src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, *blk, ysave, gout,
+                                                   ws, g_src0, g_src1, gfilm, partials, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_backward");
+}
+
+int ntm_unet_wgrad_reduce(const float *partials, int64_t count, int64_t n, float *out, void *stream)
+{
+    if (count < 0 || n < 0) return fail(NTM_EINVAL, "ntm_unet_wgrad_reduce: negative size");
+    if (n / 256 > 0x7fffffff) return fail(NTM_EINVAL, "ntm_unet_wgrad_reduce: n must be below 2^39");
+    if (n == 0) return NTM_OK;
+    if (!out || (count > 0 && !partials)) return fail(NTM_EINVAL, "ntm_unet_wgrad_reduce: null pointer");
+    hipError_t e = ntm::launch_unet_wgrad_reduce(partials, count, n, out, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_wgrad_reduce");
+}
+
 // the size checks of the three resampling entry points
 static int unet_resample_check(const std::string &w, int64_t B, int C, int64_t F, int S, int width, int taps, int64_t Fo)
 {

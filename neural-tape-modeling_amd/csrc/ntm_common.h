@@ -173,6 +173,17 @@ hipError_t launch_edm_pre(const float *z, const float *eps, float eps_scale, flo
                           float *net_in, hipStream_t stream);
 hipError_t launch_edm_post(const float *z, const float *F, float cskip, float cout, float b2, float k, int64_t N, float *out,
                            hipStream_t stream);
+// the training of that network (unet_train.hip): the whole-form block with y_0 .. y_{n-1} saved, its adjoint, the reduction
+int64_t unet_block_wgrad_floats(const ntm_unet_block &k);
+int unet_block_partials(const ntm_unet_block &k);
+hipError_t launch_unet_block_save(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
+                                  const float *w_first, const float *w_gated, const float *w_res, int64_t B, const ntm_unet_block &k,
+                                  float *ysave, float *out, hipStream_t stream);
+hipError_t launch_unet_block_backward(const float *src0, const float *src1, const float *init_w, const float *film,
+                                      int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res, int64_t B,
+                                      const ntm_unet_block &k, const float *ysave, const float *gout, float *ws, float *g_src0,
+                                      float *g_src1, float *gfilm, float *part, hipStream_t stream);
+hipError_t launch_unet_wgrad_reduce(const float *part, int64_t count, int64_t n, float *out, hipStream_t stream);
 hipError_t launch_delay_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
                             int32_t *err_flag, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,

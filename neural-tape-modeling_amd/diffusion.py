@@ -6,15 +6,19 @@ code/networks/unet_1d.py): the wow-and-flutter delay trajectories that drive Dif
                                _walk: the network's data flow, written once; forward_torch: it in torch ops (this project's
                                restatement, any dtype, any device); forward: it as launches of csrc/unet_kernels.hip bound once
                                per (B, T), HIP device only; record= of either reports the same names from the path that ran
+                               forward_train: it as a differentiable graph whose ResnetBlocks of at most 1024 frames are HIP
+                               nodes (training.ResBlockFn on csrc/unet_train.hip), everything else torch ops under autograd
   DiffusionGenerator(args, device)   the EDM sampler with the reference's attributes and methods
+  EDMTrainer(args, network, optimizer, device, backend)   the EDM training step and EMA of code/train-diffusion.py
 
-Inference only: nothing here records a graph.  Two additions to the reference's protocol, both keyword arguments:
+The sampler and `forward` are inference only.  Two additions to the reference's protocol, both keyword arguments:
   draws=   an iterator of (B, seg_len) tensors that stands in for torch.randn, in the reference's draw order for one sample
            (the first latent; then per step the extra noise where gamma != 0, then the outpainting noise);
   sample_batch(B) / sample_long(Length, batch=B) run B independent samples through every launch together where the reference
            loops over them: the draw order then differs from the reference's loop, the distribution does not, and with draws=
            given per stream every stream equals its own sample() bit for bit.
 """
+import copy
 import math
 import os
 import pickle
@@ -387,6 +391,25 @@ class _TorchWalk:
         return self.rec(name, comb(pyr, x).squeeze(1))
 
 
+class _TrainWalk(_TorchWalk):
+    """UNet1D._walk for training: a ResnetBlock of at most WHOLE_MAX_T frames is ONE autograd node on the HIP kernels
+    (training.ResBlockFn: ntm_unet_resblock_forward_save / _backward); a longer one (the upper levels of the noise net) is the
+    torch module, and so are the resample, combine, FiLM and embedding steps, all under autograd.  The node reads the
+    parameters themselves -- the gated weights stacked anew on every call, so that autograd routes the stack's gradient to the
+    eight layers -- never _pack()'s copy."""
+
+    def block(self, k, name, blk, x, skip=None, off=0, first=False):
+        frames = skip.shape[2] if skip is not None else x.shape[2]
+        if frames > WHOLE_MAX_T:
+            return super().block(k, name, blk, x, skip, off, first)
+        from .training import ResBlockFn
+        res = None if isinstance(blk.res_conv, nn.Identity) else blk.res_conv.weight
+        w_gated = torch.stack([h.conv.weight for h in blk.H])
+        out = ResBlockFn.apply(x, skip, blk.film.output_layer(self.emb), blk.first_conv[1].weight, w_gated, res,
+                               self.init_conv.weight if first else None, off)
+        return self.rec(name, out)
+
+
 class _Plan:
     """The launches of one evaluation for a (B, T), bound once: UNet1D._walk drives block / down / up / final, which allocate
     every intermediate and bind every call, nothing runs.  run() then patches the pointers named here and loops over ready calls
@@ -544,11 +567,33 @@ class UNet1D(nn.Module):
         its module name ("downs.0.0", "downs.0.2", ..., "ups.3.0", "final")."""
         return self._walk(_TorchWalk(self, self.embedding(sigma), record), inputs.unsqueeze(1))
 
+    # -- the training path --
+    def forward_train(self, inputs, sigma, record=None):
+        """The network as a differentiable graph whose ResnetBlocks of at most WHOLE_MAX_T frames are HIP nodes (_TrainWalk):
+        inputs (B, T), sigma (1 | B, 1) per stream -> (B, T).  HIP device only; `forward` (inference, bound plans) is
+        untouched by it."""
+        if not inputs.is_cuda:
+            raise RuntimeError(f"UNet1D.forward_train: HIP device only (no CPU fallback); use forward_torch.  Supported: {SUPPORTED}")
+        emb = self.embedding(sigma.reshape(-1, 1).float())
+        if emb.shape[0] not in (1, inputs.shape[0]):
+            raise ValueError(f"UNet1D.forward_train: sigma has {emb.shape[0]} rows for a batch of {inputs.shape[0]}")
+        return self._walk(_TrainWalk(self, emb, record), inputs.float().unsqueeze(1))
+
     # -- the HIP path --
+    def _versions(self):
+        """What _pack()'s copies and the plans bound to them depend on: every parameter's storage and its in-place version
+        counter, which an optimiser's step or any `p.add_()` moves."""
+        return tuple((p._version, p.data_ptr()) for p in self.parameters())
+
     def _pack(self):
-        """The parameters in the layouts the kernels read, gathered once: per block the stacked gated weights; all FiLM
-        matrices as one so that one matmul gives every block's vector."""
+        """The parameters in the layouts the kernels read, gathered once per state of the parameters (_versions): per block
+        the stacked gated weights; all FiLM matrices as one so that one matmul gives every block's vector.  A changed
+        parameter drops the copies and the plans that hold their addresses."""
+        versions = self._versions()
+        if self._packed is not None and self._packed_versions != versions:
+            self._packed, self._plans = None, {}
         if self._packed is None:
+            self._packed_versions = versions
             blocks = [m for m in self.modules() if isinstance(m, ResnetBlock)]      # registration order: the order of _walk
             films = (torch.cat([b.film.output_layer.weight for b in blocks], 0).float().contiguous(),
                      torch.cat([b.film.output_layer.bias for b in blocks], 0).float().contiguous())
@@ -568,6 +613,7 @@ class UNet1D(nn.Module):
     def _plan_for(self, B, T, per_stream, dev):
         """The _Plan of one evaluation for (B, T) on dev, with one FiLM row per stream or one for all: built on first use."""
         key = (B, T, per_stream, dev)
+        self._pack()                              # drops the plans of parameters that have changed since
         if key not in self._plans:
             plan = _Plan(self, *key)
             self._walk(plan, plan.x)
@@ -835,3 +881,102 @@ class DiffusionGenerator:
                                                     k.shape[-1], _lib.ptr(out), _lib.current_stream()), "ntm_unet_upsample")
             return out.squeeze(1)
         return apply_resample_kernel(x, k, o, n, w)
+
+
+# ---- training ----------------------------------------------------------------------------------------------------------------------------
+
+class EDMTrainer:
+    """The EDM training step of the reference (code/train-diffusion.py: the diffusion parameters of class EDM, :44-221, and
+    Trainer.train_step / update_ema, :377-430) on a UNet1D of this module.
+    backend "hip": the network runs UNet1D.forward_train (HIP device only); "torch": forward_torch, any device and dtype.
+    draws = (a, noise) stands in for the step's torch.rand(B) and torch.randn(B, T), so that a recorded run can be replayed.
+    The reference's prints, its dataset, hydra and logging code and a command-line driver are not here: the caller hands
+    train_step its batch (B, T) and counts with `iteration`."""
+
+    def __init__(self, args, network, optimizer, device, backend="hip", scheduler=None):
+        if backend not in ("hip", "torch"):
+            raise ValueError(f"EDMTrainer: backend {backend!r}; built: 'hip' and 'torch'")
+        self.args, self.network, self.optimizer, self.device, self.backend = args, network, optimizer, device, backend
+        self.scheduler = scheduler
+        dp = args.diff_params
+        self.sigma_min, self.sigma_max, self.ro, self.sigma_data = dp.sigma_min, dp.sigma_max, dp.ro, dp.sigma_data
+        network._packed, network._plans = None, {}        # caches of bound launches: not state, and not copyable
+        self.ema = copy.deepcopy(network).eval().requires_grad_(False)
+        self.it = 0
+
+    # -- the diffusion parameters --
+    def sample_ptrain_safe(self, N, a=None):
+        if a is None:
+            a = torch.rand(N)
+        return (self.sigma_max ** (1 / self.ro) + a * (self.sigma_min ** (1 / self.ro) - self.sigma_max ** (1 / self.ro))) ** self.ro
+
+    def cskip(self, sigma):
+        return self.sigma_data ** 2 * (sigma ** 2 + self.sigma_data ** 2) ** -1
+
+    def cout(self, sigma):
+        return sigma * self.sigma_data * (self.sigma_data ** 2 + sigma ** 2) ** (-0.5)
+
+    def cin(self, sigma):
+        return (self.sigma_data ** 2 + sigma ** 2) ** (-0.5)
+
+    def cnoise(self, sigma):
+        return (1 / 4) * torch.log(sigma)
+
+    def prepare_train_preconditioning(self, x, sigma, noise=None):
+        noise = (torch.randn(x.shape) if noise is None else noise).to(sigma.device) * sigma
+        cskip, cout, cin, cnoise = self.cskip(sigma), self.cout(sigma), self.cin(sigma), self.cnoise(sigma)
+        target = (1 / cout) * (x - cskip * (x + noise))
+        return cin * (x + noise), target, cnoise
+
+    def _net(self, inputs, cnoise):
+        if self.backend == "hip":
+            return self.network.forward_train(inputs, cnoise)
+        return self.network.forward_torch(inputs, cnoise)
+
+    def loss_fn(self, x, draws=None):
+        """-> (error ** 2 (B, T), sigma (B, 1))."""
+        a, noise = (None, None) if draws is None else draws
+        sigma = self.sample_ptrain_safe(x.shape[0], a).unsqueeze(-1).to(x.device)
+        inputs, target, cnoise = self.prepare_train_preconditioning(x, sigma, noise)
+        error = self._net(inputs, cnoise) - target
+        return error ** 2, sigma
+
+    # -- the loop's steps --
+    def train_step(self, x, draws=None):
+        """One optimiser step on the batch x (B, T) -> the loss (detached).  self.lr and self.grad_norm: what the step used."""
+        train = self.args.train
+        self.optimizer.zero_grad()
+        error, _ = self.loss_fn(x, draws)
+        loss = error.mean()
+        loss.backward()
+        if self.it <= train.lr_rampup_it:
+            for g in self.optimizer.param_groups:
+                g["lr"] = train.lr * min(self.it / max(train.lr_rampup_it, 1e-8), 1)
+        self.lr = self.optimizer.param_groups[0]["lr"]
+        self.grad_norm = None
+        if train.use_grad_clip:
+            self.grad_norm = torch.nn.utils.clip_grad_norm_(self.network.parameters(), train.max_grad_norm)
+        self.optimizer.step()
+        if self.scheduler is not None:
+            self.scheduler.step()
+        return loss.detach()
+
+    def update_ema(self):
+        train = self.args.train
+        t = self.it * train.batch
+        with torch.no_grad():
+            s = np.clip(t / train.ema_rampup, 0.0, train.ema_rate) if t < train.ema_rampup else train.ema_rate
+            for dst, src in zip(self.ema.parameters(), self.network.parameters()):
+                dst.copy_(dst * s + src * (1 - s))
+
+    def iteration(self, x, draws=None):
+        """What the reference's training_loop does per pass, without the checkpoint: train_step, update_ema, it += 1."""
+        loss = self.train_step(x, draws)
+        self.update_ema()
+        self.it += 1
+        return loss
+
+    def state_dict(self):
+        """The reference's checkpoint: DiffusionGenerator loads its "ema"."""
+        return {"it": self.it, "network": self.network.state_dict(), "optimizer": self.optimizer.state_dict(),
+                "ema": self.ema.state_dict(), "args": self.args}

@@ -28,6 +28,9 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
   * AdvHeadFn: the hinge / mean losses of the adversarial run on the K outputs of a critic (train_crit / train_gen of
     code/critics.py) as ONE graph node on the kernels of csrc/advhead_kernels.hip: forward = ntm_adv_head_forward, backward =
     ntm_adv_head_backward.
+  * ResBlockFn: one ResnetBlock of the diffusion generators' UNet1D (diffusion.py) in its whole form as ONE graph node on the
+    kernels of csrc/unet_train.hip: forward = ntm_unet_resblock_forward_save, backward = ntm_unet_resblock_backward +
+    ntm_unet_wgrad_reduce.  UNet1D.forward_train builds its graph from these and torch ops.
   * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
     replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
     launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
@@ -459,3 +462,70 @@ class AdvHeadFn(torch.autograd.Function):
                                                     _lib.ADV_HEAD_MODES[mode], ptr(g), _lib.ptr_array(grads), _lib.current_stream()),
                    "ntm_adv_head_backward")
         return (None, None, *[gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:])])
+
+
+class ResBlockFn(torch.autograd.Function):
+    """(src0, src1 | None, film, w_first, w_gated, w_res | None, init_w | None, off0) -> one ResnetBlock of the diffusion
+    generators' UNet1D as ONE graph node, in the whole form (at most 1024 frames): the operands of diffusion.resblock_forward,
+    film (1 | B, c0 + c1) per stream.  forward = ntm_unet_resblock_forward_save (the inference kernel's body, which also keeps
+    y_0 .. y_{n-1}); backward = ntm_unet_resblock_backward (one workgroup per stream: the sources' and FiLM's gradients and
+    per-(stream, wave) weight-gradient partials) + ntm_unet_wgrad_reduce (their sum in index order in fp64).  No atomics: equal
+    calls give equal bits.  With init_w, src0 is the waveform and takes no gradient.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, src0, src1, film, w_first, w_gated, w_res, init_w, off0):
+        from . import diffusion as D
+        D._require_hip("ResBlockFn", src0, src1, film, w_first, w_gated, w_res, init_w)
+        if init_w is not None and src0.requires_grad:
+            raise RuntimeError("ResBlockFn: with init_w the waveform takes no gradient")
+        src0, film, w_first, w_gated = (t.detach().contiguous() for t in (src0, film, w_first, w_gated))
+        src1, w_res, init_w = (None if t is None else t.detach().contiguous() for t in (src1, w_res, init_w))
+        B, T0 = src0.shape[0], src0.shape[2]
+        c0 = init_w.shape[0] if init_w is not None else src0.shape[1]
+        c1, T1 = (0, 0) if src1 is None else src1.shape[1:]
+        T = T1 if src1 is not None else T0 - int(off0)
+        spec = D.BlockSpec(c0, c1, w_first.shape[0], w_gated.shape[0], T, T0, int(off0), T1, 0, int(init_w is not None),
+                           D.FORMS["whole"])
+        L, ref = _lib.lib(), _lib.ctypes.byref(spec)
+        n_save = L.ntm_unet_resblock_save_floats(B, ref)
+        if n_save < 0:
+            raise _lib.NtmError(f"ntm_unet_resblock_save_floats refused: {L.ntm_last_error().decode()}")
+        if film.shape[0] not in (1, B) or film.shape[1] != c0 + c1:
+            raise RuntimeError(f"ResBlockFn: film {tuple(film.shape)} for {B} streams of {c0 + c1} channels")
+        ysave = torch.empty(max(n_save, 1), dtype=torch.float32, device=src0.device)
+        out = torch.empty(B, spec.c_out, T, dtype=torch.float32, device=src0.device)
+        fstride = 0 if film.shape[0] == 1 else film.stride(0)
+        _lib.check(L.ntm_unet_resblock_forward_save(ptr(src0), ptr(src1), ptr(init_w), ptr(film), fstride, ptr(w_first),
+                                                    ptr(w_gated), ptr(w_res), B, ref, ptr(ysave), ptr(out),
+                                                    _lib.current_stream()), "ntm_unet_resblock_forward_save")
+        ctx.save_for_backward(src0, src1, film, w_first, w_gated, w_res, init_w, ysave)
+        ctx.spec = spec
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        src0, src1, film, w_first, w_gated, w_res, init_w, ysave = ctx.saved_tensors
+        spec, need = ctx.spec, ctx.needs_input_grad
+        L, ref = _lib.lib(), _lib.ctypes.byref(spec)
+        B, cin, cout, n, dev = src0.shape[0], spec.c0 + spec.c1, spec.c_out, spec.n_layers, src0.device
+        gout = gout.detach().to(torch.float32).contiguous()
+        per, total = L.ntm_unet_resblock_wgrad_floats(ref), L.ntm_unet_resblock_partial_floats(B, ref)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)       # noqa: E731
+        g0 = torch.empty_like(src0) if need[0] and init_w is None else None
+        g1 = torch.empty_like(src1) if src1 is not None and need[1] else None
+        gfilm, part, ws, grads = new(B, cin), new(max(total, 1)), new(max(B * cout * spec.T, 1)), new(per)
+        fstride = 0 if film.shape[0] == 1 else film.stride(0)
+        _lib.check(L.ntm_unet_resblock_backward(ptr(src0), ptr(src1), ptr(init_w), ptr(film), fstride, ptr(w_first), ptr(w_gated),
+                                                ptr(w_res), B, ref, ptr(ysave), ptr(gout), ptr(ws), ptr(g0), ptr(g1), ptr(gfilm),
+                                                ptr(part), _lib.current_stream()), "ntm_unet_resblock_backward")
+        _lib.check(L.ntm_unet_wgrad_reduce(ptr(part), total // per, per, ptr(grads), _lib.current_stream()),
+                   "ntm_unet_wgrad_reduce")
+        n_g, n_1 = n * cout * cout * 5, cout * cin
+        d_gated = grads[:n_g].view(n, cout, cout, 5)
+        d_first = grads[n_g:n_g + n_1].view(cout, cin, 1)
+        d_res = None if w_res is None else grads[n_g + n_1:n_g + 2 * n_1].view(cout, cin, 1)
+        d_init = None if init_w is None else grads[n_g + 2 * n_1:].view(spec.c0, 1, 5)
+        if film.shape[0] == 1 and B != 1:
+            gfilm = gfilm.sum(0, keepdim=True)            # one FiLM vector for all streams: the rows add
+        return g0, g1, gfilm, d_first, d_gated, d_res, d_init, None
