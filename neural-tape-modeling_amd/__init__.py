@@ -3,7 +3,7 @@
 
 The directory name contains a hyphen, so import it through the root-level shim:  `import ntm_amd`.
 Layout:  csrc/ (HIP kernels + C ABI -> libntm.so), model.py (reference object protocol),
-utilities.py (name parsers), weights.py (exported checkpoints), harness.py (test-model.py loss loop),
+epoch.py (the reference's TBPTT epoch, validation and predict-segment loops, once for single models and Replicas), utilities.py (name parsers), weights.py (exported checkpoints), harness.py (test-model.py loss loop),
 distributed.py (stream sharding + the one RCCL all-reduce), critics.py (the adversarial run's critics: MultiSpecCrit on the
 spectrogram, DilatedConvDisc on the waveform), adversarial.py (the adversarial run's configurations and training loop),
 evaluation.py (its validation metric bundle), diffusion.py (the diffusion generators: UNet1D and the EDM sampler).
@@ -15,7 +15,7 @@ from .model import (RNN, DCPreESR, DiffDelRNN, ESRLoss, MRSTFTLoss, Replicas, Ti
 from .tape import Tape, TapeMagnetization  # noqa: F401
 from .tcn import TCN  # noqa: F401
 from .utilities import nextpow2, parse_hidden_size, parse_loss, parse_model  # noqa: F401
-from . import adversarial, critics, diffusion, distributed, evaluation, feeder, harness, weights  # noqa: F401
+from . import adversarial, critics, diffusion, distributed, epoch, evaluation, feeder, harness, weights  # noqa: F401
 from .diffusion import DiffusionGenerator, EDMTrainer, UNet1D, load_config  # noqa: F401
 
 __all__ = ["RNN", "DiffDelRNN", "Replicas", "TimeVaryingDelayLine", "TCN", "Tape", "TapeMagnetization", "ESRLoss", "DCPreESR", "MRSTFTLoss", "ValLossSupervised", "TimeFreqConverter", "stft_sums", "spec_sums", "mel_sums", "esr_dcpre_sums", "esr_sums", "esr_per_segment",

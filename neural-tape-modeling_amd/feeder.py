@@ -26,6 +26,7 @@ What is NOT kept (out of scope): half/double storage, un-preloade
 The dataset itself (Zenodo 8026272) is not available here, so this module is checked against synthetic
 files only (tests/test_feeder.py).
 """
+import contextlib
 import glob
 import os
 import re
@@ -506,9 +507,8 @@ class SegmentFeeder:
             return ev
 
         model._predict_start(B)
-        if is_dd:
-            deferred, model.diffdel.defer_check = model.diffdel.defer_check, True   # no host sync per chunk
-        try:     # the deferred-check mode of the delay line is restored whatever the chunk loop does
+        # no host sync per chunk: the assert of code/model.py:284 once for all chunks, behind the loop
+        with model.diffdel.deferred() if is_dd else contextlib.nullcontext():
             bounds = [(c0, min(L, c0 + chunk)) for c0 in range(0, L, chunk)]
             ev = send(*bounds[0])
             back = torch.cuda.Stream(device=device) if out_host is not None else None
@@ -531,11 +531,6 @@ class SegmentFeeder:
                 ev = nxt
             if back is not None:
                 cur.wait_stream(back)                               # a sync of the caller's stream covers the copies back
-        finally:
-            if is_dd:
-                model.diffdel.defer_check = deferred
-        if is_dd and not deferred:
-            model.diffdel.raise_if_violated()                  # the assert of code/model.py:284, once for all chunks
         for a in (x, t, dtr):
             if a is not None:
                 a.record_stream(side)

@@ -17,7 +17,10 @@ Deliberate differences from the reference (documented in DESIGN.md):
     GRU-HS[64] with input_size = output_size = 1 and no skip connection on the kernels of csrc/gru_train.hip (training.py);
     parameters are created with requires_grad=False and train_epoch turns it on.  forward() builds a graph only when grad
     mode is on AND a parameter requires grad; every other call is the inference path, unchanged.  DiffDelRNN.train_epoch
-    (code/model.py:426-511) trains DiffDelGRU-HS[64] the same way, with the delay line's adjoint on the device.
+    (code/model.py:426-511) trains DiffDelGRU-HS[64] the same way, with the delay line's adjoint on the device.  The loops
+    themselves -- warm-up, windows, pieces, the window counts -- are written once, in epoch.py (epoch.RNN_SCHEDULE,
+    epoch.DIFFDEL_SCHEDULE, epoch.train_epoch, epoch.validate): the train_epoch / validate methods of RNN, DiffDelRNN and
+    Replicas are their docstring and one call, a single model going in as a group of one (_Single) that calls its own forward.
   * warm_start() from a fresh state is a pure function of the parameters.  With `warm_cache = True` its result (hidden
     state; for the DiffDelGRU also the delay buffer) is computed by the kernel ONCE per (parameter storage + torch version
     counter, device, kernel variant, delay-line length) and kept, so a predict() is one launch instead of two -- same numbers
@@ -28,11 +31,15 @@ Deliberate differences from the reference (documented in DESIGN.md):
     (code/test-model.py:192-247: construct, load best.pth, .eval(), never touched again) and bench.py reports the step both
     ways; whoever enables it elsewhere and writes through `.data` calls `invalidate_warm_cache()` (tests/test_gpu_round4.py).
 """
+import contextlib
+
 import numpy as np
 import torch
 
-from . import _lib, training
+from . import _lib, epoch, training
 from ._lib import ptr
+
+START_LEN = 2**10          # warm_start(): samples of silence (code/model.py:58-65, :382-391)
 
 
 class _GRUParams(torch.nn.Module):
@@ -79,6 +86,62 @@ def _as_bt(x, what):
     return x.contiguous().view(x.shape[0], x.shape[2])
 
 
+def _bt_pair(who, x, del_traj, delays=True):
+    """(x, del_traj) (N,1,T) -> their [B,T] fp32 forms, of one shape; without `delays` (x [B,T], None)."""
+    xbt = _as_bt(x, who)
+    if not delays:
+        return xbt, None
+    if del_traj is None:
+        raise RuntimeError(f"{who}: DiffDelRNN replicas need a delay trajectory")
+    dbt = _as_bt(del_traj, who)
+    if dbt.shape != xbt.shape:
+        raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
+    return xbt, dbt
+
+
+def _initial_state(hidden, B, H, device, own=False):
+    """The initial hidden state [B,H] fp32 on `device` for B streams from the carried `hidden` (1,B,H): zeros when none is
+    carried, else a VIEW of it that stays in its graph (the training paths chain dh0 to the previous window through it);
+    `own`: a detached tensor of its own, which the inference kernels update in place."""
+    if hidden is None:
+        return torch.zeros(B, H, device=device, dtype=torch.float32)
+    if tuple(hidden.shape) != (1, B, H):
+        raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(hidden.shape)}")
+    if own:
+        hidden = hidden.detach()
+    h0 = hidden.to(device=device, dtype=torch.float32).reshape(B, H)
+    return h0.clone() if own else h0
+
+
+def _train_forward(who, owner, x, del_traj, warmup, params, R, dl):
+    """The stateful forward of RNN, DiffDelRNN (R None, `params` the six parameters, b_o None for the bias-free head) and Replicas
+    (`params` the [R, ...] stacks) as graph nodes: training.GRUTrainStep from `owner.hidden`, which becomes the differentiable
+    final state, then with a delay line `dl` training.DelayLineStep.  -> (y, pre_d) (N,1,T); (y, None) without a delay line.
+    The new delay buffer is a fresh tensor (the warm-up's outputs in it stay in the graph of the first window); a delay above
+    the buffer raises AssertionError (code/model.py:284) with the buffer as it was -- the hidden state has moved on by then, as in
+    the reference, where the GRU runs before the delay line asserts."""
+    if x.requires_grad or (del_traj is not None and del_traj.requires_grad):
+        what, state, only = (("input", "the parameters and the hidden state", training.SUPPORTED) if dl is None else
+                             ("input or the delay trajectory", "the parameters, the hidden state and the delay buffer",
+                              training.SUPPORTED_DIFFDEL))
+        raise RuntimeError(f"{who}: the {what} requires grad; the training kernels give gradients for {state} only ({only})")
+    xbt, dbt = _bt_pair(who, x, del_traj, dl is not None)
+    B, T = xbt.shape
+    if R is not None and B % R:
+        raise ValueError(f"{who}: {B} streams do not divide into {R} replicas")
+    h0 = _initial_state(owner.hidden, B, training.HIDDEN, xbt.device)
+    if dl is not None:
+        dl._prepare(B, xbt.device)
+    pre, h = training.GRUTrainStep.apply(xbt, h0, *params, R)
+    owner.hidden = h.view(1, B, training.HIDDEN)
+    if dl is None:
+        return pre.view(B, 1, T), None
+    y, buf = training.DelayLineStep.apply(pre, dl.buffer, dbt, bool(warmup), dl._err)
+    dl._launched()               # raises BEFORE the buffer moves on: a violating call leaves it as it was
+    dl.buffer = buf
+    return y.view(B, 1, T), pre.view(B, 1, T)
+
+
 class _GRUHead(torch.nn.Module):
     """GRU(1,H) + Linear(H,1[,bias]) state and launch logic shared by RNN and DiffDelRNN."""
 
@@ -119,20 +182,14 @@ class _GRUHead(torch.nn.Module):
         self.hidden = None
         self._warm = None          # (key, state tensors) of the last warm_start() from a fresh state
 
-    def _h0(self, B, device):
-        """The initial hidden state (B,H) fp32 on `device`: zeros when none is carried, else a VIEW of self.hidden that stays in
-        its graph (the training paths chain dh0 to the previous window through it)."""
-        H = self.hidden_size
-        if self.hidden is None:
-            return torch.zeros(B, H, device=device, dtype=torch.float32)
-        if tuple(self.hidden.shape) != (1, B, H):
-            raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
-        return self.hidden.to(device=device, dtype=torch.float32).reshape(B, H)
-
     def _hidden_for(self, B, device):
-        """_h0 as the (1,B,H) tensor of its own that the inference kernels update in place."""
-        h = self._h0(B, device)
-        return (h if self.hidden is None else h.clone()).view(1, B, self.hidden_size)
+        """The carried state as the (1,B,H) tensor of its own that the inference kernels update in place."""
+        return _initial_state(self.hidden, B, self.hidden_size, device, own=True).view(1, B, self.hidden_size)
+
+    def _train_params(self):
+        """The six parameters in GRUTrainStep's order (the bias-free head: b_o None)."""
+        g, o = self.GRU, self.output
+        return g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, o.weight, o.bias
 
     def _one_launch(self):
         """Whether a loss entry forms its sums in the GRU's own C call (where the matrix-pipe kernel runs they ride in the
@@ -181,35 +238,35 @@ class _GRUHead(torch.nn.Module):
             y2d += x2d
 
 
-# ---- what every train_epoch / validate does to a batch before its loop (the single models and Replicas alike)
-def _audio_channel(input, target, device):
-    """(input, target) (B,C,T) -> channel 0 of both on `device`: only the audio channel counts for training and for the loss."""
-    if input.shape[1] > 1:
-        input, target = input[:, :1, :], target[:, :1, :]
-    return input.to(device), target.to(device)
+class _Single:
+    """A single RNN / DiffDelRNN as the group of one that epoch.train_epoch / validate walk: the model's OWN forward (the R = None
+    nodes and entry points in training; `kernel_variant`, `skip`, any hidden size and the hand-over to the matrix-pipe kernel in
+    validation), its own state, and `loss_fcn(pred, target)` itself."""
 
+    def __init__(self, model):
+        self.models, self.name, self.schedule = [model], type(model).__name__, model.schedule
+        self.device = model.GRU.weight_hh_l0.device
+        self.detach_hidden, self.zero_grad = model.detach_hidden, model.zero_grad
 
-def _delay_samples(extra, fs, who):
-    """The delay trajectory (B,1,T) in samples -- the fp32 product d_seconds * fs, as the reference forms it -- from the third item
-    of a batch: the reference's meta dict with 'delay_trajectory' (B,T) in seconds, or SegmentFeeder.batches' d_seconds (B,C,T)."""
-    if isinstance(extra, dict):
-        d_traj = extra["delay_trajectory"].float()
-        return d_traj.unsqueeze(1) * fs
-    if extra is not None:
-        return extra[:, :1, :].float() * fs
-    raise RuntimeError(f"{who}: the batch carries no delay trajectory")
+    def reset(self, Bper):
+        m = self.models[0]
+        if self.schedule.delays:
+            m.initialize_hidden(Bper, m.max_delay)
+        else:
+            m.initialize_hidden()
 
+    def stepper(self, train):
+        m = self.models[0]          # its forward() takes the training or the inference form by grad mode and requires_grad
+        return m.forward if self.schedule.delays else lambda x, d_traj, warmup: (m.forward(x), None)
 
-def _diffdel_warmup(dataset):
-    """Warm-up length of a DiffDel dataset in samples: nextpow2(int(max_delay * fs)), max_delay in seconds from
-    `delay_analyzer.max_delay` (the reference's dataset) or `max_delay` (SegmentFeeder)."""
-    from .utilities import nextpow2
-    max_delay = dataset.delay_analyzer.max_delay if hasattr(dataset, "delay_analyzer") else dataset.max_delay
-    return nextpow2(int(max_delay * dataset.fs))
+    def grouped_loss(self, loss_fcn):
+        return None
 
 
 class RNN(_GRUHead):
     """GRU + fully connected output layer (reference: code/model.py:20-246)."""
+
+    schedule = epoch.RNN_SCHEDULE
 
     def __init__(self, input_size=1, hidden_size=8, output_size=1, skip=False):
         super().__init__()
@@ -254,8 +311,7 @@ class RNN(_GRUHead):
     def warm_start(self):
         """Process 1024 samples of silence, B=1 (code/model.py:58-65).  From a fresh state (hidden None) the result
         depends on the parameters only and is kept per parameter version (module docstring)."""
-        START_LEN = 2**10
-        if self.input_size != 1:            # the reference feeds zeros((1, 1, 1024)) whatever input_size is: torch.nn.GRU raises
+        if self.input_size != 1:           # the reference feeds zeros((1, 1, 1024)) whatever input_size is: torch.nn.GRU raises
             raise RuntimeError(f"input.size(-1) must be equal to input_size. Expected {self.input_size}, got 1")
         fresh = self.hidden is None and self.warm_cache
         if fresh:
@@ -293,15 +349,7 @@ class RNN(_GRUHead):
 
     def _forward_train(self, x):
         self._check_trainable("RNN.forward")
-        if x.requires_grad:
-            raise RuntimeError("RNN.forward: the input requires grad; the training kernels give gradients for the parameters "
-                               "and the hidden state only (no caller of the reference needs d/dx)")
-        xbt = _as_bt(x, "RNN.forward")
-        B, T = xbt.shape
-        g, o = self.GRU, self.output
-        y, h = training.GRUTrainStep.apply(xbt, self._h0(B, xbt.device), g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, o.weight, o.bias)
-        self.hidden = h.view(1, B, self.hidden_size)
-        return y.view(B, 1, T)
+        return _train_forward("RNN.forward", self, x, None, False, self._train_params(), None, None)[0]
 
     def _forward_infer(self, x):
         if self._general_io:
@@ -368,15 +416,8 @@ class RNN(_GRUHead):
     @torch.no_grad()
     def predict(self, input, segment_length=None):
         """initialize_hidden + warm_start + forward over the sequence (code/model.py:218-246)."""
-        T = input.shape[-1]
         self._predict_start(input.shape[0])
-        if segment_length is None:
-            return self.forward(input)
-        output = torch.empty(input.shape, device=input.device, dtype=torch.float32)
-        for i in range(int(np.ceil(T / segment_length))):
-            sl = slice(i * segment_length, (i + 1) * segment_length)
-            output[:, :, sl] = self.forward(input[:, :, sl])
-        return output
+        return epoch.in_segments(lambda sl: (self.forward(input[:, :, sl]),), input, segment_length)[0]
 
     def train_epoch(self, dataloader, loss_fcn, optimizer):
         """One epoch of truncated back-propagation through time (code/model.py:90-161, run by code/train.py): per batch the
@@ -389,70 +430,17 @@ class RNN(_GRUHead):
         any function of (pred, target) that is differentiable through torch); `optimizer`: any torch.optim optimizer over
         model.parameters().
         Supported: RNN(1, 64, 1, skip=False) on a HIP device (RuntimeError otherwise).  On entry it sets requires_grad on the
-        GRU and head parameters (they are created without it, so that inference never records a graph)."""
-        TBPTT_INIT = 2**10
-        TBPTT_LEN = 2**10
-        self._check_trainable("RNN.train_epoch")
-        for p in self.parameters():
-            p.requires_grad_(True)
-        device = self.GRU.weight_hh_l0.device
-        self.train()
+        GRU and head parameters (they are created without it, so that inference never records a graph).  The loop is
+        epoch.train_epoch, the lengths epoch.RNN_SCHEDULE."""
+        return epoch.train_epoch(_Single(self), [dataloader], loss_fcn, optimizer)[0]
 
-        num_batches = 0             # counted, so that a generator (SegmentFeeder.batches) serves as well as a DataLoader
-        epoch_loss = 0
-        for _, batch in enumerate(dataloader):
-            input, target = _audio_channel(batch[0], batch[1], device)
-
-            self.initialize_hidden()
-            num_minibatches = (input.shape[2] - TBPTT_INIT) // TBPTT_LEN
-            _ = self.forward(input[:, :, :TBPTT_INIT])          # a graph node: window 1's backward reaches it
-            self.zero_grad()
-
-            minibatch_loss = 0
-            sample_offset = TBPTT_INIT
-            for _ in range(num_minibatches):
-                input_mini = input[:, :, sample_offset:sample_offset + TBPTT_LEN]
-                target_mini = target[:, :, sample_offset:sample_offset + TBPTT_LEN]
-                pred_mini = self.forward(input_mini)
-                loss = loss_fcn(pred_mini, target_mini)
-                loss.backward()
-                optimizer.step()
-                self.detach_hidden()
-                self.zero_grad()
-                minibatch_loss += loss.item()
-                sample_offset += TBPTT_LEN
-            minibatch_loss /= num_minibatches      # ZeroDivisionError for T < 2048, as in the reference
-            epoch_loss += minibatch_loss
-            num_batches += 1
-        epoch_loss /= num_batches
-        return epoch_loss
-
-    @torch.no_grad()
     def validate(self, dataloader, loss_fcn, store_examples=True):
         """Loss over a validation set (code/model.py:163-216; called by code/train.py:242): per batch the hidden state
         is aggregated on the first 1024 REAL samples, the rest is predicted in one launch and scored with
         `loss_fcn(pred, target)`; returns (mean loss over batches, examples).  `dataloader`: anything with len() that
-        yields (input, target, meta) batches of shape (B, C, T); only channel 0 is used, as in the reference."""
-        INIT_LEN = 2**10
-        device = self.GRU.weight_hh_l0.device
-        self.eval()
-        num_batches = len(dataloader)
-        val_loss = 0
-        examples = []
-        for _, batch in enumerate(dataloader):
-            input, target, _ = batch
-            input, target = _audio_channel(input, target, device)
-            self.initialize_hidden()
-            _ = self.forward(input[:, :, :INIT_LEN])
-            input = input[:, :, INIT_LEN:]
-            target = target[:, :, INIT_LEN:]
-            pred = self.forward(input)
-            loss = loss_fcn(pred, target)
-            val_loss += loss.item() if hasattr(loss, "item") else float(loss)
-            if store_examples:
-                examples.append({"input": input[0, 0, :], "target": target[0, 0, :], "prediction": pred[0, 0, :]})
-        val_loss /= num_batches
-        return val_loss, examples
+        yields (input, target, meta) batches of shape (B, C, T); only channel 0 is used, as in the reference.  The loop is
+        epoch.validate, the lengths epoch.RNN_SCHEDULE."""
+        return epoch.validate(_Single(self), [dataloader], loss_fcn, store_examples)[0]
 
 
 class TimeVaryingDelayLine(torch.nn.Module):
@@ -524,6 +512,18 @@ class TimeVaryingDelayLine(torch.nn.Module):
         else:
             self._unchecked = True
 
+    @contextlib.contextmanager
+    def deferred(self):
+        """Inside: no launch looks at the violation flag (no host synchronisation per chunk).  On a clean exit the assert of
+        code/model.py:284 is evaluated ONCE for all of them, unless the caller had deferred it already."""
+        before, self.defer_check = self.defer_check, True
+        try:
+            yield
+        finally:
+            self.defer_check = before
+        if not before:
+            self.raise_if_violated()
+
     def _run(self, xbt, dbt, warmup):
         """[B,T] fp32 -> y [B,T]; the carried buffer is updated IN PLACE (no clone, no scratch, no host sync)."""
         B, T = xbt.shape
@@ -560,6 +560,8 @@ class TimeVaryingDelayLine(torch.nn.Module):
 class DiffDelRNN(_GRUHead):
     """RNN (bias-free head) + differentiable delay line (reference: code/model.py:335-653)."""
 
+    schedule = epoch.DIFFDEL_SCHEDULE
+
     def __init__(self, input_size=1, hidden_size=8, output_size=1, skip=False, max_delay=10000):
         super().__init__()
         self._init_net(input_size, hidden_size, output_size, skip, head_bias=False)
@@ -576,8 +578,7 @@ class DiffDelRNN(_GRUHead):
         """1024 samples of silence with zero delay, B=1 (code/model.py:382-391).  From a fresh state (hidden None,
         zero buffer of batch 1) the result -- hidden state and delay buffer -- depends on the parameters and the
         delay-line length only and is kept per parameter version (module docstring)."""
-        START_LEN = 2**10
-        dev = self.GRU.weight_hh_l0.device
+        dev =self.GRU.weight_hh_l0.device
         dl = self.diffdel
         fresh = (self.warm_cache and self.hidden is None and dl._fresh and dl.buffer.shape[0] == 1
                  and dl.buffer.device == dev)
@@ -631,41 +632,15 @@ class DiffDelRNN(_GRUHead):
             raise RuntimeError(f"{what}: DiffDelRNN training is not implemented for parameters on '{dev}': it runs on a HIP "
                                f"device only ({training.SUPPORTED_DIFFDEL})")
 
-    @staticmethod
-    def _bt_pair(x, del_traj):
-        """(x, del_traj) (N,1,T) -> their [B,T] fp32 forms, of one shape."""
-        xbt = _as_bt(x, "DiffDelRNN.forward")
-        dbt = _as_bt(del_traj, "DiffDelRNN.forward")
-        if dbt.shape != xbt.shape:
-            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
-        return xbt, dbt
-
     def _forward_train(self, x, del_traj, warmup):
-        """forward() as graph nodes.  The new delay buffer is a fresh tensor (the warm-up's outputs in it stay in the graph of
-        the first window); a delay above the buffer raises AssertionError (code/model.py:284) with the buffer as it was -- the
-        hidden state has moved on by then, as in the reference, where the GRU runs before the delay line asserts."""
         self._check_trainable("DiffDelRNN.forward")
-        if x.requires_grad or del_traj.requires_grad:
-            raise RuntimeError("DiffDelRNN.forward: the input or the delay trajectory requires grad; the training kernels give "
-                               f"gradients for the parameters, the hidden state and the delay buffer only ({training.SUPPORTED_DIFFDEL})")
-        xbt, dbt = self._bt_pair(x, del_traj)
-        B, T = xbt.shape
-        dl = self.diffdel
-        dl._prepare(B, xbt.device)
-        g = self.GRU
-        pre, h = training.GRUTrainStep.apply(xbt, self._h0(B, xbt.device), g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0,
-                                             g.bias_hh_l0, self.output.weight, None)
-        self.hidden = h.view(1, B, self.hidden_size)
-        y, buf = training.DelayLineStep.apply(pre, dl.buffer, dbt, bool(warmup), dl._err)
-        dl._launched()               # raises BEFORE the buffer moves on: a violating call leaves it as it was
-        dl.buffer = buf
-        return y.view(B, 1, T), pre.view(B, 1, T)
+        return _train_forward("DiffDelRNN.forward", self, x, del_traj, warmup, self._train_params(), None, self.diffdel)
 
     def _forward_infer(self, x, del_traj, warmup=False, _events=None):
         """(x, del_traj) (N,1,T) -> (y, pre_d) (code/model.py:393-424).  `_events`: three torch.cuda.Event objects
         recorded before the GRU launch, between it and the delay pass, and after (bench.py's per-kernel timing; with the
         fused step the middle one is recorded right behind the fused launch, ahead of the buffer update)."""
-        xbt, dbt = self._bt_pair(x, del_traj)
+        xbt, dbt = _bt_pair("DiffDelRNN.forward", x, del_traj)
         B, T = xbt.shape
         if self._one_launch(losses=False):
             y, pre = self._fused_step(xbt, dbt, warmup, _events)
@@ -747,13 +722,8 @@ class DiffDelRNN(_GRUHead):
         """_predict_start, then fn() with the delay-range assert of code/model.py:284 evaluated ONCE, after the last launch
         has been enqueued (no host synchronisation per chunk)."""
         self._predict_start(input.shape[0])
-        deferred, self.diffdel.defer_check = self.diffdel.defer_check, True
-        try:
+        with self.diffdel.deferred():
             out = fn()
-        finally:
-            self.diffdel.defer_check = deferred
-        if not deferred:
-            self.diffdel.raise_if_violated()
         return out
 
     @torch.no_grad()
@@ -804,16 +774,9 @@ class DiffDelRNN(_GRUHead):
         """initialize_hidden + warm_start + forward (code/model.py:618-653); any batch size.  The delay-range assert
         of code/model.py:284 is evaluated ONCE, after the last chunk has been enqueued (no host synchronisation
         per chunk)."""
-        def run():
-            if segment_length is None:
-                return self.forward(input, d_traj, _events=_events)
-            output = torch.empty(input.shape, device=input.device, dtype=torch.float32)
-            output_pre_d = torch.empty(input.shape, device=input.device, dtype=torch.float32)
-            for i in range(int(np.ceil(input.shape[-1] / segment_length))):
-                sl = slice(i * segment_length, (i + 1) * segment_length)
-                output[:, :, sl], output_pre_d[:, :, sl] = self.forward(input[:, :, sl], d_traj[:, :, sl])
-            return output, output_pre_d
-        return self._predict_with(run, input)
+        events = _events if segment_length is None else None
+        return self._predict_with(lambda: epoch.in_segments(
+            lambda sl: self.forward(input[:, :, sl], d_traj[:, :, sl], _events=events), input, segment_length, 2), input)
 
     def train_epoch(self, dataloader, loss_fcn, optimizer, dataset=None):
         """One epoch of truncated back-propagation through time (code/model.py:426-511, run by code/train.py --MODEL DiffDelGRU):
@@ -827,47 +790,9 @@ class DiffDelRNN(_GRUHead):
         meta['delay_trajectory'] (B, T) in seconds, or SegmentFeeder.batches' (x, t, d_seconds (B,1,T), metas).  The delays are
         the fp32 product d_seconds * fs, as the reference forms them.
         Supported: DiffDelRNN(1, 64, 1, skip=False) on a HIP device (RuntimeError otherwise).  On entry it sets requires_grad on
-        the GRU and head parameters."""
-        self._check_trainable("DiffDelRNN.train_epoch")
-        dataset = dataloader.dataset if dataset is None else dataset
-        fs = dataset.fs
-        TBPTT_INIT = _diffdel_warmup(dataset)
-        TBPTT_LEN = 2**11
-        for p in self.parameters():
-            p.requires_grad_(True)
-        device = self.GRU.weight_hh_l0.device
-        self.train()
+        the GRU and head parameters.  The loop is epoch.train_epoch, the lengths epoch.DIFFDEL_SCHEDULE."""
+        return epoch.train_epoch(_Single(self), [dataloader], loss_fcn, optimizer, dataset=dataset)[0]
 
-        num_batches = 0             # counted, so that a generator (SegmentFeeder.batches) serves as well as a DataLoader
-        epoch_loss = 0
-        for _, batch in enumerate(dataloader):
-            input, target = _audio_channel(batch[0], batch[1], device)
-            d_traj = _delay_samples(batch[2], fs, "DiffDelRNN.train_epoch").to(device)
-
-            num_minibatches = int(np.ceil((input.shape[-1] - TBPTT_INIT) // TBPTT_LEN))
-            self.initialize_hidden(input.shape[0], self.max_delay)
-            _, __ = self.forward(input[:, :, :TBPTT_INIT], d_traj[:, :, :TBPTT_INIT], warmup=True)     # graph nodes
-            self.zero_grad()
-
-            minibatch_loss = 0
-            sample_offset = TBPTT_INIT
-            for _ in range(num_minibatches):
-                sl = slice(sample_offset, sample_offset + TBPTT_LEN)
-                pred_mini, _ = self.forward(input[:, :, sl], d_traj[:, :, sl])
-                loss = loss_fcn(pred_mini, target[:, :, sl])
-                loss.backward()
-                optimizer.step()
-                self.detach_hidden()
-                self.zero_grad()
-                minibatch_loss += loss.item()
-                sample_offset += TBPTT_LEN
-            minibatch_loss /= num_minibatches      # ZeroDivisionError when no whole window follows the warm-up, as in the reference
-            epoch_loss += minibatch_loss
-            num_batches += 1
-        epoch_loss /= num_batches
-        return epoch_loss
-
-    @torch.no_grad()
     def validate(self, dataloader, loss_fcn, store_examples=True):
         """Loss over a validation set (code/model.py:513-616): INIT_LEN = nextpow2(int(analyser max_delay * fs)); per
         batch the state is aggregated on the first INIT_LEN real samples (`warmup=True`: the delay line only fills its
@@ -875,38 +800,9 @@ class DiffDelRNN(_GRUHead):
         loss -- the reference forwards those pieces one by one; here they come out of ONE launch (chunked == one-shot
         bit for bit, state carried either way) and only the loss loop runs per piece.  Needs of the dataloader what the
         reference needs: len(), (input, target, meta) batches with meta['delay_trajectory'] (B, T) in seconds,
-        `.dataset.delay_analyzer.max_delay` (seconds) and `.dataset.fs`."""
-        fs = dataloader.dataset.fs
-        INIT_LEN = _diffdel_warmup(dataloader.dataset)
-        TBPTT_LEN = 2**11
-        device = self.GRU.weight_hh_l0.device
-        self.eval()
-        num_batches = len(dataloader)
-        val_loss = 0
-        examples = []
-        for _, batch in enumerate(dataloader):
-            input, target, meta = batch
-            input, target = _audio_channel(input, target, device)
-            d_traj = _delay_samples(meta, fs, "DiffDelRNN.validate").to(device)
-            num_minibatches = int(np.ceil((input.shape[-1] - INIT_LEN) / TBPTT_LEN))
-            self.initialize_hidden(input.shape[0], self.max_delay)
-            _, __ = self.forward(input[:, :, :INIT_LEN], d_traj[:, :, :INIT_LEN], warmup=True)
-            pred = torch.empty(target.shape, device=device, dtype=torch.float32)
-            pre_d = torch.empty(target.shape, device=device, dtype=torch.float32)
-            if num_minibatches > 0:
-                pred[:, :, INIT_LEN:], pre_d[:, :, INIT_LEN:] = self.forward(input[:, :, INIT_LEN:], d_traj[:, :, INIT_LEN:])
-            minibatch_loss = 0
-            for k in range(num_minibatches):
-                sl = slice(INIT_LEN + k * TBPTT_LEN, INIT_LEN + (k + 1) * TBPTT_LEN)
-                loss = loss_fcn(pred[:, :, sl], target[:, :, sl])
-                minibatch_loss += loss.item() if hasattr(loss, "item") else float(loss)
-            minibatch_loss /= num_minibatches           # ZeroDivisionError for T <= INIT_LEN, as in the reference
-            val_loss += minibatch_loss
-            if store_examples:
-                examples.append({"input": input[0, 0, INIT_LEN:], "target": target[0, 0, INIT_LEN:],
-                                 "prediction": pred[0, 0, INIT_LEN:], "prediction_pre_d": pre_d[0, 0, INIT_LEN:]})
-        val_loss /= num_batches
-        return val_loss, examples
+        `.dataset.delay_analyzer.max_delay` (seconds) and `.dataset.fs`.  The loop is epoch.validate, the lengths
+        epoch.DIFFDEL_SCHEDULE."""
+        return epoch.validate(_Single(self), [dataloader], loss_fcn, store_examples)[0]
 
 
 class Replicas:
@@ -943,7 +839,8 @@ class Replicas:
         if len(devs) != 1:
             raise ValueError(f"Replicas: all models must be on one device, got {sorted(map(str, devs))}")
         self.models = models
-        self.diffdel = kinds == {DiffDelRNN}
+        self.name, self.schedule = "Replicas", models[0].schedule      # a group for epoch.train_epoch / validate as it stands
+        self.diffdel = self.schedule.delays
         self.device = devs.pop()
         self.hidden = None                               # (1, R*Bper, 64) replica-major, in the graph between detach_hidden() calls
         self._dl = TimeVaryingDelayLine(max_delay=models[0].max_delay) if self.diffdel else None
@@ -953,10 +850,7 @@ class Replicas:
 
     def _stacks(self):
         """The six parameters as [R, ...] stacks, nodes of the graph (the bias-free head: b_o None)."""
-        ms = self.models
-        return (torch.stack([m.GRU.weight_ih_l0 for m in ms]), torch.stack([m.GRU.weight_hh_l0 for m in ms]),
-                torch.stack([m.GRU.bias_ih_l0 for m in ms]), torch.stack([m.GRU.bias_hh_l0 for m in ms]),
-                torch.stack([m.output.weight for m in ms]), None if self.diffdel else torch.stack([m.output.bias for m in ms]))
+        return tuple(None if ps[0] is None else torch.stack(ps) for ps in zip(*(m._train_params() for m in self.models)))
 
     def initialize_hidden(self, Bper=None):
         """Every replica's initialize_hidden: hidden <- None, for DiffDelRNN also a zero delay buffer of max_delay + 1 samples for
@@ -996,104 +890,43 @@ class Replicas:
         for m in self.models:
             m.zero_grad()
 
-    def _stage(self, who, x, xbt, del_traj, own=False):
-        """What forward() and infer() need beside x [B,T]: the group's state as h0 [B,64] (zeros from a fresh state; `own`: a
-        detached tensor of its own, which the inference kernel updates in place) and, for DiffDelRNN replicas, del_traj as
-        [B,T] of x's shape (else None)."""
-        B, H = xbt.shape[0], training.HIDDEN
-        if self.hidden is None:
-            h0 = torch.zeros(B, H, device=xbt.device, dtype=torch.float32)
-        elif tuple(self.hidden.shape) != (1, B, H):
-            raise RuntimeError(f"Expected hidden size (1, {B}, {H}), got {list(self.hidden.shape)}")
-        elif own:
-            h0 = self.hidden.detach().to(device=xbt.device, dtype=torch.float32).reshape(B, H).clone()
-        else:
-            h0 = self.hidden.to(device=xbt.device, dtype=torch.float32).reshape(B, H)
-        if not self.diffdel:
-            return h0, None
-        if del_traj is None:
-            raise RuntimeError(f"{who}: DiffDelRNN replicas need a delay trajectory")
-        dbt = _as_bt(del_traj, who)
-        if dbt.shape != xbt.shape:
-            raise RuntimeError(f"shape mismatch: x {tuple(x.shape)} vs del_traj {tuple(del_traj.shape)}")
-        return h0, dbt
-
     def forward(self, x, del_traj=None, warmup=False, _share=True):
         """One stateful training forward of all replicas: x (and del_traj, in samples) (R*Bper, 1, T) replica-major -> y for RNN,
         (y, pre_d) for DiffDelRNN, as the models' own forward() gives on their slices (same bits), as graph nodes.  A delay above
         the buffer in ANY replica raises AssertionError with every replica's delay buffer as it was."""
-        R = len(self.models)
-        xbt = _as_bt(x, "Replicas.forward")
-        B, T = xbt.shape
-        if B % R:
-            raise ValueError(f"Replicas.forward: {B} streams do not divide into {R} replicas")
-        if x.requires_grad or (del_traj is not None and del_traj.requires_grad):
-            raise RuntimeError("Replicas.forward: the input requires grad; the training kernels give gradients for the parameters, "
-                               "the hidden state and the delay buffer only")
-        h0, dbt = self._stage("Replicas.forward", x, xbt, del_traj)
-        if self.diffdel:
-            self._dl._prepare(B, xbt.device)
-        pre, h = training.GRUTrainStep.apply(xbt, h0, *self._stacks(), R)
-        self.hidden = h.view(1, B, training.HIDDEN)
-        if not self.diffdel:
-            if _share:
-                self._share()
-            return pre.view(B, 1, T)
-        dl = self._dl
-        y, buf = training.DelayLineStep.apply(pre, dl.buffer, dbt, bool(warmup), dl._err)
-        dl._launched()               # raises BEFORE any buffer moves on
-        dl.buffer = buf
+        out = _train_forward("Replicas.forward", self, x, del_traj, warmup, self._stacks(), len(self.models), self._dl)
         if _share:
             self._share()
-        return y.view(B, 1, T), pre.view(B, 1, T)
+        return out if self.diffdel else out[0]
 
     __call__ = forward
 
-    def _losses(self, loss_fcn, pred, target):
-        """[R] losses: ESRLoss / DCPreESR grouped (one launch per kernel); any other callable per replica slice."""
-        R = len(self.models)
-        if isinstance(loss_fcn, (ESRLoss, DCPreESR)):
-            return loss_fcn.replicas(pred, target, R)
-        n = pred.shape[0] // R
-        return torch.stack([loss_fcn(pred[r * n:(r + 1) * n], target[r * n:(r + 1) * n]).reshape(()) for r in range(R)])
+    # ---- the group as epoch.train_epoch / validate see it (beside models, name, device, schedule, detach_hidden, zero_grad)
+    reset = initialize_hidden
 
-    @staticmethod
-    def _is_batch(b):
-        return isinstance(b, (tuple, list)) and len(b) >= 2 and torch.is_tensor(b[0])
-
-    def _per_replica(self, arg, what, who="Replicas.train_epoch"):
-        """-> (list of R, shared): `arg` is a list / tuple of R loaders (none of whose items is itself a batch), or ONE loader
-        (which may itself be a list of batches) shared by all replicas."""
-        R = len(self.models)
-        if isinstance(arg, (list, tuple)) and arg and not any(self._is_batch(b) for b in arg):
-            if len(arg) != R:
-                raise ValueError(f"{who}: {len(arg)} {what} for {R} replicas")
-            return list(arg), False
-        return [arg] * R, True
-
-    def _gather(self, batches, prepare, who="Replicas.train_epoch", keep=False):
-        """The R batches of one iteration, each prepared as its model's train_epoch prepares it, stacked replica-major.  All R
-        must have one shape: ValueError naming both shapes otherwise, before anything is launched for the iteration.
-        `keep`: -> (stacked, the R prepared batches as they were before stacking)."""
-        for r, batch in enumerate(batches):
-            for a, b in zip(batches[0][:2], batch[:2]):
-                if a.shape != b.shape:
-                    raise ValueError(f"{who}: the batch of replica {r} has shape {tuple(b.shape)}, that of replica 0 "
-                                     f"{tuple(a.shape)}; all replicas need batches of one shape")
-        per = [prepare(r, b) for r, b in enumerate(batches)]
-        if all(b is batches[0] for b in batches):
-            R = len(batches)
-            stacked = [t.repeat(R, 1, 1) for t in per[0]]
+    def stepper(self, train):
+        """(x, d_traj or None, warmup) -> (pred, pre_d or None): forward() (the models' views of the state are refreshed by
+        detach_hidden() after every window), or infer() with the parameter stacks built once."""
+        if train:
+            run = lambda x, d_traj, warmup: self.forward(x, d_traj, warmup, _share=False)  # noqa: E731
         else:
-            stacked = [torch.cat(ts, dim=0) for ts in zip(*per)]
-        return (stacked, per) if keep else stacked
+            stacks = self._infer_stacks()
+            run = lambda x, d_traj, warmup: self.infer(x, d_traj, warmup, _stacks=stacks)  # noqa: E731
+        return run if self.diffdel else lambda x, d_traj, warmup: (run(x, d_traj, warmup), None)
+
+    def grouped_loss(self, loss_fcn):
+        """ESRLoss / DCPreESR: all R losses from one launch per kernel; any other callable: None (it is applied per replica)."""
+        if isinstance(loss_fcn, (ESRLoss, DCPreESR)):
+            return lambda pred, target: loss_fcn.replicas(pred, target, len(self.models))
+        return None
 
     def train_epoch(self, dataloaders, loss_fcn, optimizers, dataset=None, losses_hook=None):
         """One epoch of every replica's train_epoch (RNN: code/model.py:90-161, TBPTT_INIT = TBPTT_LEN = 1024; DiffDelRNN:
         code/model.py:426-511, the analyser's nextpow2 warm-up, windows of 2048, the fp32 d * fs product, the `//` window count)
         in lock step; -> the list of R epoch losses.  Per replica the loop is statement for statement that of its own
-        train_epoch: warm-up forward in the graph, zero_grad, then per window forward, loss, backward (of the sum of the R losses:
-        they share no node, so each model receives its own gradient), every optimizer's step(), detach_hidden, zero_grad.
+        train_epoch (it is the same loop, epoch.train_epoch): warm-up forward in the graph, zero_grad, then per window forward,
+        loss, backward (of the sum of the R losses: they share no node, so each model receives its own gradient), every
+        optimizer's step(), detach_hidden, zero_grad.
         `dataloaders`: a list / tuple of R loaders (zipped; the epoch ends with the shortest), or ONE loader whose batches every
         replica sees.  In every iteration the R batches must have the same shape (ValueError otherwise).
         `optimizers`: a list / tuple of optimizers (e.g. one per replica), or one optimizer over every replica's parameters;
@@ -1103,74 +936,7 @@ class Replicas:
         `dataset` (DiffDelRNN; one or a list of R; default each loader's .dataset): as DiffDelRNN.train_epoch's; all must give
         the same warm-up length, and the models the same max_delay.
         `losses_hook(list of R floats)` is called once per window with the window's losses, in replica order."""
-        R = len(self.models)
-        loaders, shared = self._per_replica(dataloaders, "loaders")
-        opts = list(optimizers) if isinstance(optimizers, (list, tuple)) else [optimizers]
-        for m in self.models:
-            m._check_trainable("Replicas.train_epoch")
-            for p in m.parameters():
-                p.requires_grad_(True)
-            m.train()
-        device = self.device
-        if self.diffdel:
-            datasets = ([ld.dataset for ld in loaders] if dataset is None else
-                        list(dataset) if isinstance(dataset, (list, tuple)) else [dataset] * R)
-            if len(datasets) != R:
-                raise ValueError(f"Replicas.train_epoch: {len(datasets)} datasets for {R} replicas")
-            fss = [ds.fs for ds in datasets]
-            inits = [_diffdel_warmup(ds) for ds in datasets]
-            if len(set(inits)) != 1:
-                raise ValueError(f"Replicas.train_epoch: the datasets give different warm-up lengths {inits}; one is needed")
-            TBPTT_INIT, TBPTT_LEN = inits[0], 2**11
-        else:
-            TBPTT_INIT, TBPTT_LEN = 2**10, 2**10
-
-        def prepare(r, batch):
-            pair = _audio_channel(batch[0], batch[1], device)
-            if not self.diffdel:
-                return pair
-            return pair + (_delay_samples(batch[2], fss[r], "Replicas.train_epoch").to(device),)
-
-        num_batches = 0
-        epoch_loss = [0] * R
-        for batches in (((b,) * R for b in loaders[0]) if shared else zip(*loaders)):
-            stacked = self._gather(batches, prepare)
-            input, target = stacked[0], stacked[1]
-            d_traj = stacked[2] if self.diffdel else None
-            sl = slice(0, TBPTT_INIT)
-            if self.diffdel:
-                num_minibatches = int(np.ceil((input.shape[-1] - TBPTT_INIT) // TBPTT_LEN))
-                self.initialize_hidden(input.shape[0] // R)
-                self.forward(input[:, :, sl], d_traj[:, :, sl], warmup=True, _share=False)          # graph nodes
-            else:
-                num_minibatches = (input.shape[2] - TBPTT_INIT) // TBPTT_LEN
-                self.initialize_hidden()
-                self.forward(input[:, :, sl], _share=False)
-            self.zero_grad()
-
-            minibatch_loss = [0] * R
-            sample_offset = TBPTT_INIT
-            for _ in range(num_minibatches):
-                sl = slice(sample_offset, sample_offset + TBPTT_LEN)
-                if self.diffdel:
-                    pred_mini, _ = self.forward(input[:, :, sl], d_traj[:, :, sl], _share=False)
-                else:
-                    pred_mini = self.forward(input[:, :, sl], _share=False)
-                losses = self._losses(loss_fcn, pred_mini, target[:, :, sl])
-                losses.sum().backward()
-                for opt in opts:
-                    opt.step()
-                self.detach_hidden()
-                self.zero_grad()
-                values = losses.tolist()                 # one host synchronisation for the R losses
-                if losses_hook is not None:
-                    losses_hook(values)
-                minibatch_loss = [a + v for a, v in zip(minibatch_loss, values)]
-                sample_offset += TBPTT_LEN
-            minibatch_loss = [a / num_minibatches for a in minibatch_loss]      # ZeroDivisionError as in the single models
-            epoch_loss = [a + b for a, b in zip(epoch_loss, minibatch_loss)]
-            num_batches += 1
-        return [a / num_batches for a in epoch_loss]
+        return epoch.train_epoch(self, dataloaders, loss_fcn, optimizers, dataset, losses_hook)
 
     # ---- inference of the group (DESIGN.md 11.3): one launch of the low-latency kernel for all R models
 
@@ -1202,11 +968,11 @@ class Replicas:
         flag for the group; the hidden state has moved on by then, as in the single model)."""
         R = len(self.models)
         H = training.HIDDEN
-        xbt = _as_bt(x, "Replicas.infer")
+        xbt, dbt = _bt_pair("Replicas.infer", x, del_traj, self.diffdel)
         B, T = xbt.shape
         Bper = self._streams_per_replica(B, R, "Replicas.infer")
         _require_hip(self.models[0].GRU.weight_hh_l0, "model parameters (call .to('cuda'))")
-        h, dbt = self._stage("Replicas.infer", x, xbt, del_traj, own=True)
+        h = _initial_state(self.hidden, B, H, xbt.device, own=True)
         w_ih, w_hh, b_ih, b_hh, w_o, b_o = self._infer_stacks() if _stacks is None else _stacks
         pre = torch.empty_like(xbt)
         rc = _lib.lib().ntm_gru_forward_replicas(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(w_o), ptr(b_o), ptr(xbt), ptr(pre),
@@ -1222,18 +988,6 @@ class Replicas:
             self._share()
         return y.view(B, 1, T), pre.view(B, 1, T)
 
-    @staticmethod
-    def _host_rows(rows):
-        """The losses of one batch, rows [pieces][R], as Python floats -- the values `.item()` gives the single model's validate,
-        brought over in ONE .tolist() of a [pieces, R] tensor wherever they are tensors of one kind on one device."""
-        if all(torch.is_tensor(r) for r in rows):
-            return torch.stack(rows).tolist() if rows else []
-        flat = [v for r in rows for v in r]
-        if flat and all(torch.is_tensor(v) and v.dtype == flat[0].dtype and v.device == flat[0].device for v in flat):
-            return torch.stack([v.reshape(()) for v in flat]).view(len(rows), -1).tolist()
-        return [[v.item() if hasattr(v, "item") else float(v) for v in r] for r in rows]
-
-    @torch.no_grad()
     def validate(self, dataloaders, loss_fcn, store_examples=True):
         """Every replica's validate() (RNN: code/model.py:163-216, INIT_LEN = 1024, one loss per batch; DiffDelRNN:
         code/model.py:513-616, INIT_LEN = the analyser's nextpow2 warm-up run with `warmup=True`, the loss on 2048-sample pieces,
@@ -1247,83 +1001,7 @@ class Replicas:
         them out (a fresh prediction tensor, the replica's own target), so that a torch reduction takes the same path.  The losses
         of a batch reach the host in one .tolist() and are added in Python in the order the single validate adds its .item()s.
         The examples of replica r are the first stream of its slice, with the single model's keys."""
-        who = "Replicas.validate"
-        R = len(self.models)
-        loaders, shared = self._per_replica(dataloaders, "loaders", who)
-        counts = [len(ld) for ld in loaders]
-        if len(set(counts)) != 1:
-            raise ValueError(f"{who}: the loaders have different lengths {counts}; every replica needs as many batches")
-        device = self.device
-        for m in self.models:
-            m.eval()
-        grouped = isinstance(loss_fcn, (ESRLoss, DCPreESR))
-        if self.diffdel:
-            fss = [ld.dataset.fs for ld in loaders]
-            inits = [_diffdel_warmup(ld.dataset) for ld in loaders]
-            if len(set(inits)) != 1:
-                raise ValueError(f"{who}: the datasets give different warm-up lengths {inits}; one is needed")
-            INIT_LEN, TBPTT_LEN = inits[0], 2**11
-        else:
-            INIT_LEN = 2**10
-
-        def prepare(r, batch):
-            input, target, meta = batch
-            pair = _audio_channel(input, target, device)
-            if not self.diffdel:
-                return pair
-            return pair + (_delay_samples(meta, fss[r], who).to(device),)
-
-        stacks = self._infer_stacks()           # once per call, not once per batch
-        val_loss = [0] * R
-        examples = [[] for _ in range(R)]
-        for batches in (((b,) * R for b in loaders[0]) if shared else zip(*loaders)):
-            stacked, per = self._gather(batches, prepare, who, keep=True)
-            input, target = stacked[0], stacked[1]
-            n = self._streams_per_replica(input.shape[0], R, who)
-            T = input.shape[-1]
-            if self.diffdel:
-                d_traj = stacked[2]
-                num_minibatches = int(np.ceil((T - INIT_LEN) / TBPTT_LEN))
-                self.initialize_hidden(n)
-                self.infer(input[:, :, :INIT_LEN], d_traj[:, :, :INIT_LEN], warmup=True, _stacks=stacks)
-                if num_minibatches > 0:
-                    pred, pre_d = self.infer(input[:, :, INIT_LEN:], d_traj[:, :, INIT_LEN:], _stacks=stacks)
-                else:
-                    pred = pre_d = torch.empty(input.shape[0], 1, max(T - INIT_LEN, 0), device=device, dtype=torch.float32)
-                pieces = [slice(k * TBPTT_LEN, (k + 1) * TBPTT_LEN) for k in range(num_minibatches)]
-            else:
-                self.initialize_hidden()
-                self.infer(input[:, :, :INIT_LEN], _stacks=stacks)
-                pred = self.infer(input[:, :, INIT_LEN:], _stacks=stacks)
-                num_minibatches, pieces = None, [slice(None)]
-            input, target = input[:, :, INIT_LEN:], target[:, :, INIT_LEN:]
-            if grouped:
-                rows = [loss_fcn.replicas(pred[:, :, sl], target[:, :, sl], R) for sl in pieces]
-            else:
-                rows = [[] for _ in pieces]
-                for r in range(R):
-                    own_t = per[r][1]
-                    if self.diffdel:        # the single model scores slices of a whole-length prediction buffer
-                        own_p = torch.empty(own_t.shape, device=device, dtype=torch.float32)
-                        own_p[:, :, INIT_LEN:] = pred[r * n:(r + 1) * n]
-                        own_p, own_t = own_p[:, :, INIT_LEN:], own_t[:, :, INIT_LEN:]
-                    else:
-                        own_p, own_t = pred[r * n:(r + 1) * n].clone(), own_t[:, :, INIT_LEN:]
-                    for k, sl in enumerate(pieces):
-                        rows[k].append(loss_fcn(own_p[:, :, sl], own_t[:, :, sl]))
-            batch_loss = [0] * R
-            for values in self._host_rows(rows):                        # in piece order, as the single loop adds them
-                batch_loss = [a + v for a, v in zip(batch_loss, values)]
-            if num_minibatches is not None:
-                batch_loss = [a / num_minibatches for a in batch_loss]  # ZeroDivisionError for T <= INIT_LEN, as in the single model
-            val_loss = [a + b for a, b in zip(val_loss, batch_loss)]
-            if store_examples:
-                for r in range(R):
-                    ex = {"input": input[r * n, 0, :], "target": target[r * n, 0, :], "prediction": pred[r * n, 0, :]}
-                    if self.diffdel:
-                        ex["prediction_pre_d"] = pre_d[r * n, 0, :]
-                    examples[r].append(ex)
-        return [(v / c, ex) for v, c, ex in zip(val_loss, counts, examples)]
+        return epoch.validate(self, dataloaders, loss_fcn, store_examples)
 
     @torch.no_grad()
     def predict(self, input, d_traj=None, segment_length=None):
@@ -1334,49 +1012,26 @@ class Replicas:
         (see infer()).  The warm start is recomputed on every call (the models' `warm_cache` is neither read nor written: what it
         would hold is what the launch computes, and a stale key cannot arise).  As in DiffDelRNN.predict the delay-range assert
         is evaluated once, after the last piece has been enqueued."""
-        START_LEN = 2**10
         R = len(self.models)
         if input.dim() != 3:
             raise RuntimeError(f"Replicas.predict: expected (N_BATCHES, N_CHANNELS, N_SAMPLES), got {tuple(input.shape)}")
-        B, T = input.shape[0], input.shape[-1]
-        Bper = self._streams_per_replica(B, R, "Replicas.predict")
+        Bper = self._streams_per_replica(input.shape[0], R, "Replicas.predict")
         if self.diffdel and d_traj is None:
             raise RuntimeError("Replicas.predict: DiffDelRNN replicas need a delay trajectory")
-        stacks = self._infer_stacks()
+        step = self.stepper(train=False)
+        n_out = 2 if self.diffdel else 1
         self.initialize_hidden(1)
         zeros = torch.zeros((R, 1, START_LEN), device=self.device)
-        if self.diffdel:
-            deferred, self._dl.defer_check = self._dl.defer_check, True
-        try:
-            if self.diffdel:
-                self.infer(zeros, zeros, _stacks=stacks)
-                self._dl.buffer = self._dl.buffer.repeat_interleave(Bper, dim=0) if Bper != 1 else self._dl.buffer
-            else:
-                self.infer(zeros, _stacks=stacks)
+        with self._dl.deferred() if self.diffdel else contextlib.nullcontext():
+            step(zeros, zeros, False)
             if Bper != 1:
                 self.hidden = self.hidden.repeat_interleave(Bper, dim=1)
-            self._share()
-
-            def run(sl):
                 if self.diffdel:
-                    return self.infer(input[:, :, sl], d_traj[:, :, sl], _stacks=stacks)
-                return (self.infer(input[:, :, sl], _stacks=stacks),)
-            if segment_length is None:
-                outs = run(slice(None))
-            else:
-                outs = tuple(torch.empty(input.shape, device=input.device, dtype=torch.float32) for _ in range(2 if self.diffdel else 1))
-                for i in range(int(np.ceil(T / segment_length))):
-                    sl = slice(i * segment_length, (i + 1) * segment_length)
-                    for o, v in zip(outs, run(sl)):
-                        o[:, :, sl] = v
-        finally:
-            if self.diffdel:
-                self._dl.defer_check = deferred
-        if self.diffdel:
-            if not deferred:
-                self._dl.raise_if_violated()
-            return outs
-        return outs[0]
+                    self._dl.buffer = self._dl.buffer.repeat_interleave(Bper, dim=0)
+            self._share()
+            outs = epoch.in_segments(lambda sl: step(input[:, :, sl], d_traj[:, :, sl] if self.diffdel else None, False)[:n_out],
+                                     input, segment_length, n_out)
+        return outs if self.diffdel else outs[0]
 
 
 # ------------------------------------------------------------------------------------------
