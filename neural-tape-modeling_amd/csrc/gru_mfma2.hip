@@ -16,8 +16,9 @@
 //     ds_write_b128 of those same registers.  (transpose_groups4 below is kept for the unit test of
 //     the permlane-swap idiom; the kernel no longer needs it.)
 //   * step t starts with 12 MFMAs (r,n,z x 4 own K-steps) straight out of registers; behind the third
-//     one sits the step's only barrier (all h_{t-1} writes are complete), then three ds_read_b128
-//     fetch the other three quarters while the remaining own MFMAs run; the other 36 MFMAs follow.
+//     one sits the step's only barrier (all h_{t-1} writes are complete), alone in its MFMA gap; three
+//     ds_read_b128, one behind each of the next three MFMAs, fetch the other three quarters while the
+//     remaining own MFMAs run (x of step t+1 behind the fourth); the other 36 MFMAs follow.
 //   * K-steps are numbered per wave (sigma = (s - 4w) mod 16) so that "own first" uses fixed registers.
 //   * the VALU block after the MFMAs: input terms of step t+1, the three gates on packed fp32 ops
 //     (v_pk_fma/add) and v_exp/v_rcp, the blend, the head partial of y_t over the lane's 4 units (the
@@ -744,17 +745,51 @@ __global__ __launch_bounds__(256, 1) void gru_mfma2_kernel(GruArgs a)
             asm volatile("s_barrier" : "+v"(acc_r), "+v"(acc_n), "+v"(acc_z)::"memory");
             NTM2_STAMP(2)   // barrier
         } else asm volatile("s_waitcnt lgkmcnt(1)\n\ts_barrier" : "+v"(acc_r), "+v"(acc_n), "+v"(acc_z)::"memory");
+        // x of step t+1 (its tile was staged at ph 34 of the previous tile at the latest)
+        auto x_next = [&]() __attribute__((always_inline)) { return xb[(((t + 1) >> 6) & 1) * SG * XS + j * XS + (int)((t + 1) & 63)]; };
+        float xn;
+        if constexpr (ENGINE == 0 && !(ABL & 2)) {
+            // ONE LDS operation per MFMA gap behind the barrier.  The wave issues in order and the matrix pipe accepts an MFMA
+            // every 32 cycles, so the wave reaches the wait at most one MFMA ahead of the pipe, and whatever else sits between
+            // two MFMAs is free only while it fits the ~24 issue cycles the MFMA in front leaves over.  The wait and the barrier
+            // (~30 cycles) therefore have their gap to themselves; the three 1 KiB reads of the other quarters (8 LDS cycles
+            // each) follow behind the next three MFMAs, one per gap, and the read of x behind the fourth -- the quarters are
+            // not consumed before K-step 4, eight MFMAs behind the first read at NB = 1, x only by the vector block.  The fences are empty: the
+            // accumulators tie each MFMA, the memory clobber each read, to its place between two of them.
+            auto gap = [&](const int g) __attribute__((always_inline)) {           // ties MFMA g behind the barrier (0-based), by its accumulator
+                const int c = g % 3;
+                if (c == 0) asm volatile("" : "+v"(acc_r)::"memory");
+                else if ((c == 1) == (NTM2_ORDER == 0)) asm volatile("" : "+v"(acc_n)::"memory");
+                else asm volatile("" : "+v"(acc_z)::"memory");
+            };
+            constexpr int LAST = (ABL & 8) ? 4 : 16;
+            auto gap_read = [&](const int g) __attribute__((always_inline)) {      // the read in the gap between MFMA g - 1 and MFMA g
+                gap(g - 1);
+                if (g < 4) {
+                    const f32x4 v = *(const f32x4 *)((g == 1 ? hrd1 : g == 2 ? hrd2 : hrd3) + cur * HB);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) hB[4 * g + i] = v[i];
+                } else xn = x_next();
+                gap(g);
+            };
+#pragma unroll
+            for (int sg = NB; sg < LAST; ++sg) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int g = 3 * (sg - NB) + c;      // MFMAs issued since the barrier
+                    if (g >= 1 && g <= 4) gap_read(g);
+                    if (c == 0) acc_r = mfma16x(Ar[sg], hB[sg], acc_r);
+                    else if ((c == 1) == (NTM2_ORDER == 0)) acc_n = mfma16x(An[sg], hB[sg], acc_n);
+                    else acc_z = mfma16x(Az[sg], hB[sg], acc_z);
+                }
+                if (sg == 3) asm volatile("" : "+v"(acc_r), "+v"(acc_n), "+v"(acc_z));
+            }
+#pragma unroll
+            for (int g = (3 * (LAST - NB) < 1 ? 1 : 3 * (LAST - NB)); g <= 4; ++g) gap_read(g);   // (fewer than five MFMAs behind the barrier)
+        }
         if constexpr (ABL & 2) {
 #pragma unroll
             for (int i = 4; i < 16; ++i) hB[i] = hT[i & 3];
-        } else if constexpr (ENGINE == 0) {
-            const f32x4 v1 = *(const f32x4 *)(hrd1 + cur * HB);
-            const f32x4 v2 = *(const f32x4 *)(hrd2 + cur * HB);
-            const f32x4 v3 = *(const f32x4 *)(hrd3 + cur * HB);
-            if constexpr (ENGINE == 0) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { hB[4 + i] = v1[i]; hB[8 + i] = v2[i]; hB[12 + i] = v3[i]; }
-            }
         }
         if constexpr (ENGINE == 1 && !(ABL & 2)) {
             B8h = *(const f16x8 *)(hrow + cur * HB + 2 * pa);
@@ -762,11 +797,10 @@ __global__ __launch_bounds__(256, 1) void gru_mfma2_kernel(GruArgs a)
             Bh[1] = *(const f16x4 *)(hrow + cur * HB + 2 * ps);
             Bl[1] = *(const f16x4 *)(hrow + cur * HB + 8 + 2 * ps);
         }
-        // x of step t+1 (its tile was staged at ph 34 of the previous tile at the latest)
-        float xn = xb[(((t + 1) >> 6) & 1) * SG * XS + j * XS + (int)((t + 1) & 63)];
+        if constexpr (ENGINE != 0 || (ABL & 2)) xn = x_next();      // (these keep the whole packet in the barrier's gap)
         if constexpr (ENGINE == 0) {
 #pragma unroll
-            for (int sg = NB; sg < ((ABL & 8) ? 4 : 16); ++sg) {
+            for (int sg = NB; sg < ((ABL & 2) ? ((ABL & 8) ? 4 : 16) : 0); ++sg) {      // (the no-exchange ablation)
                 acc_r = mfma16x(Ar[sg], hB[sg], acc_r);
 #if NTM2_ORDER
                 acc_z = mfma16x(Az[sg], hB[sg], acc_z);

@@ -24,12 +24,15 @@ DEFAULT_LIB = os.path.join(ROOT, "neural-tape-modeling_amd", "libntm.so")
 
 # gru_mfma2_kernel<PRESCALE, STAMP, ABL, ENGINE, YPN, FUSE, ESR[, DCPRE]> of libntm.so: VGPRs of the binary behind profiles/r05_*
 # (hipcc 7.2); keyed by (ENGINE, YPN, FUSE, ESR, DCPRE).  A count ABOVE the pin fails --check; below is reported.
+# Three YPN = 4 builds are pinned to the binary behind profiles/gap_* instead (one LDS operation per MFMA gap behind the step
+# barrier): 186 / 218 / 230 against 184 / 216 / 228 before -- two more registers for the temporaries of the tile flush, where
+# these builds have their peak; every YPN = 16 build, the headline among them, kept its count.
 PINNED_VGPRS = {
-    (0, 16, 0, 0, 0): 194, (0, 4, 0, 0, 0): 184,
+    (0, 16, 0, 0, 0): 194, (0, 4, 0, 0, 0): 186,
     (0, 16, 0, 1, 0): 254, (0, 4, 0, 1, 0): 206,
     (1, 16, 0, 0, 0): 194, (1, 4, 0, 0, 0): 190,
-    (0, 16, 1, 0, 0): 222, (0, 4, 1, 0, 0): 216,
-    (0, 16, 1, 1, 0): 234, (0, 4, 1, 1, 0): 228,
+    (0, 16, 1, 0, 0): 222, (0, 4, 1, 0, 0): 218,
+    (0, 16, 1, 1, 0): 234, (0, 4, 1, 1, 0): 230,
     (0, 16, 0, 1, 1): 264, (0, 4, 0, 1, 1): 220,          # ESR + DCP: 256 VGPRs + 8 AGPRs (AGPR spills, no scratch)
     (0, 16, 1, 1, 1): 251, (0, 4, 1, 1, 1): 243,          # FUSE + ESR + DCP
     (2, 16, 0, 0, 0): 250, (2, 4, 0, 0, 0): 250,          # bf16x3 engine (round 6; opt-in): <= 256, so that two groups share a CU from 8192 streams up
