@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from gru_train_cases import T_EDGES
 from helpers import load
 
 W_G = "GRU-HS[64]-L[DCPreESR]-DS[ReelToReel_Dataset_MiniPulse100_CHOWTAPE]_BEST"
@@ -36,9 +37,14 @@ def _random_sd(seed, scale):
     return {n: ((torch.rand(*s, generator=g) * 2 - 1) * k * scale).float() for n, s in shapes.items()}
 
 
+# the grid of batch sizes and lengths, and B = 1, 3 at every length of the edge list of tests/gru_train_cases.py (the tail of the
+# step pairs, the 32-step save stage, the x prefetch at step 128, the 256-sample tile and finish()'s two ways to the previous y tile)
+FORWARD_GRID = list(dict.fromkeys([(T, B) for T in (1, 5, 256, 1024, 1500) for B in (1, 7, 32, 300, 1100)] +
+                                  [(T, B) for B in (1, 3) for T in T_EDGES]))
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("B", [1, 7, 32, 300, 1100])
-@pytest.mark.parametrize("T", [1, 5, 256, 1024, 1500])
+@pytest.mark.parametrize("T,B", FORWARD_GRID)
 def test_training_forward_is_bit_identical_to_the_low_latency_kernel(ntm, B, T):
     sd = ntm.weights.load_state_dict(W_G)
     g = torch.Generator().manual_seed(B * 7919 + T)
@@ -77,6 +83,10 @@ CASES = [(1, 1, "ckpt", 1.0, True), (7, 5, "ckpt", 1.0, True), (32, 1024, "ckpt"
          (300, 1500, "ckpt", 1.0, True), (1100, 256, "ckpt", 1.0, True), (32, 256, "rand", 1.0, True), (32, 256, "rand", 10.0, True),
          (32, 256, "rand", 3.0, True), (7, 1500, "rand", 1.0, False),
          (32, 256, "rand", 0.1, True), (32, 256, "rand", 0.01, True)]
+# every tail length of the backward's groups of four steps, the start of its register ring (T < 4) and the forward's stage and
+# tile edges, through the path users call (the raw kernels are held exactly at these lengths by tests/test_gpu_gru_train_edges.py)
+CASES += [(3, T, "ckpt", 1.0, True) for T in T_EDGES] + [(2, T, "rand", 1.0, False) for T in (2, 3, 7, 33, 259)]
+assert len(set(CASES)) == len(CASES)
 # Random weights over three decades of scale, 0.01 to 10 times torch's init scale (beyond 10, the recurrence's gradients grow
 # without bound in float64 too).  Below init scale the bar has a third term: the forward's tanh form 1 - 2/(1 + e^(2v)) (the
 # low-latency kernel's, which the training forward reproduces bit for bit) has an ABSOLUTE error of ~1 ulp of 1 (6e-8), so with
