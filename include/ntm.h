@@ -840,6 +840,39 @@ int ntm_unet_resblock_backward(const float *src0, const float *src1, const float
                                float *partials, void *stream);
 int ntm_unet_wgrad_reduce(const float *partials, int64_t count, int64_t n, float *out, void *stream);
 
+/*
+ * The adjoints of ntm_unet_down_combine and ntm_unet_up_combine (csrc/unet_resample_train.hip).  Additions within ABI version 9.
+ * Sizes, layouts and limits are the forwards'; fp32 in and out, one launch each.  No atomics: every sum is a gather in a fixed
+ * order, so equal calls give equal bits and a stream's results do not depend on its batch.  An upstream gradient that is NULL is
+ * zero (not both), and an output that is NULL is not computed (not all).
+ *
+ * ntm_unet_down_combine_backward: from g_xo [B][C][Fo] and g_po [B][1][Fo], Fo = ceil(F / S), with w = width:
+ *     g_pd[b][j]   = g_po[b][j] + (sum_c wc[c] g_xo[b][c][j]) / sqrt 2
+ *     g_x[b][c][f] = (sum_j ker[f + w - j S] g_xo[b][c][j]) / sqrt 2       [B][C][F]; j ascending over the terms in range
+ *     g_pyr[b][f]  = sum_j ker[f + w - j S] g_pd[b][j]                      [B][1][F]
+ *     partials[b][c] = (sum_j g_xo[b][c][j] pyr_d[b][j]) / sqrt 2           [B][C]; pyr_d is the forward's pyr_out.  Added in fp64
+ *                    in a fixed order, rounded once; ntm_unet_wgrad_reduce(partials, B, C, g_wc) gives the combiner's gradient.
+ * ntm_unet_up_combine_backward: from g_xo [B][C][S F] (NULL with S == 1) and g_po [B][1][S F]; pyr_T == 0 says that the forward
+ *   had no pyramid, else it is the forward's pyr_T >= F:
+ *     g_p[b][f]    = sum_{ph, i} ker[ph][i] g_po[b][(f - i + w) S + ph]     (S == 1: g_po[b][f]); / sqrt 2 with a pyramid
+ *     g_x[b][c][f] = the same gather of g_xo[b][c] + wc[c] g_p[b][f]        [B][C][F]
+ *     g_pyr[b][f]  = g_p[b][f], 0 for F <= f < pyr_T                        [B][1][pyr_T]; only with a pyramid
+ *     partials[b][t][c] = sum_{f in tile t} g_p[b][f] x[b][c][f]            [B][P][C], P = ntm_unet_up_combine_backward_partials(F)
+ *                    = ceil(F / 256) tiles of 256 frames; fp64 in a fixed order, rounded once;
+ *                    ntm_unet_wgrad_reduce(partials, B P, C, g_wc) gives the combiner's gradient.
+ *   Refused (NTM_EINVAL, a message starting with the function's name, before anything touches a device): what the forwards refuse
+ *   of the sizes (B outside [0, 65535], C outside [1, 32], taps > 64 or not 2 width + S (down) / 2 width + 1 (up), S == 1 with a
+ *   filter, C frames >= 2^31), 0 < pyr_T < F, g_pyr with pyr_T == 0, both upstream gradients NULL, every output NULL, a NULL ker
+ *   or wc, partials without pyr_d (down) or x (up).  B == 0 returns NTM_OK.
+ */
+int ntm_unet_down_combine_backward(const float *pyr_d, const float *ker, const float *wc, const float *g_xo, const float *g_po,
+                                   int64_t B, int C, int64_t F, int S, int width, int taps, float *g_x, float *g_pyr, float *partials,
+                                   void *stream);
+int64_t ntm_unet_up_combine_backward_partials(int64_t F);
+int ntm_unet_up_combine_backward(const float *x, const float *ker, const float *wc, const float *g_xo, const float *g_po, int64_t B,
+                                 int C, int64_t F, int S, int width, int taps, int64_t pyr_T, float *g_x, float *g_pyr,
+                                 float *partials, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

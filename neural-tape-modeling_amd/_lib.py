@@ -92,6 +92,9 @@ _SIGNATURES = {
     "ntm_unet_resblock_forward_save": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ntm_unet_resblock_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ntm_unet_wgrad_reduce": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "ntm_unet_down_combine_backward": (_int, [_vp] * 5 + [_i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "ntm_unet_up_combine_backward_partials": (_i64, [_i64]),
+    "ntm_unet_up_combine_backward": (_int, [_vp] * 5 + [_i64, _int, _i64, _int, _int, _int, _i64, _vp, _vp, _vp, _vp]),
     "ntm_unet_down_combine": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp]),
     "ntm_unet_up_combine": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp]),
     "ntm_unet_upsample": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),

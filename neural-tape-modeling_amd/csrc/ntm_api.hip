@@ -445,6 +445,52 @@ int ntm_unet_upsample(const float *x, const float *ker, int64_t B, int64_t F, in
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_upsample");
 }
 
+int ntm_unet_down_combine_backward(const float *pyr_d, const float *ker, const float *wc, const float *g_xo, const float *g_po,
+                                   int64_t B, int C, int64_t F, int S, int width, int taps, float *g_x, float *g_pyr, float *partials,
+                                   void *stream)
+{
+    const std::string w("ntm_unet_down_combine_backward");
+    if (int rc = unet_resample_check(w, B, C, F, S, width, taps, F)) return rc;
+    if (taps != 2 * width + S) return fail(NTM_EINVAL, w + ": taps must be 2 * width + S");
+    if (B == 0) return NTM_OK;
+    if (!g_xo && !g_po) return fail(NTM_EINVAL, w + ": g_xo and g_po are both null: no gradient to take");
+    if (!g_x && !g_pyr && !partials) return fail(NTM_EINVAL, w + ": g_x, g_pyr and partials are all null: nothing to write");
+    if (!ker || !wc || (partials && !pyr_d)) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_unet_down_backward(pyr_d, ker, wc, g_xo, g_po, B, C, F, S, width, taps, g_x, g_pyr, partials,
+                                                  (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_down_combine_backward");
+}
+
+int64_t ntm_unet_up_combine_backward_partials(int64_t F)
+{
+    if (F < 1 || F > 0x7fffffff / 2) {
+        fail(NTM_EINVAL, "ntm_unet_up_combine_backward_partials: F must lie in [1, 2^30)");
+        return -1;
+    }
+    return ntm::unet_up_backward_tiles(F);
+}
+
+int ntm_unet_up_combine_backward(const float *x, const float *ker, const float *wc, const float *g_xo, const float *g_po, int64_t B,
+                                 int C, int64_t F, int S, int width, int taps, int64_t pyr_T, float *g_x, float *g_pyr,
+                                 float *partials, void *stream)
+{
+    const std::string w("ntm_unet_up_combine_backward");
+    if (int rc = unet_resample_check(w, B, C, F, S, width, taps, (int64_t)S * F)) return rc;
+    if (S == 1 ? (taps != 0 || width != 0) : taps != 2 * width + 1)
+        return fail(NTM_EINVAL, w + ": taps must be 2 * width + 1 (S == 1: no filter, width == taps == 0)");
+    if (pyr_T != 0 && pyr_T < F) return fail(NTM_EINVAL, w + ": the pyramid is shorter than F (pyr_T == 0: no pyramid)");
+    if (pyr_T > 0x7fffffff) return fail(NTM_EINVAL, w + ": pyr_T must be below 2^31");
+    if (S == 1 && (ker || g_xo)) return fail(NTM_EINVAL, w + ": S == 1 is the combiner alone: ker and g_xo must be NULL");
+    if (pyr_T == 0 && g_pyr) return fail(NTM_EINVAL, w + ": g_pyr without a pyramid (pyr_T == 0)");
+    if (B == 0) return NTM_OK;
+    if (!g_xo && !g_po) return fail(NTM_EINVAL, w + ": g_xo and g_po are both null: no gradient to take");
+    if (!g_x && !g_pyr && !partials) return fail(NTM_EINVAL, w + ": g_x, g_pyr and partials are all null: nothing to write");
+    if (!wc || (S > 1 && !ker) || (partials && !x)) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_unet_up_backward(x, ker, wc, g_xo, g_po, B, C, F, S, width, taps, pyr_T, g_x, g_pyr, partials,
+                                                (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_up_combine_backward");
+}
+
 int ntm_edm_pre(const float *z, const float *eps, float eps_scale, float snoise, const float *mask, int64_t mask_stride,
                 const float *x_out, const float *n, float sigma0, float cin, int64_t B, int64_t T, float *z_out, float *net_in,
                 void *stream)

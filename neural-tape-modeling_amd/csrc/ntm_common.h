@@ -184,6 +184,14 @@ hipError_t launch_unet_block_backward(const float *src0, const float *src1, cons
                                       const ntm_unet_block &k, const float *ysave, const float *gout, float *ws, float *g_src0,
                                       float *g_src1, float *gfilm, float *part, hipStream_t stream);
 hipError_t launch_unet_wgrad_reduce(const float *part, int64_t count, int64_t n, float *out, hipStream_t stream);
+// the adjoints of the resample + combine steps (unet_resample_train.hip)
+int64_t unet_up_backward_tiles(int64_t F);     // combiner-weight partials of one stream of ntm_unet_up_combine_backward
+hipError_t launch_unet_down_backward(const float *pd, const float *ker, const float *wc, const float *g_xo, const float *g_po,
+                                     int64_t B, int C, int64_t F, int S, int width, int taps, float *g_x, float *g_pyr, float *part,
+                                     hipStream_t stream);
+hipError_t launch_unet_up_backward(const float *x, const float *ker, const float *wc, const float *g_xo, const float *g_po, int64_t B,
+                                   int C, int64_t F, int S, int width, int taps, int64_t pyr_T, float *g_x, float *g_pyr, float *part,
+                                   hipStream_t stream);
 hipError_t launch_delay_f64(const float *x, const double *d, float *y, int64_t B, int64_t T, float *dl_state, int D, int warmup,
                             int32_t *err_flag, hipStream_t stream);
 hipError_t launch_delay_bwd(const float *gy, const float *d, const float *g_newbuf, float *gpre, float *gbuf, int64_t B, int64_t L,

@@ -7,7 +7,11 @@ code/networks/unet_1d.py): the wow-and-flutter delay trajectories that drive Dif
                                restatement, any dtype, any device); forward: it as launches of csrc/unet_kernels.hip bound once
                                per (B, T), HIP device only; record= of either reports the same names from the path that ran
                                forward_train: it as a differentiable graph whose ResnetBlocks of at most 1024 frames are HIP
-                               nodes (training.ResBlockFn on csrc/unet_train.hip), everything else torch ops under autograd
+                               nodes (training.ResBlockFn on csrc/unet_train.hip) and whose resample + combine steps are HIP
+                               nodes at any length (training.DownCombineFn / UpCombineFn on csrc/unet_resample_train.hip);
+                               FiLM and the embedding are torch ops under autograd
+  down_combine / up_combine    one resample + combine step on the device; differentiable (the same nodes) when an operand
+                               requires a gradient
   DiffusionGenerator(args, device)   the EDM sampler with the reference's attributes and methods
   EDMTrainer(args, network, optimizer, device, backend)   the EDM training step and EMA of code/train-diffusion.py
 
@@ -347,18 +351,30 @@ def resblock_forward(src0, film, w_first, w_gated, w_res=None, src1=None, off0=0
     return _bind_resblock(src0.device, src0, film, w_first, w_gated, w_res, src1, off0, frames, init_w, form)(_lib.current_stream())
 
 
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def down_combine(x, pyr, kernel, wc, S, width):
     """Downsample(S) of x (B, C, F) and pyr (B, 1, F) with the (1, 1, 2 width + S) filter, then CombinerDown:
-    -> ((conv1x1(pyr_d) + x_d) / sqrt 2, pyr_d), both ceil(F / S) frames (ntm_unet_down_combine)."""
+    -> ((conv1x1(pyr_d) + x_d) / sqrt 2, pyr_d), both ceil(F / S) frames (ntm_unet_down_combine).  With grad mode on and x, pyr
+    or wc requiring a gradient the same launch runs as a graph node (training.DownCombineFn): same bits, differentiable."""
     _require_hip("down_combine", x, pyr, kernel, wc)
+    if _wants_grad(x, pyr, wc):
+        from .training import DownCombineFn
+        return DownCombineFn.apply(x, pyr, kernel, wc, S, width)
     return _bind_down(x.device, x.contiguous(), pyr.contiguous(), kernel, wc, S, width)(_lib.current_stream())
 
 
 def up_combine(x, pyr, kernel, wc, S, width):
     """CombinerUp then Upsample(S): p = conv1x1(x), or (pyr[..., :F] + conv1x1(x)) / sqrt 2 with a pyramid (B, 1, >= F);
     -> (x, p) both upsampled to S F frames with the (S, 1, 2 width + 1) filter bank.  S = 1 (kernel None): -> (None, p), no
-    resampling -- the last level (ntm_unet_up_combine)."""
+    resampling -- the last level (ntm_unet_up_combine).  With grad mode on and x, pyr or wc requiring a gradient the same launch
+    runs as a graph node (training.UpCombineFn): same bits, differentiable."""
     _require_hip("up_combine", x, pyr, kernel, wc)
+    if _wants_grad(x, pyr, wc):
+        from .training import UpCombineFn
+        return UpCombineFn.apply(x, pyr, kernel, wc, S, width)
     return _bind_up(x.device, x.contiguous(), None if pyr is None else pyr.contiguous(), kernel, wc, S, width)(_lib.current_stream())
 
 
@@ -367,6 +383,7 @@ class _TorchWalk:
 
     def __init__(self, net, emb, record):
         self.init_conv, self.emb, self.record = net.init_conv, emb, record or (lambda name, t: None)
+        self.given = record is not None
 
     def rec(self, name, t):
         self.record(name, t)
@@ -394,7 +411,9 @@ class _TorchWalk:
 class _TrainWalk(_TorchWalk):
     """UNet1D._walk for training: a ResnetBlock of at most WHOLE_MAX_T frames is ONE autograd node on the HIP kernels
     (training.ResBlockFn: ntm_unet_resblock_forward_save / _backward); a longer one (the upper levels of the noise net) is the
-    torch module, and so are the resample, combine, FiLM and embedding steps, all under autograd.  The node reads the
+    torch module.  Every resample + combine step, at any length, is ONE node too (training.DownCombineFn / UpCombineFn: the
+    inference launches ntm_unet_down_combine / ntm_unet_up_combine forward, their adjoints backward), the last step the
+    S = 1 form of the up node.  FiLM and the embedding stay torch ops under autograd.  The block node reads the
     parameters themselves -- the gated weights stacked anew on every call, so that autograd routes the stack's gradient to the
     eight layers -- never _pack()'s copy."""
 
@@ -408,6 +427,24 @@ class _TrainWalk(_TorchWalk):
         out = ResBlockFn.apply(x, skip, blk.film.output_layer(self.emb), blk.first_conv[1].weight, w_gated, res,
                                self.init_conv.weight if first else None, off)
         return self.rec(name, out)
+
+    def down(self, name, down, comb, x, pyr):
+        from .training import DownCombineFn
+        r = down.resample
+        xo, po = DownCombineFn.apply(x, pyr, r.kernel, comb.conv1x1.weight, r.orig, r.width)
+        return self.rec(name, xo), po
+
+    def up(self, name, up, comb, x, pyr):
+        from .training import UpCombineFn
+        r, wc = up.resample, comb.conv1x1.weight
+        if self.given:            # the CombinerUp output before upsampling: the fused node never materialises it (_Plan.up)
+            with torch.no_grad():
+                self.record(name, UpCombineFn.apply(x, pyr, None, wc, 1, 0)[1])
+        return UpCombineFn.apply(x, pyr, r.kernel, wc, r.new, r.width)
+
+    def final(self, name, comb, x, pyr):
+        from .training import UpCombineFn
+        return self.rec(name, UpCombineFn.apply(x, pyr, None, comb.conv1x1.weight, 1, 0)[1].squeeze(1))
 
 
 class _Plan:

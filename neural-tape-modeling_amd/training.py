@@ -31,6 +31,10 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
   * ResBlockFn: one ResnetBlock of the diffusion generators' UNet1D (diffusion.py) in its whole form as ONE graph node on the
     kernels of csrc/unet_train.hip: forward = ntm_unet_resblock_forward_save, backward = ntm_unet_resblock_backward +
     ntm_unet_wgrad_reduce.  UNet1D.forward_train builds its graph from these and torch ops.
+  * DownCombineFn / UpCombineFn: one Downsample + CombinerDown, or CombinerUp + Upsample (S = 1: the combiner alone), step of
+    that network as ONE graph node each on csrc/unet_resample_train.hip: forward = the inference launch (ntm_unet_down_combine /
+    ntm_unet_up_combine), backward = ntm_unet_down_combine_backward / ntm_unet_up_combine_backward + ntm_unet_wgrad_reduce.
+    diffusion.down_combine / up_combine route through them when an operand requires a gradient.
   * GRUTrainStep and loss_with_grad take an optional replica count R: the same nodes for R independent models stacked
     replica-major (model.Replicas) through the `_replicas` entry points -- one forward, one BPTT, one reduction and one loss
     launch for all of them, each replica's bits those of the R = None node on its slice.  The reduction and the loss adjoints
@@ -529,3 +533,94 @@ class ResBlockFn(torch.autograd.Function):
         if film.shape[0] == 1 and B != 1:
             gfilm = gfilm.sum(0, keepdim=True)            # one FiLM vector for all streams: the rows add
         return g0, g1, gfilm, d_first, d_gated, d_res, d_init, None
+
+
+def _grad32(g):
+    return None if g is None else g.detach().to(torch.float32).contiguous()
+
+
+class DownCombineFn(torch.autograd.Function):
+    """(x (B, C, F), pyr (B, 1, F), kernel (1, 1, 2 width + S), wc (C, 1, 1), S, width) -> (xo, po): the Downsample(S) +
+    CombinerDown step of the diffusion generators' UNet1D (diffusion.down_combine) as ONE graph node.  forward =
+    ntm_unet_down_combine, the inference launch, so the outputs are its bits; backward = ntm_unet_down_combine_backward (one
+    launch: g_x, g_pyr and the per-stream partials of the combiner weight, summed in fp64 in a fixed order) +
+    ntm_unet_wgrad_reduce (the partials over the streams in index order).  An output that nothing reads arrives as no gradient
+    and costs nothing; an input that needs no gradient (the top level's pyramid is the network input) is not computed.  No
+    gradient goes to the filter, S or width.  No atomics: equal calls give equal bits.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, pyr, kernel, wc, S, width):
+        from . import diffusion as D
+        D._require_hip("DownCombineFn", x, pyr, kernel, wc)
+        x, pyr, kernel, wc = (t.detach().contiguous() for t in (x, pyr, kernel, wc))
+        xo, po = D._bind_down(x.device, x, pyr, kernel, wc, int(S), int(width))(_lib.current_stream())
+        ctx.save_for_backward(kernel, wc, po)
+        ctx.res = (x.shape, int(S), int(width))
+        ctx.set_materialize_grads(False)
+        return xo, po
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xo, g_po):
+        kernel, wc, po = ctx.saved_tensors
+        (B, C, Fr), S, width = ctx.res
+        need, L = ctx.needs_input_grad, _lib.lib()
+        if (g_xo is None and g_po is None) or not (need[0] or need[1] or need[3]):
+            return None, None, None, None, None, None
+        g_xo, g_po = _grad32(g_xo), _grad32(g_po)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=po.device)       # noqa: E731
+        g_x = new(B, C, Fr) if need[0] else None
+        g_pyr = new(B, 1, Fr) if need[1] else None
+        part, g_wc = (new(B, C), new(C)) if need[3] else (None, None)
+        _lib.check(L.ntm_unet_down_combine_backward(ptr(po), ptr(kernel), ptr(wc), ptr(g_xo), ptr(g_po), B, C, Fr, S, width,
+                                                    kernel.shape[-1], ptr(g_x), ptr(g_pyr), ptr(part), _lib.current_stream()),
+                   "ntm_unet_down_combine_backward")
+        if part is not None:
+            _lib.check(L.ntm_unet_wgrad_reduce(ptr(part), B, C, ptr(g_wc), _lib.current_stream()), "ntm_unet_wgrad_reduce")
+            g_wc = g_wc.view(wc.shape)
+        return g_x, g_pyr, None, g_wc, None, None
+
+
+class UpCombineFn(torch.autograd.Function):
+    """(x (B, C, F), pyr (B, 1, >= F) | None, kernel (S, 1, 2 width + 1) | None, wc (1, C, 1), S, width) -> (xo | None, po): the
+    CombinerUp + Upsample(S) step of the diffusion generators' UNet1D (diffusion.up_combine) as ONE graph node; S = 1 with no
+    kernel is the combiner alone, the network's last step, and returns (None, po).  forward = ntm_unet_up_combine, the inference
+    launch, so the outputs are its bits; backward = ntm_unet_up_combine_backward (one launch: g_x, g_pyr -- zero behind frame F
+    -- and the per-(stream, tile) partials of the combiner weight in fp64) + ntm_unet_wgrad_reduce.  The rules of
+    DownCombineFn hold: absent gradients and unwanted outputs cost nothing, the filter, S and width take none, equal calls give
+    equal bits, no double backward."""
+
+    @staticmethod
+    def forward(ctx, x, pyr, kernel, wc, S, width):
+        from . import diffusion as D
+        D._require_hip("UpCombineFn", x, pyr, kernel, wc)
+        x, wc = x.detach().contiguous(), wc.detach().contiguous()
+        pyr, kernel = (None if t is None else t.detach().contiguous() for t in (pyr, kernel))
+        xo, po = D._bind_up(x.device, x, pyr, kernel, wc, int(S), int(width))(_lib.current_stream())
+        ctx.save_for_backward(x, kernel, wc)
+        ctx.res = (int(S), int(width), 0 if pyr is None else pyr.shape[-1])
+        ctx.set_materialize_grads(False)
+        return xo, po
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xo, g_po):
+        x, kernel, wc = ctx.saved_tensors
+        S, width, pyr_T = ctx.res
+        B, C, Fr = x.shape
+        need, L = ctx.needs_input_grad, _lib.lib()
+        if (g_xo is None and g_po is None) or not (need[0] or (need[1] and pyr_T) or need[3]):
+            return None, None, None, None, None, None
+        g_xo, g_po = _grad32(g_xo), _grad32(g_po)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)        # noqa: E731
+        g_x = new(B, C, Fr) if need[0] else None
+        g_pyr = new(B, 1, pyr_T) if need[1] and pyr_T else None
+        tiles = L.ntm_unet_up_combine_backward_partials(Fr)
+        part, g_wc = (new(B * tiles, C), new(C)) if need[3] else (None, None)
+        _lib.check(L.ntm_unet_up_combine_backward(ptr(x), ptr(kernel), ptr(wc), ptr(g_xo), ptr(g_po), B, C, Fr, S, width,
+                                                  0 if kernel is None else kernel.shape[-1], pyr_T, ptr(g_x), ptr(g_pyr), ptr(part),
+                                                  _lib.current_stream()), "ntm_unet_up_combine_backward")
+        if part is not None:
+            _lib.check(L.ntm_unet_wgrad_reduce(ptr(part), B * tiles, C, ptr(g_wc), _lib.current_stream()), "ntm_unet_wgrad_reduce")
+            g_wc = g_wc.view(wc.shape)
+        return g_x, g_pyr, None, g_wc, None, None

@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Times one EDM training step of the trajectory net at the reference's shape (B = 4 x 512 samples, configs/conf_trajectories.yaml)
-on the HIP backend (UNet1D.forward_train: training.ResBlockFn on csrc/unet_train.hip) against the torch backend (the same modules
-under torch autograd) on the same device, splits the HIP step into the ResBlockFn forwards, their backwards, the weight-gradient
-reductions inside those and the torch-op remainder, and times one block forward + backward at each level's frame count both ways.
+on the HIP backend (UNet1D.forward_train: training.ResBlockFn on csrc/unet_train.hip, training.DownCombineFn / UpCombineFn on
+csrc/unet_resample_train.hip) against the torch backend (the same modules under torch autograd) on the same device and against
+the PARENT-STYLE step (the same HIP trainer with the resample + combine steps of _TrainWalk bypassed to _TorchWalk's torch ops:
+what the step was before those nodes), the two alternating in one process and the pair measured twice to show the spread; counts
+the device kernels of a step both ways (torch.profiler, where it works); splits the HIP step into the ResBlockFn forwards and
+backwards, the resample + combine nodes' forwards and backwards, the weight-gradient reductions inside the backwards and the
+torch-op remainder; and times one block forward + backward at each level's frame count both ways.
 Warm-up, then device-event times, medians; one JSON line at the end.
 
 Usage:  python tools/diffusion_train_probe.py [--reps 9]
@@ -51,6 +55,61 @@ def trainer(backend):
     return tr
 
 
+class parent_style:
+    """Inside, _TrainWalk runs its resample + combine steps as _TorchWalk does: torch ops under autograd."""
+    NAMES = ("down", "up", "final")
+
+    def __enter__(self):
+        W = diffusion._TrainWalk
+        self.saved = {n: W.__dict__[n] for n in self.NAMES}
+        for n in self.NAMES:
+            setattr(W, n, getattr(diffusion._TorchWalk, n))
+
+    def __exit__(self, *exc):
+        for n, f in self.saved.items():
+            setattr(diffusion._TrainWalk, n, f)
+
+
+def parent_step(tr, x):
+    with parent_style():
+        tr.train_step(x)
+
+
+def one(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def alternating(new, old, reps, warmup=3):
+    """-> medians (new, old) of `reps` steps each, one of each in turn."""
+    for _ in range(warmup):
+        new(), old()
+    torch.cuda.synchronize()
+    rows = [(one(new), one(old)) for _ in range(reps)]
+    return statistics.median(r[0] for r in rows), statistics.median(r[1] for r in rows)
+
+
+def kernels_of(fn):
+    """Device kernels one call of fn starts, or None where the profiler gives no device events."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower()
+                and "memset" not in e.name.lower())
+        return n or None
+    except Exception as e:                                    # noqa: BLE001 -- a count, not a result
+        print(f"kernel count: {type(e).__name__}: {e}", flush=True)
+        return None
+
+
 class Spans:
     """Device time between pairs of events, summed per name over one step."""
 
@@ -88,11 +147,24 @@ def main():
                             "torch": round(timed(lambda: ref.train_step(x), args.reps), 4)}
     print(f"train_step  HIP {out['train_step_ms']['hip']:.3f} ms   torch {out['train_step_ms']['torch']:.3f} ms", flush=True)
 
+    # the new step against the parent-style step, alternating, the pair twice
+    old = trainer("hip")
+    pairs = [alternating(lambda: hip.train_step(x), lambda: parent_step(old, x), args.reps) for _ in range(2)]
+    out["new_vs_parent_style_ms"] = [{"new": round(a, 4), "parent_style": round(b, 4)} for a, b in pairs]
+    out["spread_ms"] = {"new": round(abs(pairs[0][0] - pairs[1][0]), 4), "parent_style": round(abs(pairs[0][1] - pairs[1][1]), 4)}
+    print("new vs parent-style step, two alternating runs:", out["new_vs_parent_style_ms"], "spread", out["spread_ms"], flush=True)
+    out["kernels_per_step"] = {"new": kernels_of(lambda: hip.train_step(x)), "parent_style": kernels_of(lambda: parent_step(old, x))}
+    print("device kernels per step:", out["kernels_per_step"], flush=True)
+
     # the split of the HIP step
     spans, L, F = Spans(), _lib.lib(), training.ResBlockFn
     saved = (F.forward, F.backward, L.ntm_unet_wgrad_reduce)
     F.forward, F.backward = staticmethod(spans.wrap("forward", saved[0])), staticmethod(spans.wrap("backward", saved[1]))
     L.ntm_unet_wgrad_reduce = spans.wrap("reduce", saved[2])
+    nodes = (training.DownCombineFn, training.UpCombineFn)
+    saved_nodes = [(N.forward, N.backward) for N in nodes]
+    for N, (fw, bw) in zip(nodes, saved_nodes):
+        N.forward, N.backward = staticmethod(spans.wrap("resample_forward", fw)), staticmethod(spans.wrap("resample_backward", bw))
     try:
         rows = []
         for _ in range(args.reps):
@@ -105,8 +177,10 @@ def main():
             rows.append(row)
     finally:
         F.forward, F.backward, L.ntm_unet_wgrad_reduce = staticmethod(saved[0]), staticmethod(saved[1]), saved[2]
+        for N, (fw, bw) in zip(nodes, saved_nodes):
+            N.forward, N.backward = staticmethod(fw), staticmethod(bw)
     med = {k: statistics.median(r[k] for r in rows) for k in rows[0]}
-    med["torch_ops"] = med["step"] - med["forward"] - med["backward"]
+    med["torch_ops"] = med["step"] - med["forward"] - med["backward"] - med["resample_forward"] - med["resample_backward"]
     out["hip_step_split_ms"] = {k: round(v, 4) for k, v in med.items()}
     print("split of the HIP step (with the events' own cost):", out["hip_step_split_ms"], flush=True)
 
