@@ -841,6 +841,45 @@ int ntm_unet_resblock_backward(const float *src0, const float *src1, const float
 int ntm_unet_wgrad_reduce(const float *partials, int64_t count, int64_t n, float *out, void *stream);
 
 /*
+ * The same pair for the TILED form of the block, at any length (the upper levels of the noise net: 65 536 frames and more).
+ * Additions within ABI version 9.  Operands, layouts and results are those of the whole-form namesakes; accepted are form
+ * NTM_UNET_TILED at any T >= 1 and NTM_UNET_AUTO with T > NTM_UNET_WHOLE_MAX_T.  With tiles = ceil(T / NTM_UNET_TILE):
+ *
+ * ntm_unet_resblock_tiled_forward_save: the tiled forward in its runs of layers (ntm_unet_resblock_forward), which also writes
+ *   y_0 .. y_{n_layers - 1} to ysave [B][n_layers][c_out][T] (ntm_unet_resblock_tiled_save_floats(B, blk) floats), every frame
+ *   by the tile that owns it; y travels between the runs in the save itself, so there is no workspace.  out is bit-identical
+ *   to ntm_unet_resblock_forward's tiled form (one body).
+ * ntm_unet_resblock_tiled_backward: one workgroup per (tile, stream) on the forward's windows (the tile and 256 frames of halo a
+ *   side: the gradient enters a run of layers over the window and leaves it exact on the tile).  The forward's runs last to
+ *   first, then the 1x1s, FiLM and the sources per tile, then three fixed-order sums: 2 + 3 launches up to seven layers,
+ *   3 + 3 for eight.
+ *     ws        ntm_unet_resblock_tiled_workspace_floats(B, blk) floats: gy [B][c_out][T] between the launches (two such planes
+ *               when the layers take two runs) and the gfilm partials [B][tiles][c0 + c1]
+ *     gfilm     [B][c0 + c1], the partials of a stream's tiles added in tile order in fp64, rounded once
+ *     partials  ntm_unet_resblock_tiled_partial_floats(B, blk) = B (1 + 9 tiles) P floats, P =
+ *               ntm_unet_resblock_tiled_wgrad_floats(blk) = ntm_unet_resblock_wgrad_floats' formula: on return the FIRST B
+ *               partials [B][P] are the per-stream sums (a tile's eight waves in wave order, then a stream's tiles in tile
+ *               order, fp64 each, rounded once each), which ntm_unet_wgrad_reduce(partials, B, P, out) adds over the streams;
+ *               behind them the per-tile and the per-(tile, wave) partials as the kernels wrote them
+ *   No atomics anywhere: equal calls give equal bits, and a stream's g_src0, g_src1, gfilm and partial do not depend on its batch.
+ *   The four size queries return -1 on arguments the entry points refuse.  Refused (NTM_EINVAL, a message starting with the
+ *   function's name, before anything touches a device): what the whole-form pair refuses except the length -- and instead of
+ *   the tiled form the whole one (NTM_UNET_WHOLE, NTM_UNET_AUTO with T <= NTM_UNET_WHOLE_MAX_T) -- and 8 B tiles >= 2^31.
+ *   B == 0 returns NTM_OK.
+ */
+int64_t ntm_unet_resblock_tiled_save_floats(int64_t B, const ntm_unet_block *blk);
+int64_t ntm_unet_resblock_tiled_workspace_floats(int64_t B, const ntm_unet_block *blk);
+int64_t ntm_unet_resblock_tiled_wgrad_floats(const ntm_unet_block *blk);
+int64_t ntm_unet_resblock_tiled_partial_floats(int64_t B, const ntm_unet_block *blk);
+int ntm_unet_resblock_tiled_forward_save(const float *src0, const float *src1, const float *init_w, const float *film,
+                                         int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res,
+                                         int64_t B, const ntm_unet_block *blk, float *ysave, float *out, void *stream);
+int ntm_unet_resblock_tiled_backward(const float *src0, const float *src1, const float *init_w, const float *film,
+                                     int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res, int64_t B,
+                                     const ntm_unet_block *blk, const float *ysave, const float *gout, float *ws, float *g_src0,
+                                     float *g_src1, float *gfilm, float *partials, void *stream);
+
+/*
  * The adjoints of ntm_unet_down_combine and ntm_unet_up_combine (csrc/unet_resample_train.hip).  Additions within ABI version 9.
  * Sizes, layouts and limits are the forwards'; fp32 in and out, one launch each.  No atomics: every sum is a gather in a fixed
  * order, so equal calls give equal bits and a stream's results do not depend on its batch.  An upstream gradient that is NULL is

@@ -92,6 +92,12 @@ _SIGNATURES = {
     "ntm_unet_resblock_forward_save": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ntm_unet_resblock_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ntm_unet_wgrad_reduce": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "ntm_unet_resblock_tiled_save_floats": (_i64, [_i64, _vp]),
+    "ntm_unet_resblock_tiled_workspace_floats": (_i64, [_i64, _vp]),
+    "ntm_unet_resblock_tiled_wgrad_floats": (_i64, [_vp]),
+    "ntm_unet_resblock_tiled_partial_floats": (_i64, [_i64, _vp]),
+    "ntm_unet_resblock_tiled_forward_save": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ntm_unet_resblock_tiled_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ntm_unet_down_combine_backward": (_int, [_vp] * 5 + [_i64, _int, _i64, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "ntm_unet_up_combine_backward_partials": (_i64, [_i64]),
     "ntm_unet_up_combine_backward": (_int, [_vp] * 5 + [_i64, _int, _i64, _int, _int, _int, _i64, _vp, _vp, _vp, _vp]),

@@ -314,12 +314,16 @@ int ntm_unet_resblock_forward(const float *src0, const float *src1, const float 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_forward");
 }
 
-// the argument checks the training entry points of the block share: the forward's, and the whole form only
-static int unet_train_check(const std::string &w, int64_t B, const ntm_unet_block *k)
+// the argument checks the training entry points of the block share: the forward's, and the whole form only -- or, for the
+// ntm_unet_resblock_tiled_* family, the tiled form only: forced at any length, or what NTM_UNET_AUTO picks above 1024 frames
+static int unet_train_check(const std::string &w, int64_t B, const ntm_unet_block *k, bool tiled = false)
 {
     if (int rc = unet_block_check(w, B, k)) return rc;
-    if (k->T > NTM_UNET_WHOLE_MAX_T || k->form == NTM_UNET_TILED)
-        return fail(NTM_EINVAL, w + ": the whole form only, T <= 1024 (the adjoint of the tiled form is not built)");
+    if (!tiled && (k->T > NTM_UNET_WHOLE_MAX_T || k->form == NTM_UNET_TILED))
+        return fail(NTM_EINVAL, w + ": the whole form only, T <= 1024 (the tiled form: ntm_unet_resblock_tiled_*)");
+    if (tiled && (k->form == NTM_UNET_WHOLE || (k->form == NTM_UNET_AUTO && k->T <= NTM_UNET_WHOLE_MAX_T)))
+        return fail(NTM_EINVAL, w + ": the tiled form only, NTM_UNET_TILED or NTM_UNET_AUTO with T > 1024");
+    if (tiled && B * ntm::unet_block_tiles(*k) > 0x7fffffff / 8) return fail(NTM_EINVAL, w + ": 8 B tiles must be below 2^31");
     return NTM_OK;
 }
 
@@ -344,9 +348,9 @@ int64_t ntm_unet_resblock_partial_floats(int64_t B, const ntm_unet_block *blk)
 // what _forward_save and _backward check of the forward's operands
 static int unet_train_operands(const std::string &w, const float *src0, const float *src1, const float *init_w, const float *film,
                                int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res, int64_t B,
-                               const ntm_unet_block *blk)
+                               const ntm_unet_block *blk, bool tiled = false)
 {
-    if (int rc = unet_train_check(w, B, blk)) return rc;
+    if (int rc = unet_train_check(w, B, blk, tiled)) return rc;
     const int cin = blk->c0 + blk->c1;
     if (film_stride != 0 && film_stride < cin) return fail(NTM_EINVAL, w + ": film_stride must be 0 or at least c0 + c1");
     if (!w_res && cin != blk->c_out) return fail(NTM_EINVAL, w + ": an identity residual (w_res == NULL) needs c0 + c1 == c_out");
@@ -383,6 +387,60 @@ int ntm_unet_resblock_backward(const float *src0, const float *src1, const float
     hipError_t e = ntm::launch_unet_block_backward(src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, *blk, ysave, gout,
                                                    ws, g_src0, g_src1, gfilm, partials, (hipStream_t)stream);
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_backward");
+}
+
+int64_t ntm_unet_resblock_tiled_save_floats(int64_t B, const ntm_unet_block *blk)
+{
+    if (unet_train_check("ntm_unet_resblock_tiled_save_floats", B, blk, true) != NTM_OK) return -1;
+    return B * blk->n_layers * blk->c_out * blk->T;
+}
+
+int64_t ntm_unet_resblock_tiled_workspace_floats(int64_t B, const ntm_unet_block *blk)
+{
+    if (unet_train_check("ntm_unet_resblock_tiled_workspace_floats", B, blk, true) != NTM_OK) return -1;
+    return ntm::unet_block_tiled_workspace(B, *blk);
+}
+
+int64_t ntm_unet_resblock_tiled_wgrad_floats(const ntm_unet_block *blk)
+{
+    if (unet_train_check("ntm_unet_resblock_tiled_wgrad_floats", 0, blk, true) != NTM_OK) return -1;
+    return ntm::unet_block_wgrad_floats(*blk);
+}
+
+int64_t ntm_unet_resblock_tiled_partial_floats(int64_t B, const ntm_unet_block *blk)
+{
+    if (unet_train_check("ntm_unet_resblock_tiled_partial_floats", B, blk, true) != NTM_OK) return -1;
+    return ntm::unet_block_tiled_partials(B, *blk) * ntm::unet_block_wgrad_floats(*blk);
+}
+
+int ntm_unet_resblock_tiled_forward_save(const float *src0, const float *src1, const float *init_w, const float *film,
+                                         int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res,
+                                         int64_t B, const ntm_unet_block *blk, float *ysave, float *out, void *stream)
+{
+    const std::string w("ntm_unet_resblock_tiled_forward_save");
+    if (int rc = unet_train_operands(w, src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, blk, true)) return rc;
+    if (B == 0) return NTM_OK;
+    if (!ysave || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    if (out == src0 || out == src1) return fail(NTM_EINVAL, w + ": out must not alias a source");
+    hipError_t e = ntm::launch_unet_block_tiled_save(src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, *blk, ysave,
+                                                     out, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_tiled_forward_save");
+}
+
+int ntm_unet_resblock_tiled_backward(const float *src0, const float *src1, const float *init_w, const float *film,
+                                     int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res, int64_t B,
+                                     const ntm_unet_block *blk, const float *ysave, const float *gout, float *ws, float *g_src0,
+                                     float *g_src1, float *gfilm, float *partials, void *stream)
+{
+    const std::string w("ntm_unet_resblock_tiled_backward");
+    if (int rc = unet_train_operands(w, src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, blk, true)) return rc;
+    if (blk->init && g_src0) return fail(NTM_EINVAL, w + ": with init the waveform takes no gradient (g_src0 must be NULL)");
+    if (blk->c1 == 0 && g_src1) return fail(NTM_EINVAL, w + ": g_src1 without a second source");
+    if (B == 0) return NTM_OK;
+    if (!ysave || !gout || !ws || !gfilm || !partials) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_unet_block_tiled_backward(src0, src1, init_w, film, film_stride, w_first, w_gated, w_res, B, *blk, ysave,
+                                                         gout, ws, g_src0, g_src1, gfilm, partials, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_resblock_tiled_backward");
 }
 
 int ntm_unet_wgrad_reduce(const float *partials, int64_t count, int64_t n, float *out, void *stream)

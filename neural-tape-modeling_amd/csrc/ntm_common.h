@@ -184,6 +184,17 @@ hipError_t launch_unet_block_backward(const float *src0, const float *src1, cons
                                       const ntm_unet_block &k, const float *ysave, const float *gout, float *ws, float *g_src0,
                                       float *g_src1, float *gfilm, float *part, hipStream_t stream);
 hipError_t launch_unet_wgrad_reduce(const float *part, int64_t count, int64_t n, float *out, hipStream_t stream);
+// the same in the tiled form, at any length: sizes in tiles, floats of workspace and partials (of wgrad_floats each)
+int64_t unet_block_tiles(const ntm_unet_block &k);
+int64_t unet_block_tiled_workspace(int64_t B, const ntm_unet_block &k);
+int64_t unet_block_tiled_partials(int64_t B, const ntm_unet_block &k);
+hipError_t launch_unet_block_tiled_save(const float *src0, const float *src1, const float *init_w, const float *film,
+                                        int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res, int64_t B,
+                                        const ntm_unet_block &k, float *ysave, float *out, hipStream_t stream);
+hipError_t launch_unet_block_tiled_backward(const float *src0, const float *src1, const float *init_w, const float *film,
+                                            int64_t film_stride, const float *w_first, const float *w_gated, const float *w_res,
+                                            int64_t B, const ntm_unet_block &k, const float *ysave, const float *gout, float *ws,
+                                            float *g_src0, float *g_src1, float *gfilm, float *part, hipStream_t stream);
 // the adjoints of the resample + combine steps (unet_resample_train.hip)
 int64_t unet_up_backward_tiles(int64_t F);     // combiner-weight partials of one stream of ntm_unet_up_combine_backward
 hipError_t launch_unet_down_backward(const float *pd, const float *ker, const float *wc, const float *g_xo, const float *g_po,

@@ -45,8 +45,14 @@ __device__ __forceinline__ float ublock_src(const UBlockArgs &a, int64_t b, int 
     return a.src1[(b * a.c1 + (ci - a.c0)) * a.T1 + f + a.off1];
 }
 
-// The forward of one window of one stream.  SAVE (the whole form only, l0 == 0): y_l of every gated layer l < nl also goes to
-// ysave [B][nl][cout][T], for the adjoint; without SAVE the pointer is not read and the code is the inference kernel's.
+// window position p of a frame in [0, T): one of the tile's own frames, not the halo's
+__device__ __forceinline__ bool ublock_mine_in(const UBlockArgs &a, int p) { return (unsigned)(p - a.halo) < (unsigned)a.tile; }
+
+// The forward of one window of one stream.  SAVE: y_l of every gated layer l < nl also goes to ysave [B][nl][cout][T], for the
+// adjoint, at the frames the window OWNS (deep in a fused run the halo's values are not the signal's; in the whole form every
+// frame is owned).  Between the runs of the tiled form y travels in the save itself: a run reads y_{l0} from its plane and
+// leaves y_{l1} in the next one, y_in / y_out are not read.  Without SAVE the pointer is not read and the code is the inference
+// kernel's.
 template <bool SAVE>
 __device__ __forceinline__ void unet_block_body(UBlockArgs a, float *ysave)
 {
@@ -92,14 +98,19 @@ __device__ __forceinline__ void unet_block_body(UBlockArgs a, float *ysave)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = kq * 4 + r;
-                if (row < cout && in) Y[j][r] = a.y_in[(b * cout + row) * a.T + f];
+                if (row < cout && in) {
+                    if constexpr (SAVE)
+                        Y[j][r] = (ysave + (b * a.nl + a.l0) * cout * a.T)[row * a.T + f];
+                    else
+                        Y[j][r] = a.y_in[(b * cout + row) * a.T + f];
+                }
             }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = kq * 4 + r;
             if (row < a.CP) lds[row * P + p0 + li] = in ? gelu_f32(Y[j][r]) : 0.0f;
-            if (SAVE && row < cout && in) (ysave + (b * a.nl + a.l0) * cout * a.T)[row * a.T + f] = Y[j][r];
+            if (SAVE && a.l0 == 0 && row < cout && in && ublock_mine_in(a, p0 + li)) (ysave + b * a.nl * cout * a.T)[row * a.T + f] = Y[j][r];
         }
     }
     __syncthreads();
@@ -154,7 +165,7 @@ __device__ __forceinline__ void unet_block_body(UBlockArgs a, float *ysave)
                 Y[j][r] = (Y[j][r] + acc[r]) * kRsqrt2;
                 const int row = kq * 4 + r;
                 if (more && row < a.CP) Gn[row * P + p0 + li] = in ? gelu_f32(Y[j][r]) : 0.0f;
-                if (SAVE && more && row < cout && in) (ysave + (b * a.nl + l + 1) * cout * a.T)[row * a.T + f] = Y[j][r];
+                if (SAVE && more && row < cout && in && ublock_mine_in(a, p0 + li)) (ysave + (b * a.nl + l + 1) * cout * a.T)[row * a.T + f] = Y[j][r];
             }
         }
 #pragma unroll
@@ -178,7 +189,12 @@ __device__ __forceinline__ void unet_block_body(UBlockArgs a, float *ysave)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = kq * 4 + r;
-                if (mine && row < cout) a.y_out[(b * cout + row) * a.T + f] = Y[j][r];
+                if (mine && row < cout) {
+                    if constexpr (SAVE)
+                        (ysave + (b * a.nl + a.l1) * cout * a.T)[row * a.T + f] = Y[j][r];
+                    else
+                        a.y_out[(b * cout + row) * a.T + f] = Y[j][r];
+                }
             }
             continue;
         }
@@ -214,5 +230,6 @@ __device__ __forceinline__ void unet_block_body(UBlockArgs a, float *ysave)
 UBlockArgs unet_block_args(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
                            const float *w_first, const float *w_gated, const float *w_res, const ntm_unet_block &k, float *out);
 size_t unet_block_lds_bytes(const UBlockArgs &a);
+int ublock_run_end(int l0, int nl);     // layers [l0, l1) of a tiled run
 
 }  // namespace ntm

@@ -30,7 +30,7 @@ namespace ntm {
 __global__ __launch_bounds__(kUWaves * 64) void unet_block_kernel(UBlockArgs a) { unet_block_body<false>(a, nullptr); }
 
 // layers [l0, l1) of a tiled run: as many as keep 2 sum(d) within the halo
-static int ublock_run_end(int l0, int nl)
+int ublock_run_end(int l0, int nl)
 {
     int l1 = l0, reach = 0;
     while (l1 < nl && reach + (2 << l1) <= kUHalo) reach += 2 << l1, ++l1;    // a layer of dilation d reaches 2 d a side

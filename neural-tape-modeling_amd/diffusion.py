@@ -6,8 +6,9 @@ code/networks/unet_1d.py): the wow-and-flutter delay trajectories that drive Dif
                                _walk: the network's data flow, written once; forward_torch: it in torch ops (this project's
                                restatement, any dtype, any device); forward: it as launches of csrc/unet_kernels.hip bound once
                                per (B, T), HIP device only; record= of either reports the same names from the path that ran
-                               forward_train: it as a differentiable graph whose ResnetBlocks of at most 1024 frames are HIP
-                               nodes (training.ResBlockFn on csrc/unet_train.hip) and whose resample + combine steps are HIP
+                               forward_train: it as a differentiable graph whose ResnetBlocks are HIP nodes at any length
+                               (training.ResBlockFn up to 1024 frames, training.ResBlockTiledFn above, on
+                               csrc/unet_train.hip) and whose resample + combine steps are HIP
                                nodes at any length (training.DownCombineFn / UpCombineFn on csrc/unet_resample_train.hip);
                                FiLM and the embedding are torch ops under autograd
   down_combine / up_combine    one resample + combine step on the device; differentiable (the same nodes) when an operand
@@ -409,22 +410,26 @@ class _TorchWalk:
 
 
 class _TrainWalk(_TorchWalk):
-    """UNet1D._walk for training: a ResnetBlock of at most WHOLE_MAX_T frames is ONE autograd node on the HIP kernels
-    (training.ResBlockFn: ntm_unet_resblock_forward_save / _backward); a longer one (the upper levels of the noise net) is the
-    torch module.  Every resample + combine step, at any length, is ONE node too (training.DownCombineFn / UpCombineFn: the
+    """UNet1D._walk for training: a ResnetBlock is ONE autograd node on the HIP kernels -- training.ResBlockFn
+    (ntm_unet_resblock_forward_save / _backward, the whole form) up to WHOLE_MAX_T frames, training.ResBlockTiledFn
+    (ntm_unet_resblock_tiled_forward_save / _backward) above, the upper levels of the noise net.  tiled_blocks = False sends the
+    longer blocks to the torch module instead (what tools/diffusion_train_probe.py times the tiled node against).  Every resample + combine step, at any length, is ONE node too (training.DownCombineFn / UpCombineFn: the
     inference launches ntm_unet_down_combine / ntm_unet_up_combine forward, their adjoints backward), the last step the
     S = 1 form of the up node.  FiLM and the embedding stay torch ops under autograd.  The block node reads the
     parameters themselves -- the gated weights stacked anew on every call, so that autograd routes the stack's gradient to the
     eight layers -- never _pack()'s copy."""
 
+    tiled_blocks = True
+
     def block(self, k, name, blk, x, skip=None, off=0, first=False):
         frames = skip.shape[2] if skip is not None else x.shape[2]
-        if frames > WHOLE_MAX_T:
+        if frames > WHOLE_MAX_T and not self.tiled_blocks:
             return super().block(k, name, blk, x, skip, off, first)
-        from .training import ResBlockFn
+        from .training import ResBlockFn, ResBlockTiledFn
         res = None if isinstance(blk.res_conv, nn.Identity) else blk.res_conv.weight
         w_gated = torch.stack([h.conv.weight for h in blk.H])
-        out = ResBlockFn.apply(x, skip, blk.film.output_layer(self.emb), blk.first_conv[1].weight, w_gated, res,
+        node = ResBlockTiledFn if frames > WHOLE_MAX_T else ResBlockFn
+        out = node.apply(x, skip, blk.film.output_layer(self.emb), blk.first_conv[1].weight, w_gated, res,
                                self.init_conv.weight if first else None, off)
         return self.rec(name, out)
 
@@ -606,7 +611,7 @@ class UNet1D(nn.Module):
 
     # -- the training path --
     def forward_train(self, inputs, sigma, record=None):
-        """The network as a differentiable graph whose ResnetBlocks of at most WHOLE_MAX_T frames are HIP nodes (_TrainWalk):
+        """The network as a differentiable graph whose ResnetBlocks, of any length, are HIP nodes (_TrainWalk):
         inputs (B, T), sigma (1 | B, 1) per stream -> (B, T).  HIP device only; `forward` (inference, bound plans) is
         untouched by it."""
         if not inputs.is_cuda:

@@ -31,6 +31,8 @@ no skip connection, exact fp32, on the kernels of csrc/gru_train.hip.
   * ResBlockFn: one ResnetBlock of the diffusion generators' UNet1D (diffusion.py) in its whole form as ONE graph node on the
     kernels of csrc/unet_train.hip: forward = ntm_unet_resblock_forward_save, backward = ntm_unet_resblock_backward +
     ntm_unet_wgrad_reduce.  UNet1D.forward_train builds its graph from these and torch ops.
+  * ResBlockTiledFn: the same node in the block's tiled form, at any length (the levels of the noise net above 1024 frames):
+    forward = ntm_unet_resblock_tiled_forward_save, backward = ntm_unet_resblock_tiled_backward + ntm_unet_wgrad_reduce.
   * DownCombineFn / UpCombineFn: one Downsample + CombinerDown, or CombinerUp + Upsample (S = 1: the combiner alone), step of
     that network as ONE graph node each on csrc/unet_resample_train.hip: forward = the inference launch (ntm_unet_down_combine /
     ntm_unet_up_combine), backward = ntm_unet_down_combine_backward / ntm_unet_up_combine_backward + ntm_unet_wgrad_reduce.
@@ -468,6 +470,73 @@ class AdvHeadFn(torch.autograd.Function):
         return (None, None, *[gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:])])
 
 
+# The two block nodes (ResBlockFn, ResBlockTiledFn) differ in their entry points, in the form they ask for and in how the
+# partials are laid out; the rest is these two helpers.  `fam`: (class name, form, prefix of the entry points).
+
+def _resblock_forward(ctx, fam, src0, src1, film, w_first, w_gated, w_res, init_w, off0):
+    from . import diffusion as D
+    name, form, prefix = fam
+    D._require_hip(name, src0, src1, film, w_first, w_gated, w_res, init_w)
+    if init_w is not None and src0.requires_grad:
+        raise RuntimeError(f"{name}: with init_w the waveform takes no gradient")
+    src0, film, w_first, w_gated = (t.detach().contiguous() for t in (src0, film, w_first, w_gated))
+    src1, w_res, init_w = (None if t is None else t.detach().contiguous() for t in (src1, w_res, init_w))
+    B, T0 = src0.shape[0], src0.shape[2]
+    c0 = init_w.shape[0] if init_w is not None else src0.shape[1]
+    c1, T1 = (0, 0) if src1 is None else src1.shape[1:]
+    T = T1 if src1 is not None else T0 - int(off0)
+    if form == "tiled" and T > D.WHOLE_MAX_T:
+        form = "auto"               # what the entry points pick themselves at this length; "tiled" forces it on a shorter block
+    spec = D.BlockSpec(c0, c1, w_first.shape[0], w_gated.shape[0], T, T0, int(off0), T1, 0, int(init_w is not None),
+                       D.FORMS[form])
+    L, ref = _lib.lib(), _lib.ctypes.byref(spec)
+    n_save = getattr(L, prefix + "save_floats")(B, ref)
+    if n_save < 0:
+        raise _lib.NtmError(f"{prefix}save_floats refused: {L.ntm_last_error().decode()}")
+    if film.shape[0] not in (1, B) or film.shape[1] != c0 + c1:
+        raise RuntimeError(f"{name}: film {tuple(film.shape)} for {B} streams of {c0 + c1} channels")
+    ysave = torch.empty(max(n_save, 1), dtype=torch.float32, device=src0.device)
+    out = torch.empty(B, spec.c_out, T, dtype=torch.float32, device=src0.device)
+    fstride = 0 if film.shape[0] == 1 else film.stride(0)
+    _lib.check(getattr(L, prefix + "forward_save")(ptr(src0), ptr(src1), ptr(init_w), ptr(film), fstride, ptr(w_first),
+                                                   ptr(w_gated), ptr(w_res), B, ref, ptr(ysave), ptr(out),
+                                                   _lib.current_stream()), prefix + "forward_save")
+    ctx.save_for_backward(src0, src1, film, w_first, w_gated, w_res, init_w, ysave)
+    ctx.spec = spec
+    return out
+
+
+def _resblock_backward(ctx, fam, gout):
+    src0, src1, film, w_first, w_gated, w_res, init_w, ysave = ctx.saved_tensors
+    spec, need = ctx.spec, ctx.needs_input_grad
+    tiled = fam[1] == "tiled"
+    prefix = fam[2]
+    L, ref = _lib.lib(), _lib.ctypes.byref(spec)
+    B, cin, cout, n, dev = src0.shape[0], spec.c0 + spec.c1, spec.c_out, spec.n_layers, src0.device
+    gout = gout.detach().to(torch.float32).contiguous()
+    per, total = getattr(L, prefix + "wgrad_floats")(ref), getattr(L, prefix + "partial_floats")(B, ref)
+    n_ws = L.ntm_unet_resblock_tiled_workspace_floats(B, ref) if tiled else B * cout * spec.T
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)       # noqa: E731
+    g0 = torch.empty_like(src0) if need[0] and init_w is None else None
+    g1 = torch.empty_like(src1) if src1 is not None and need[1] else None
+    gfilm, part, ws, grads = new(B, cin), new(max(total, 1)), new(max(n_ws, 1)), new(per)
+    fstride = 0 if film.shape[0] == 1 else film.stride(0)
+    _lib.check(getattr(L, prefix + "backward")(ptr(src0), ptr(src1), ptr(init_w), ptr(film), fstride, ptr(w_first), ptr(w_gated),
+                                               ptr(w_res), B, ref, ptr(ysave), ptr(gout), ptr(ws), ptr(g0), ptr(g1), ptr(gfilm),
+                                               ptr(part), _lib.current_stream()), prefix + "backward")
+    # whole: every (stream, wave) partial; tiled: the per-stream sums the backward left at the head of the buffer
+    _lib.check(L.ntm_unet_wgrad_reduce(ptr(part), B if tiled else total // per, per, ptr(grads), _lib.current_stream()),
+               "ntm_unet_wgrad_reduce")
+    n_g, n_1 = n * cout * cout * 5, cout * cin
+    d_gated = grads[:n_g].view(n, cout, cout, 5)
+    d_first = grads[n_g:n_g + n_1].view(cout, cin, 1)
+    d_res = None if w_res is None else grads[n_g + n_1:n_g + 2 * n_1].view(cout, cin, 1)
+    d_init = None if init_w is None else grads[n_g + 2 * n_1:].view(spec.c0, 1, 5)
+    if film.shape[0] == 1 and B != 1:
+        gfilm = gfilm.sum(0, keepdim=True)            # one FiLM vector for all streams: the rows add
+    return g0, g1, gfilm, d_first, d_gated, d_res, d_init, None
+
+
 class ResBlockFn(torch.autograd.Function):
     """(src0, src1 | None, film, w_first, w_gated, w_res | None, init_w | None, off0) -> one ResnetBlock of the diffusion
     generators' UNet1D as ONE graph node, in the whole form (at most 1024 frames): the operands of diffusion.resblock_forward,
@@ -475,64 +544,35 @@ class ResBlockFn(torch.autograd.Function):
     y_0 .. y_{n-1}); backward = ntm_unet_resblock_backward (one workgroup per stream: the sources' and FiLM's gradients and
     per-(stream, wave) weight-gradient partials) + ntm_unet_wgrad_reduce (their sum in index order in fp64).  No atomics: equal
     calls give equal bits.  With init_w, src0 is the waveform and takes no gradient.  No double backward."""
+    _family = ("ResBlockFn", "whole", "ntm_unet_resblock_")
 
     @staticmethod
     def forward(ctx, src0, src1, film, w_first, w_gated, w_res, init_w, off0):
-        from . import diffusion as D
-        D._require_hip("ResBlockFn", src0, src1, film, w_first, w_gated, w_res, init_w)
-        if init_w is not None and src0.requires_grad:
-            raise RuntimeError("ResBlockFn: with init_w the waveform takes no gradient")
-        src0, film, w_first, w_gated = (t.detach().contiguous() for t in (src0, film, w_first, w_gated))
-        src1, w_res, init_w = (None if t is None else t.detach().contiguous() for t in (src1, w_res, init_w))
-        B, T0 = src0.shape[0], src0.shape[2]
-        c0 = init_w.shape[0] if init_w is not None else src0.shape[1]
-        c1, T1 = (0, 0) if src1 is None else src1.shape[1:]
-        T = T1 if src1 is not None else T0 - int(off0)
-        spec = D.BlockSpec(c0, c1, w_first.shape[0], w_gated.shape[0], T, T0, int(off0), T1, 0, int(init_w is not None),
-                           D.FORMS["whole"])
-        L, ref = _lib.lib(), _lib.ctypes.byref(spec)
-        n_save = L.ntm_unet_resblock_save_floats(B, ref)
-        if n_save < 0:
-            raise _lib.NtmError(f"ntm_unet_resblock_save_floats refused: {L.ntm_last_error().decode()}")
-        if film.shape[0] not in (1, B) or film.shape[1] != c0 + c1:
-            raise RuntimeError(f"ResBlockFn: film {tuple(film.shape)} for {B} streams of {c0 + c1} channels")
-        ysave = torch.empty(max(n_save, 1), dtype=torch.float32, device=src0.device)
-        out = torch.empty(B, spec.c_out, T, dtype=torch.float32, device=src0.device)
-        fstride = 0 if film.shape[0] == 1 else film.stride(0)
-        _lib.check(L.ntm_unet_resblock_forward_save(ptr(src0), ptr(src1), ptr(init_w), ptr(film), fstride, ptr(w_first),
-                                                    ptr(w_gated), ptr(w_res), B, ref, ptr(ysave), ptr(out),
-                                                    _lib.current_stream()), "ntm_unet_resblock_forward_save")
-        ctx.save_for_backward(src0, src1, film, w_first, w_gated, w_res, init_w, ysave)
-        ctx.spec = spec
-        return out
+        return _resblock_forward(ctx, ResBlockFn._family, src0, src1, film, w_first, w_gated, w_res, init_w, off0)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        src0, src1, film, w_first, w_gated, w_res, init_w, ysave = ctx.saved_tensors
-        spec, need = ctx.spec, ctx.needs_input_grad
-        L, ref = _lib.lib(), _lib.ctypes.byref(spec)
-        B, cin, cout, n, dev = src0.shape[0], spec.c0 + spec.c1, spec.c_out, spec.n_layers, src0.device
-        gout = gout.detach().to(torch.float32).contiguous()
-        per, total = L.ntm_unet_resblock_wgrad_floats(ref), L.ntm_unet_resblock_partial_floats(B, ref)
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)       # noqa: E731
-        g0 = torch.empty_like(src0) if need[0] and init_w is None else None
-        g1 = torch.empty_like(src1) if src1 is not None and need[1] else None
-        gfilm, part, ws, grads = new(B, cin), new(max(total, 1)), new(max(B * cout * spec.T, 1)), new(per)
-        fstride = 0 if film.shape[0] == 1 else film.stride(0)
-        _lib.check(L.ntm_unet_resblock_backward(ptr(src0), ptr(src1), ptr(init_w), ptr(film), fstride, ptr(w_first), ptr(w_gated),
-                                                ptr(w_res), B, ref, ptr(ysave), ptr(gout), ptr(ws), ptr(g0), ptr(g1), ptr(gfilm),
-                                                ptr(part), _lib.current_stream()), "ntm_unet_resblock_backward")
-        _lib.check(L.ntm_unet_wgrad_reduce(ptr(part), total // per, per, ptr(grads), _lib.current_stream()),
-                   "ntm_unet_wgrad_reduce")
-        n_g, n_1 = n * cout * cout * 5, cout * cin
-        d_gated = grads[:n_g].view(n, cout, cout, 5)
-        d_first = grads[n_g:n_g + n_1].view(cout, cin, 1)
-        d_res = None if w_res is None else grads[n_g + n_1:n_g + 2 * n_1].view(cout, cin, 1)
-        d_init = None if init_w is None else grads[n_g + 2 * n_1:].view(spec.c0, 1, 5)
-        if film.shape[0] == 1 and B != 1:
-            gfilm = gfilm.sum(0, keepdim=True)            # one FiLM vector for all streams: the rows add
-        return g0, g1, gfilm, d_first, d_gated, d_res, d_init, None
+        return _resblock_backward(ctx, ResBlockFn._family, gout)
+
+
+class ResBlockTiledFn(torch.autograd.Function):
+    """ResBlockFn's signature and return values for the TILED form of the block, at any length (the levels of the noise net
+    above 1024 frames; a shorter block runs forced through the same windows): forward = ntm_unet_resblock_tiled_forward_save
+    (out is the tiled inference forward's bits), backward = ntm_unet_resblock_tiled_backward (one workgroup per (tile, stream) on
+    the forward's windows of a tile of 512 frames and 256 of halo a side; gfilm and the weight gradients summed per stream in a
+    fixed order) + ntm_unet_wgrad_reduce over the streams.  No atomics: equal calls give equal bits, and a stream's source and
+    FiLM gradients do not depend on its batch.  With init_w the waveform takes no gradient.  No double backward."""
+    _family = ("ResBlockTiledFn", "tiled", "ntm_unet_resblock_tiled_")
+
+    @staticmethod
+    def forward(ctx, src0, src1, film, w_first, w_gated, w_res, init_w, off0):
+        return _resblock_forward(ctx, ResBlockTiledFn._family, src0, src1, film, w_first, w_gated, w_res, init_w, off0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        return _resblock_backward(ctx, ResBlockTiledFn._family, gout)
 
 
 def _grad32(g):

@@ -9,7 +9,14 @@ backwards, the resample + combine nodes' forwards and backwards, the weight-grad
 torch-op remainder; and times one block forward + backward at each level's frame count both ways.
 Warm-up, then device-event times, medians; one JSON line at the end.
 
-Usage:  python tools/diffusion_train_probe.py [--reps 9]
+--net noise: the same for the tape-hiss net at the reference's operating point (configs/conf_noise.yaml at the checkpoint's
+depth 6, B = 4 x 65 536 samples), whose three levels above 1024 frames run training.ResBlockTiledFn.  The parent-style step is
+then the HIP trainer with those levels as torch modules (_TrainWalk.tiled_blocks = False: what the step was before the tiled
+node); the split counts both block nodes, and where the profiler gives device times it adds the kernels of the tiled adjoint by
+name (its fixed-order sums run inside the C call, where no event of this script reaches); the block table is at 4 096, 16 384
+and 65 536 frames.
+
+Usage:  python tools/diffusion_train_probe.py [--reps 9] [--net trajectories|noise]
 """
 import argparse
 import json
@@ -24,6 +31,7 @@ sys.path.insert(0, ROOT)
 from ntm_amd import _lib, diffusion, training  # noqa: E402
 
 B, T = 4, 512
+NET = "trajectories"
 
 
 def timed(fn, reps, warmup=3):
@@ -42,7 +50,9 @@ def timed(fn, reps, warmup=3):
 
 
 def trainer(backend):
-    args = diffusion.load_config("trajectories")
+    args = diffusion.load_config(NET)
+    if NET == "noise":
+        args.network.depth = 6        # the checkpoint's (weights/83)
     torch.manual_seed(11)
     net = diffusion.UNet1D(args, "cuda")
     for m in net.modules():           # the reference starts these at zero, which would leave the blocks without a gradient
@@ -56,16 +66,23 @@ def trainer(backend):
 
 
 class parent_style:
-    """Inside, _TrainWalk runs its resample + combine steps as _TorchWalk does: torch ops under autograd."""
+    """Inside, _TrainWalk runs its resample + combine steps as _TorchWalk does: torch ops under autograd.  For the noise net:
+    inside, its blocks above 1024 frames are the torch modules."""
     NAMES = ("down", "up", "final")
 
     def __enter__(self):
         W = diffusion._TrainWalk
+        if NET == "noise":
+            W.tiled_blocks = False
+            return
         self.saved = {n: W.__dict__[n] for n in self.NAMES}
         for n in self.NAMES:
             setattr(W, n, getattr(diffusion._TorchWalk, n))
 
     def __exit__(self, *exc):
+        if NET == "noise":
+            diffusion._TrainWalk.tiled_blocks = True
+            return
         for n, f in self.saved.items():
             setattr(diffusion._TrainWalk, n, f)
 
@@ -110,6 +127,26 @@ def kernels_of(fn):
         return None
 
 
+def kernel_ms_of(fn, word="unet_"):
+    """Device milliseconds of one call of fn per kernel whose name holds `word`, or None where the profiler gives none."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        out = {}
+        for e in prof.key_averages():
+            t = getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0)
+            if word in e.key and t:
+                out[e.key.split("(")[0]] = round(t / 1000.0, 4)
+        return out or None
+    except Exception as e:                                    # noqa: BLE001 -- a table, not a result
+        print(f"kernel times: {type(e).__name__}: {e}", flush=True)
+        return None
+
+
 class Spans:
     """Device time between pairs of events, summed per name over one step."""
 
@@ -139,9 +176,12 @@ class Spans:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--net", choices=("trajectories", "noise"), default="trajectories")
     args = ap.parse_args()
+    global NET, T
+    NET, T = args.net, 65536 if args.net == "noise" else T
     x = 1e-4 * torch.randn(B, T, device="cuda")
-    out = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "B": B, "T": T}
+    out = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "net": NET, "B": B, "T": T}
     hip, ref = trainer("hip"), trainer("torch")
     out["train_step_ms"] = {"hip": round(timed(lambda: hip.train_step(x), args.reps), 4),
                             "torch": round(timed(lambda: ref.train_step(x), args.reps), 4)}
@@ -157,14 +197,15 @@ def main():
     print("device kernels per step:", out["kernels_per_step"], flush=True)
 
     # the split of the HIP step
-    spans, L, F = Spans(), _lib.lib(), training.ResBlockFn
-    saved = (F.forward, F.backward, L.ntm_unet_wgrad_reduce)
-    F.forward, F.backward = staticmethod(spans.wrap("forward", saved[0])), staticmethod(spans.wrap("backward", saved[1]))
-    L.ntm_unet_wgrad_reduce = spans.wrap("reduce", saved[2])
-    nodes = (training.DownCombineFn, training.UpCombineFn)
+    spans, L = Spans(), _lib.lib()
+    saved_reduce = L.ntm_unet_wgrad_reduce
+    L.ntm_unet_wgrad_reduce = spans.wrap("reduce", saved_reduce)
+    blocks, resamples = (training.ResBlockFn, training.ResBlockTiledFn), (training.DownCombineFn, training.UpCombineFn)
+    nodes = blocks + resamples
     saved_nodes = [(N.forward, N.backward) for N in nodes]
     for N, (fw, bw) in zip(nodes, saved_nodes):
-        N.forward, N.backward = staticmethod(spans.wrap("resample_forward", fw)), staticmethod(spans.wrap("resample_backward", bw))
+        pre = "" if N in blocks else "resample_"
+        N.forward, N.backward = staticmethod(spans.wrap(pre + "forward", fw)), staticmethod(spans.wrap(pre + "backward", bw))
     try:
         rows = []
         for _ in range(args.reps):
@@ -176,7 +217,7 @@ def main():
             row["step"] = e0.elapsed_time(e1)
             rows.append(row)
     finally:
-        F.forward, F.backward, L.ntm_unet_wgrad_reduce = staticmethod(saved[0]), staticmethod(saved[1]), saved[2]
+        L.ntm_unet_wgrad_reduce = saved_reduce
         for N, (fw, bw) in zip(nodes, saved_nodes):
             N.forward, N.backward = staticmethod(fw), staticmethod(bw)
     med = {k: statistics.median(r[k] for r in rows) for k in rows[0]}
@@ -184,9 +225,13 @@ def main():
     out["hip_step_split_ms"] = {k: round(v, 4) for k, v in med.items()}
     print("split of the HIP step (with the events' own cost):", out["hip_step_split_ms"], flush=True)
 
+    if NET == "noise":
+        out["unet_kernel_ms_per_step"] = kernel_ms_of(lambda: hip.train_step(x))
+        print("device time of the step's unet kernels, by name:", out["unet_kernel_ms_per_step"], flush=True)
+
     # one block, forward + backward, at each level's frames
     out["block_ms"] = {}
-    for frames in (512, 256, 128, 32):
+    for frames in ((4096, 16384, 65536) if NET == "noise" else (512, 256, 128, 32)):
         torch.manual_seed(frames)
         blk = diffusion.ResnetBlock(32, 16, 16).cuda()
         x0, x1 = (torch.randn(B, 16, frames, device="cuda", requires_grad=True) for _ in range(2))
@@ -194,7 +239,8 @@ def main():
 
         def node():
             w = torch.stack([h.conv.weight for h in blk.H])
-            y = training.ResBlockFn.apply(x0, x1, blk.film.output_layer(emb), blk.first_conv[1].weight, w, blk.res_conv.weight, None, 0)
+            fn = training.ResBlockTiledFn if frames > diffusion.WHOLE_MAX_T else training.ResBlockFn
+            y = fn.apply(x0, x1, blk.film.output_layer(emb), blk.first_conv[1].weight, w, blk.res_conv.weight, None, 0)
             y.backward(gout)
 
         def module():
@@ -202,7 +248,7 @@ def main():
 
         a, b = timed(node, args.reps), timed(module, args.reps)
         out["block_ms"][frames] = {"hip": round(a, 4), "torch": round(b, 4), "speedup": round(b / a, 2)}
-        print(f"block 16+16->16, {frames:4d} frames, forward + backward  HIP {a:.3f} ms   torch {b:.3f} ms   x{b / a:.2f}", flush=True)
+        print(f"block 16+16->16, {frames:5d} frames, forward + backward  HIP {a:.3f} ms   torch {b:.3f} ms   x{b / a:.2f}", flush=True)
     print(json.dumps(out))
 
 
