@@ -912,6 +912,52 @@ int ntm_unet_up_combine_backward(const float *x, const float *ker, const float *
                                  int C, int64_t F, int S, int width, int taps, int64_t pyr_T, float *g_x, float *g_pyr,
                                  float *partials, void *stream);
 
+/*
+ * The optimiser step over a list of tensors (csrc/multi_tensor.hip): the total gradient norm and clip coefficient of
+ * torch.nn.utils.clip_grad_norm_, torch.optim.Adam's single-tensor step, and the EMA dst = dst s + src (1 - s) of the diffusion
+ * trainer.  Additions within ABI version 9.  Every list (p, g, m, v, dst, src) is a HOST array of `count` device pointers to
+ * contiguous fp32 tensors, n the host array of their element counts; a tensor of zero elements is skipped (its pointers are not
+ * read).  A launch serves up to NTM_MULTI_MAX_TENSORS tensors -- their pointers, sizes and chunk map travel by value in the kernel
+ * arguments, so nothing is copied to the device and the arrays may be freed on return -- and a longer list is cut into
+ * ceil(tensors / NTM_MULTI_MAX_TENSORS) launches here (tensors: those with n > 0).  One 256-thread workgroup per chunk of
+ * NTM_MULTI_CHUNK elements of one tensor; 16-byte accesses where all of a tensor's base pointers are 16-byte aligned, the same
+ * elements one by one otherwise, with the same bits either way.  Nothing synchronises with the host.
+ *
+ * ntm_multi_partials(n, count) = sum_k ceil(n[k] / NTM_MULTI_CHUNK): the doubles ntm_multi_sqnorm writes; -1 on what it refuses.
+ * ntm_multi_sqnorm: partials[c] = the sum of g^2 over chunk c, chunks numbered through the whole list in list order.  fp64 in a
+ *     fixed order: thread i of 256 adds the elements 4 (i + 256 r) ... + 3, r ascending; then a halving tree over the 256 sums.
+ *     *n_partials_out (may be NULL) = ntm_multi_partials(n, count).  Calls on several lists may fill one partials array side by
+ *     side (offset the pointer); ntm_multi_clip_coef then takes the norm over all of them.
+ * ntm_multi_clip_coef: one workgroup adds partials[0 .. n_partials) in index order in fp64 and writes
+ *     norm_coef[0] = (float)sqrt(sum),  norm_coef[1] = (float)min(1, max_norm / (sqrt(sum) + 1e-6))
+ *     -- clip_grad_norm_ with error_if_nonfinite=False: a non-finite norm goes into the coefficient (a NaN stays a NaN) and from
+ *     there into the parameters; no host check.  n_partials == 0: the norm of nothing, 0.
+ * ntm_multi_adam: per element, every operation rounded to fp32 on its own (no fused multiply-add, IEEE division and square root),
+ *     in torch's order:
+ *         g' = g coef                                     coef = norm_coef[1]; g' is written back to g.  norm_coef == NULL: g' = g,
+ *                                                         g is not written
+ *         m' = m + (1 - beta1) (g' - m)                   for 1 - beta1 < 0.5; else g' - (g' - m) (1 - (1 - beta1)): ATen's lerp
+ *         v' = beta2 v + ((1 - beta2) g') g'
+ *         p' = p + (-step_size) (m' / (sqrtf(v') / bc2_sqrt + eps))
+ *     with step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) formed by the caller in double and rounded to fp32 at
+ *     the call, like one_minus_beta1 and one_minus_beta2 -- what torch does with its Python scalars.
+ * ntm_multi_ema: dst' = dst s + src one_minus_s: two rounded products, one rounded sum (dst == src is allowed).
+ *   No atomics: equal calls give equal bits, and a tensor's results do not depend on the list it is in (the norm aside).
+ *   Refused (NTM_EINVAL, a message starting with the function's name, before anything touches a device): count < 0, a NULL list or
+ *   n with count > 0, n[k] < 0 or above 2^32, a NULL tensor pointer with n[k] > 0, p, m and v of one tensor not all distinct
+ *   (ntm_multi_adam), NULL partials with chunks to write, a NULL norm_coef or n_partials < 0 (ntm_multi_clip_coef).  count == 0
+ *   returns NTM_OK.
+ */
+#define NTM_MULTI_MAX_TENSORS 64
+#define NTM_MULTI_CHUNK 2048
+int64_t ntm_multi_partials(const int64_t *n, int64_t count);
+int ntm_multi_sqnorm(const float *const *g, const int64_t *n, int64_t count, double *partials, int64_t *n_partials_out, void *stream);
+int ntm_multi_clip_coef(const double *partials, int64_t n_partials, float max_norm, float *norm_coef, void *stream);
+int ntm_multi_adam(float *const *p, float *const *g, float *const *m, float *const *v, const int64_t *n, int64_t count,
+                   const float *norm_coef, float step_size, float bc2_sqrt, float one_minus_beta1, float beta2, float one_minus_beta2,
+                   float eps, void *stream);
+int ntm_multi_ema(float *const *dst, const float *const *src, const int64_t *n, int64_t count, float s, float one_minus_s, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

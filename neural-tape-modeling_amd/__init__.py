@@ -6,7 +6,8 @@ Layout:  csrc/ (HIP kernels + C ABI -> libntm.so), model.py (reference object pr
 epoch.py (the reference's TBPTT epoch, validation and predict-segment loops, once for single models and Replicas), utilities.py (name parsers), weights.py (exported checkpoints), harness.py (test-model.py loss loop),
 distributed.py (stream sharding + the one RCCL all-reduce), critics.py (the adversarial run's critics: MultiSpecCrit on the
 spectrogram, DilatedConvDisc on the waveform), adversarial.py (the adversarial run's configurations and training loop),
-evaluation.py (its validation metric bundle), diffusion.py (the diffusion generators: UNet1D and the EDM sampler).
+evaluation.py (its validation metric bundle), diffusion.py (the diffusion generators: UNet1D and the EDM sampler),
+optim.py (the optimiser step on the device: FusedAdam with the gradient clip, and the EMA).
 """
 from . import _lib  # noqa: F401
 from ._lib import NtmError, build  # noqa: F401
@@ -15,9 +16,10 @@ from .model import (RNN, DCPreESR, DiffDelRNN, ESRLoss, MRSTFTLoss, Replicas, Ti
 from .tape import Tape, TapeMagnetization  # noqa: F401
 from .tcn import TCN  # noqa: F401
 from .utilities import nextpow2, parse_hidden_size, parse_loss, parse_model  # noqa: F401
-from . import adversarial, critics, diffusion, distributed, epoch, evaluation, feeder, harness, weights  # noqa: F401
+from . import adversarial, critics, diffusion, distributed, epoch, evaluation, feeder, harness, optim, weights  # noqa: F401
 from .diffusion import DiffusionGenerator, EDMTrainer, UNet1D, load_config  # noqa: F401
+from .optim import FusedAdam, ema_update_  # noqa: F401
 
 __all__ = ["RNN", "DiffDelRNN", "Replicas", "TimeVaryingDelayLine", "TCN", "Tape", "TapeMagnetization", "ESRLoss", "DCPreESR", "MRSTFTLoss", "ValLossSupervised", "TimeFreqConverter", "stft_sums", "spec_sums", "mel_sums", "esr_dcpre_sums", "esr_sums", "esr_per_segment",
            "parse_hidden_size", "parse_model", "parse_loss", "nextpow2", "weights", "critics", "adversarial", "evaluation", "build", "NtmError",
-           "diffusion", "UNet1D", "DiffusionGenerator", "EDMTrainer", "load_config"]
+           "diffusion", "UNet1D", "DiffusionGenerator", "EDMTrainer", "load_config", "optim", "FusedAdam", "ema_update_"]

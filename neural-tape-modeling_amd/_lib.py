@@ -106,6 +106,13 @@ _SIGNATURES = {
     "ntm_unet_upsample": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "ntm_edm_pre": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64, _vp, _vp, _vp]),
     "ntm_edm_post": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i64, _vp, _vp]),
+    # the optimiser step over a list of tensors (additions within ABI version 9): p / g / m / v / dst / src are host arrays of
+    # device pointers (ptr_array), n a host int64 array (i64_array)
+    "ntm_multi_partials": (_i64, [_vp, _i64]),
+    "ntm_multi_sqnorm": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "ntm_multi_clip_coef": (_int, [_vp, _i64, ctypes.c_float, _vp, _vp]),
+    "ntm_multi_adam": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp] + [ctypes.c_float] * 6 + [_vp]),
+    "ntm_multi_ema": (_int, [_vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, _vp]),
 }
 # the three critic conv stacks (additions within ABI version 9): the spectral critics (layers: ConvLayer[n], the float is the log
 # floor), the dilated stack of the time-domain critic (ConvLayerD[n]) and the strided stack of the MelGAN critic (ConvLayerS[n]; for
@@ -117,6 +124,7 @@ for _p in ("speccrit", "convstack", "sconvstack"):
     _SIGNATURES[f"ntm_{_p}_backward"] = (_int, [_vp, _i64, _i64, _i64, ctypes.c_float, _int] + [_vp] * (12 if _p == "sconvstack" else 11))
 ADV_HEAD_MODES = {"crit": 0, "gen": 1}      # include/ntm.h NTM_ADV_HEAD_CRIT / NTM_ADV_HEAD_GEN
 ADV_HEAD_MAX_K, ADV_HEAD_CHUNK = 8, 4096    # include/ntm.h NTM_ADV_HEAD_MAX_K, NTM_ADV_HEAD_CHUNK
+MULTI_MAX_TENSORS, MULTI_CHUNK = 64, 2048   # include/ntm.h NTM_MULTI_MAX_TENSORS, NTM_MULTI_CHUNK
 
 
 class ConvLayer(ctypes.Structure):

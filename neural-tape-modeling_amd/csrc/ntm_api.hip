@@ -1584,4 +1584,128 @@ int ntm_adv_head_backward(const float *const *outs, const int64_t *elems, int K,
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_adv_head_backward");
 }
 
+// ---- the optimiser step over a list of tensors (multi_tensor.hip) ----
+extern "C++" {      // templates
+constexpr int64_t kMultiMaxFloats = (int64_t)1 << 32;       // per tensor: 2^21 chunks
+constexpr int64_t kMultiMaxGrid = (int64_t)1 << 23;         // workgroups per launch: 2^31 threads, below HIP's 2^32 per dimension
+
+static int64_t multi_chunks(int64_t n)
+{
+    return (n + NTM_MULTI_CHUNK - 1) / NTM_MULTI_CHUNK;
+}
+
+// what every ntm_multi entry point checks of its NP lists of `count` device pointers and of n, all before a device is touched
+template <int NP>
+struct MultiLists {
+    const void *const *l[NP];
+    const void *const *operator[](int j) const { return l[j]; }
+};
+
+template <int NP>
+static int multi_check(const std::string &w, const MultiLists<NP> &lists, const int64_t *n, int64_t count)
+{
+    if (count < 0) return fail(NTM_EINVAL, w + ": negative count");
+    if (count == 0) return NTM_OK;
+    if (!n) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int j = 0; j < NP; ++j)
+        if (!lists[j]) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int64_t i = 0; i < count; ++i) {
+        if (n[i] < 0) return fail(NTM_EINVAL, w + ": negative size (tensor " + std::to_string(i) + ")");
+        if (n[i] > kMultiMaxFloats) return fail(NTM_EINVAL, w + ": a tensor must hold at most 2^32 floats");
+        for (int j = 0; j < NP; ++j)
+            if (n[i] > 0 && !lists[j][i]) return fail(NTM_EINVAL, w + ": null pointer (tensor " + std::to_string(i) + ")");
+    }
+    return NTM_OK;
+}
+
+// cuts the checked lists into tables of at most NTM_MULTI_MAX_TENSORS tensors (and kMultiMaxGrid workgroups) and hands each,
+// with the number of chunks before it, to `go`; tensors of zero elements are skipped
+template <int NP, class F>
+static hipError_t multi_walk(const MultiLists<NP> &lists, const int64_t *n, int64_t count, F &&go)
+{
+    ntm::MultiTable<NP> t{};
+    int64_t base = 0;
+    for (int64_t i = 0; i <= count; ++i) {
+        const int64_t c = i < count ? multi_chunks(n[i]) : 0;
+        const bool full = t.count == NTM_MULTI_MAX_TENSORS || t.first[t.count] + c > kMultiMaxGrid;
+        if (t.count > 0 && (i == count || (c > 0 && full))) {
+            hipError_t e = go(t, base);
+            if (e != hipSuccess) return e;
+            base += t.first[t.count];
+            t = ntm::MultiTable<NP>{};
+        }
+        if (c == 0) continue;
+        for (int j = 0; j < NP; ++j) t.ptr[j][t.count] = const_cast<void *>(lists[j][i]);
+        t.n[t.count] = n[i];
+        t.first[t.count + 1] = t.first[t.count] + (int32_t)c;
+        ++t.count;
+    }
+    return hipSuccess;
+}
+
+}  // extern "C++"
+
+int64_t ntm_multi_partials(const int64_t *n, int64_t count)
+{
+    if (count < 0 || (count > 0 && !n)) return -1;
+    int64_t total = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        if (n[i] < 0 || n[i] > kMultiMaxFloats) return -1;
+        total += multi_chunks(n[i]);
+    }
+    return total;
+}
+
+int ntm_multi_sqnorm(const float *const *g, const int64_t *n, int64_t count, double *partials, int64_t *n_partials_out, void *stream)
+{
+    const std::string w("ntm_multi_sqnorm");
+    const MultiLists<1> lists{{(const void *const *)g}};
+    if (int rc = multi_check(w, lists, n, count)) return rc;
+    const int64_t total = ntm_multi_partials(n, count);
+    if (total > 0 && !partials) return fail(NTM_EINVAL, w + ": null pointer (partials)");
+    hipError_t e = multi_walk(lists, n, count, [&](const ntm::MultiTable<1> &t, int64_t base) {
+        return ntm::launch_multi_sqnorm(t, partials, base, (hipStream_t)stream);
+    });
+    if (e != hipSuccess) return hip_fail(e, "ntm_multi_sqnorm");
+    if (n_partials_out) *n_partials_out = total;
+    return NTM_OK;
+}
+
+int ntm_multi_clip_coef(const double *partials, int64_t n_partials, float max_norm, float *norm_coef, void *stream)
+{
+    const std::string w("ntm_multi_clip_coef");
+    if (n_partials < 0) return fail(NTM_EINVAL, w + ": negative size");
+    if (!norm_coef || (n_partials > 0 && !partials)) return fail(NTM_EINVAL, w + ": null pointer");
+    hipError_t e = ntm::launch_multi_norm_finalize(partials, n_partials, max_norm, norm_coef, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_multi_clip_coef");
+}
+
+int ntm_multi_adam(float *const *p, float *const *g, float *const *m, float *const *v, const int64_t *n, int64_t count,
+                   const float *norm_coef, float step_size, float bc2_sqrt, float one_minus_beta1, float beta2, float one_minus_beta2,
+                   float eps, void *stream)
+{
+    const std::string w("ntm_multi_adam");
+    const MultiLists<4> lists{{(const void *const *)p, (const void *const *)g, (const void *const *)m, (const void *const *)v}};
+    if (int rc = multi_check(w, lists, n, count)) return rc;
+    for (int64_t i = 0; i < count; ++i)
+        if (n[i] > 0 && (p[i] == m[i] || p[i] == v[i] || m[i] == v[i]))
+            return fail(NTM_EINVAL, w + ": p, m and v of a tensor must not alias (tensor " + std::to_string(i) + ")");
+    const ntm::MultiAdamScalars s{-step_size, bc2_sqrt, one_minus_beta1, beta2, one_minus_beta2, eps};
+    hipError_t e = multi_walk(lists, n, count, [&](const ntm::MultiTable<4> &t, int64_t) {
+        return ntm::launch_multi_adam(t, norm_coef, s, (hipStream_t)stream);
+    });
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_multi_adam");
+}
+
+int ntm_multi_ema(float *const *dst, const float *const *src, const int64_t *n, int64_t count, float s, float one_minus_s, void *stream)
+{
+    const std::string w("ntm_multi_ema");
+    const MultiLists<2> lists{{(const void *const *)dst, (const void *const *)src}};
+    if (int rc = multi_check(w, lists, n, count)) return rc;
+    hipError_t e = multi_walk(lists, n, count, [&](const ntm::MultiTable<2> &t, int64_t) {
+        return ntm::launch_multi_ema(t, s, one_minus_s, (hipStream_t)stream);
+    });
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_multi_ema");
+}
+
 }  // extern "C"

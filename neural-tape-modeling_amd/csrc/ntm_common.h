@@ -158,6 +158,22 @@ struct AdvHeadArgs {
 int64_t adv_head_chunks(const AdvHeadArgs &a);   // chunks of the longest half: the first grid dimension, the row length of ws
 hipError_t launch_adv_head_forward(const AdvHeadArgs &a, double *ws, float *loss, hipStream_t stream);
 hipError_t launch_adv_head_backward(const AdvHeadArgs &a, const float *gout, hipStream_t stream);
+// the optimiser step over a list of tensors (multi_tensor.hip): one launch's table, passed by value.  ptr[j][k]: pointer j of
+// tensor k (sqnorm: g; ema: dst, src; adam: p, g, m, v), n[k] > 0 its floats, first[k] its first workgroup, first[count] the grid
+template <int NP>
+struct MultiTable {
+    void *ptr[NP][NTM_MULTI_MAX_TENSORS];
+    int64_t n[NTM_MULTI_MAX_TENSORS];
+    int32_t first[NTM_MULTI_MAX_TENSORS + 1];
+    int32_t count;
+};
+struct MultiAdamScalars {
+    float neg_step_size, bc2_sqrt, one_minus_beta1, beta2, one_minus_beta2, eps;
+};
+hipError_t launch_multi_sqnorm(const MultiTable<1> &t, double *partials, int64_t base, hipStream_t stream);
+hipError_t launch_multi_norm_finalize(const double *partials, int64_t n, float max_norm, float *norm_coef, hipStream_t stream);
+hipError_t launch_multi_adam(const MultiTable<4> &t, const float *norm_coef, const MultiAdamScalars &s, hipStream_t stream);
+hipError_t launch_multi_ema(const MultiTable<2> &t, float s, float one_minus_s, hipStream_t stream);
 // the diffusion generators' network and sampler step (unet_kernels.hip); the sizes are checked by ntm_api.hip
 int unet_block_launches(const ntm_unet_block &k);
 int64_t unet_block_workspace(int64_t B, const ntm_unet_block &k);

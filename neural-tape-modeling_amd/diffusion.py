@@ -35,7 +35,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, optim
 
 SUPPORTED = "fp32 on a HIP device, Nin = 1, c_in <= 32, c_out <= 16, at most 8 gated layers, use_norm = False"
 WHOLE_MAX_T, TILE = 1024, 512      # include/ntm.h NTM_UNET_WHOLE_MAX_T, NTM_UNET_TILE
@@ -932,6 +932,8 @@ class EDMTrainer:
     Trainer.train_step / update_ema, :377-430) on a UNet1D of this module.
     backend "hip": the network runs UNet1D.forward_train (HIP device only); "torch": forward_torch, any device and dtype.
     draws = (a, noise) stands in for the step's torch.rand(B) and torch.randn(B, T), so that a recorded run can be replayed.
+    With an optim.FusedAdam the gradient clip, the Adam step and the EMA run as launches over lists of tensors (optim.py);
+    with any other optimizer they are torch's, as in the reference.
     The reference's prints, its dataset, hydra and logging code and a command-line driver are not here: the caller hands
     train_step its batch (B, T) and counts with `iteration`."""
 
@@ -996,9 +998,12 @@ class EDMTrainer:
                 g["lr"] = train.lr * min(self.it / max(train.lr_rampup_it, 1e-8), 1)
         self.lr = self.optimizer.param_groups[0]["lr"]
         self.grad_norm = None
-        if train.use_grad_clip:
-            self.grad_norm = torch.nn.utils.clip_grad_norm_(self.network.parameters(), train.max_grad_norm)
-        self.optimizer.step()
+        if isinstance(self.optimizer, optim.FusedAdam):      # the norm, the clip and the step as launches over lists of tensors
+            self.grad_norm = self.optimizer.step(max_grad_norm=train.max_grad_norm if train.use_grad_clip else None)
+        else:
+            if train.use_grad_clip:
+                self.grad_norm = torch.nn.utils.clip_grad_norm_(self.network.parameters(), train.max_grad_norm)
+            self.optimizer.step()
         if self.scheduler is not None:
             self.scheduler.step()
         return loss.detach()
@@ -1008,6 +1013,9 @@ class EDMTrainer:
         t = self.it * train.batch
         with torch.no_grad():
             s = np.clip(t / train.ema_rampup, 0.0, train.ema_rate) if t < train.ema_rampup else train.ema_rate
+            if isinstance(self.optimizer, optim.FusedAdam):
+                optim.ema_update_(self.ema.parameters(), self.network.parameters(), s)
+                return
             for dst, src in zip(self.ema.parameters(), self.network.parameters()):
                 dst.copy_(dst * s + src * (1 - s))
 

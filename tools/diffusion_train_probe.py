@@ -16,7 +16,15 @@ node); the split counts both block nodes, and where the profiler gives device ti
 name (its fixed-order sums run inside the C call, where no event of this script reaches); the block table is at 4 096, 16 384
 and 65 536 frames.
 
-Usage:  python tools/diffusion_train_probe.py [--reps 9] [--net trajectories|noise]
+--optimizer fused|torch: the optimiser of the HIP trainer in the sections above (torch.optim.Adam as in the reference, or
+optim.FusedAdam: the clip, the Adam step and the EMA as launches over lists of tensors, csrc/multi_tensor.hip).  Whatever it
+says, the optimiser section times train_step and iteration() (train_step + update_ema) with FusedAdam against torch.optim.Adam
+on the same EDMTrainer(backend="hip"), alternating in one process, the pair twice; counts the device kernels of both both ways
+and the fused optimiser's own launches against the formula 2 L + 1 (+ L for the EMA), L = ceil(tensors / NTM_MULTI_MAX_TENSORS);
+and reports whether one iteration leaves the weights and the EMA torch.equal to torch's own device ops, with and without the
+clip.  --only-optimizer: that section alone.
+
+Usage:  python tools/diffusion_train_probe.py [--reps 9] [--net trajectories|noise] [--optimizer fused|torch] [--only-optimizer]
 """
 import argparse
 import json
@@ -28,10 +36,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from ntm_amd import _lib, diffusion, training  # noqa: E402
+from ntm_amd import _lib, diffusion, optim, training  # noqa: E402
 
 B, T = 4, 512
 NET = "trajectories"
+OPTIMIZER = "torch"
 
 
 def timed(fn, reps, warmup=3):
@@ -49,8 +58,9 @@ def timed(fn, reps, warmup=3):
     return statistics.median(ms)
 
 
-def trainer(backend):
+def trainer(backend, optimizer=None, clip=True):
     args = diffusion.load_config(NET)
+    args.train.use_grad_clip = clip
     if NET == "noise":
         args.network.depth = 6        # the checkpoint's (weights/83)
     torch.manual_seed(11)
@@ -58,8 +68,9 @@ def trainer(backend):
     for m in net.modules():           # the reference starts these at zero, which would leave the blocks without a gradient
         if isinstance(m, diffusion.CombinerUp):
             torch.nn.init.kaiming_uniform_(m.conv1x1.weight, a=5 ** 0.5)
-    opt = torch.optim.Adam(net.parameters(), lr=args.train.lr, betas=(args.train.optimizer.beta1, args.train.optimizer.beta2),
-                           eps=args.train.optimizer.eps)
+    adam = optim.FusedAdam if (optimizer or OPTIMIZER) == "fused" and backend == "hip" else torch.optim.Adam
+    opt = adam(net.parameters(), lr=args.train.lr, betas=(args.train.optimizer.beta1, args.train.optimizer.beta2),
+               eps=args.train.optimizer.eps)
     tr = diffusion.EDMTrainer(args, net, opt, "cuda", backend=backend)
     tr.it = 500                       # inside the ramp-up, a non-zero learning rate
     return tr
@@ -127,6 +138,77 @@ def kernels_of(fn):
         return None
 
 
+def launches_of(fn, word="multi_"):
+    """Launches of the kernels whose name holds `word` in one call of fn, by name, or None where the profiler gives none."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        out = {}
+        for e in prof.events():
+            if str(e.device_type).endswith("CUDA") and word in e.name:
+                name = e.name.split("(")[0].split("::")[-1]
+                out[name] = out.get(name, 0) + 1
+        return out or None
+    except Exception as e:                                    # noqa: BLE001 -- a count, not a result
+        print(f"launch count: {type(e).__name__}: {e}", flush=True)
+        return None
+
+
+def optimizer_section(out, x, reps):
+    """FusedAdam against torch.optim.Adam on the same HIP trainer: times, kernel counts, launch formula, bit equality."""
+    fused, ref = trainer("hip", "fused"), trainer("hip", "torch")
+    tensors = sum(1 for p in fused.network.parameters() if p.requires_grad and p.numel())
+    L = -(-tensors // _lib.MULTI_MAX_TENSORS)
+    ema_tensors = sum(1 for p in fused.ema.parameters() if p.numel())
+    Le = -(-ema_tensors // _lib.MULTI_MAX_TENSORS)
+    res = {"tensors": tensors, "floats": sum(p.numel() for p in fused.network.parameters()), "L": L, "L_ema": Le}
+    for what in ("train_step", "iteration"):
+        pairs = [alternating(lambda: getattr(fused, what)(x), lambda: getattr(ref, what)(x), reps) for _ in range(2)]
+        spread = max(abs(pairs[0][0] - pairs[1][0]), abs(pairs[0][1] - pairs[1][1]))
+        gain = statistics.mean(p[1] for p in pairs) - statistics.mean(p[0] for p in pairs)
+        res[what + "_ms"] = {"pairs": [{"fused": round(a, 4), "torch": round(b, 4)} for a, b in pairs], "spread": round(spread, 4),
+                             "gain": round(gain, 4), "beyond_the_spread": bool(abs(gain) > spread)}
+        print(f"{what}: FusedAdam vs torch.optim.Adam, two alternating runs:", res[what + "_ms"], flush=True)
+        res[what + "_kernels"] = {"fused": kernels_of(lambda: getattr(fused, what)(x)), "torch": kernels_of(lambda: getattr(ref, what)(x))}
+        print(f"device kernels per {what}:", res[what + "_kernels"], flush=True)
+    res["fused_launches_per_iteration"] = launches_of(lambda: fused.iteration(x))
+    res["formula"] = {"clip + adam": 2 * L + 1, "ema": Le}
+    got = res["fused_launches_per_iteration"]
+    if got is None:
+        print("the profiler gives no device events here: the fused optimiser's launches are not counted", flush=True)
+    else:
+        res["formula_holds"] = sum(v for k, v in got.items() if "ema" not in k) == 2 * L + 1 and got.get("multi_ema_kernel", 0) == Le
+        print(f"fused optimiser launches per iteration: {got}; formula 2 L + 1 = {2 * L + 1}, EMA {Le}: "
+              f"{'holds' if res['formula_holds'] else 'DOES NOT HOLD'}", flush=True)
+    # one iteration from equal weights on equal draws: are the results torch.equal to torch's own device ops?
+    res["equal_to_torch"] = {}
+    for clip in (True, False):
+        a, b = trainer("hip", "fused", clip), trainer("hip", "torch", clip)
+        g = torch.Generator().manual_seed(5)
+        draws = (torch.rand(B, generator=g), torch.randn(B, T, generator=g))
+        for tr in (a, b):
+            tr.it = 1000                  # behind the EMA's ramp: s = ema_rate
+            tr.iteration(x, draws)
+        pa, pb = list(a.network.parameters()), list(b.network.parameters())
+        ea, eb = list(a.ema.parameters()), list(b.ema.parameters())
+        res["equal_to_torch"]["clip" if clip else "no clip"] = {
+            "weights": f"{sum(torch.equal(p, q) for p, q in zip(pa, pb))} of {len(pa)} tensors",
+            "ema": f"{sum(torch.equal(p, q) for p, q in zip(ea, eb))} of {len(ea)} tensors"}
+        # the EMA alone, on equal inputs
+        d1, d2 = [p.detach().clone() for p in eb], [p.detach().clone() for p in eb]
+        optim.ema_update_(d1, pb, 0.999)
+        with torch.no_grad():
+            for d, q in zip(d2, pb):
+                d.copy_(d * 0.999 + q * (1 - 0.999))
+        res["equal_to_torch"]["ema_update_ alone"] = f"{sum(torch.equal(p, q) for p, q in zip(d1, d2))} of {len(d1)} tensors"
+    print("torch.equal to torch's own device ops after one iteration:", res["equal_to_torch"], flush=True)
+    out["fused_vs_torch"] = res
+
+
 def kernel_ms_of(fn, word="unet_"):
     """Device milliseconds of one call of fn per kernel whose name holds `word`, or None where the profiler gives none."""
     try:
@@ -177,11 +259,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--net", choices=("trajectories", "noise"), default="trajectories")
+    ap.add_argument("--optimizer", choices=("fused", "torch"), default="torch")
+    ap.add_argument("--only-optimizer", action="store_true")
     args = ap.parse_args()
-    global NET, T
-    NET, T = args.net, 65536 if args.net == "noise" else T
+    global NET, T, OPTIMIZER
+    NET, T, OPTIMIZER = args.net, 65536 if args.net == "noise" else T, args.optimizer
     x = 1e-4 * torch.randn(B, T, device="cuda")
-    out = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "net": NET, "B": B, "T": T}
+    out = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "net": NET, "B": B, "T": T, "optimizer": OPTIMIZER}
+    optimizer_section(out, x, args.reps)
+    if args.only_optimizer:
+        print(json.dumps(out))
+        return
     hip, ref = trainer("hip"), trainer("torch")
     out["train_step_ms"] = {"hip": round(timed(lambda: hip.train_step(x), args.reps), 4),
                             "torch": round(timed(lambda: ref.train_step(x), args.reps), 4)}
