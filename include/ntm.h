@@ -958,6 +958,35 @@ int ntm_multi_adam(float *const *p, float *const *g, float *const *m, float *con
                    float eps, void *stream);
 int ntm_multi_ema(float *const *dst, const float *const *src, const int64_t *n, int64_t count, float s, float one_minus_s, void *stream);
 
+/*
+ * The batch feeder of the diffusion trainers (csrc/segment_feed.hip): what the reference's datasets_diffusion.py and
+ * Trainer.get_batch do per batch -- a random crop of a file, minus the crop's mean, resampled to the network's rate -- on a
+ * "bank" that lives on the device: every training file mixed to mono in fp32, concatenated, bank_len floats.  Additions within
+ * ABI version 9.  Row b is bank[start[b] .. start[b] + L); start is a HOST array of B first samples (offset of the file in the
+ * bank + the crop's index).  A launch serves up to NTM_SEGMENT_MAX_ROWS rows, whose starts travel by value in the kernel
+ * arguments: nothing is copied to the device, the array may be freed on return, and a larger B is cut into
+ * ceil(B / NTM_SEGMENT_MAX_ROWS) launches here.  Nothing synchronises with the host.
+ *
+ * ntm_segment_mean: mean[b] = (float)(sum / L), the sum in fp64 in a fixed order (thread i of 1024 adds x[i], x[i + 1024], ...
+ *     ascending; then lanes by shuffles and the 16 waves in wave order), rounded once.
+ * ntm_segment_crop: out[b][i] = x[i] - mean[b], one rounded fp32 subtraction (equal rates: the noise net).
+ * ntm_segment_decimate: torchaudio's polyphase rule for a reduced ratio orig : 1 with the filter ker[taps], taps == 2 width + orig:
+ *         out[b][j] = sum_k ker[k] xz[b][j orig + k - width],   j < ceil(L / orig),
+ *     xz = x - mean[b] inside [0, L) and exactly 0 outside (the padding is zeros, not -mean).  The crop, the subtraction and the
+ *     filter are one pass over the bank: no [B][L] intermediate.  One 256-thread workgroup per output; thread i takes the taps
+ *     i, i + 256, ... ascending, the difference and the product rounded to fp32 each, added in fp64; the same fixed tree joins them.
+ *   No atomics: equal calls give equal bits, and a row's result does not depend on the rows beside it.
+ *   Refused (NTM_EINVAL, a message starting with the function's name, before anything touches a device): a NULL pointer, B < 0,
+ *   L < 1, orig < 1, width < 0, taps != 2 width + orig, ceil(L / orig) above 2^31 - 1, and a row outside the bank
+ *   (start[b] < 0 or start[b] + L > bank_len).  B == 0 returns NTM_OK.
+ */
+#define NTM_SEGMENT_MAX_ROWS 64
+int ntm_segment_mean(const float *bank, int64_t bank_len, const int64_t *start, int64_t B, int64_t L, float *mean, void *stream);
+int ntm_segment_crop(const float *bank, int64_t bank_len, const int64_t *start, const float *mean, int64_t B, int64_t L, float *out,
+                     void *stream);
+int ntm_segment_decimate(const float *bank, int64_t bank_len, const int64_t *start, const float *mean, int64_t B, int64_t L,
+                         const float *ker, int orig, int width, int taps, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

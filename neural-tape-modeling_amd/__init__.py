@@ -7,7 +7,8 @@ epoch.py (the reference's TBPTT epoch, validation and predict-segment loops, onc
 distributed.py (stream sharding + the one RCCL all-reduce), critics.py (the adversarial run's critics: MultiSpecCrit on the
 spectrogram, DilatedConvDisc on the waveform), adversarial.py (the adversarial run's configurations and training loop),
 evaluation.py (its validation metric bundle), diffusion.py (the diffusion generators: UNet1D and the EDM sampler),
-optim.py (the optimiser step on the device: FusedAdam with the gradient clip, and the EMA).
+optim.py (the optimiser step on the device: FusedAdam with the gradient clip, and the EMA), datasets_diffusion.py (the
+diffusion trainers' dataset classes and the device batch feeder).
 """
 from . import _lib  # noqa: F401
 from ._lib import NtmError, build  # noqa: F401
@@ -16,7 +17,7 @@ from .model import (RNN, DCPreESR, DiffDelRNN, ESRLoss, MRSTFTLoss, Replicas, Ti
 from .tape import Tape, TapeMagnetization  # noqa: F401
 from .tcn import TCN  # noqa: F401
 from .utilities import nextpow2, parse_hidden_size, parse_loss, parse_model  # noqa: F401
-from . import adversarial, critics, diffusion, distributed, epoch, evaluation, feeder, harness, optim, weights  # noqa: F401
+from . import adversarial, critics, datasets_diffusion, diffusion, distributed, epoch, evaluation, feeder, harness, optim, weights  # noqa: F401
 from .diffusion import DiffusionGenerator, EDMTrainer, UNet1D, load_config  # noqa: F401
 from .optim import FusedAdam, ema_update_  # noqa: F401
 

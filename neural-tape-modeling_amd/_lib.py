@@ -113,6 +113,11 @@ _SIGNATURES = {
     "ntm_multi_clip_coef": (_int, [_vp, _i64, ctypes.c_float, _vp, _vp]),
     "ntm_multi_adam": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp] + [ctypes.c_float] * 6 + [_vp]),
     "ntm_multi_ema": (_int, [_vp, _vp, _vp, _i64, ctypes.c_float, ctypes.c_float, _vp]),
+    # the batch feeder of the diffusion trainers (additions within ABI version 9): bank, bank_len, start (a host int64 array,
+    # i64_array), ...
+    "ntm_segment_mean": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "ntm_segment_crop": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "ntm_segment_decimate": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp]),
 }
 # the three critic conv stacks (additions within ABI version 9): the spectral critics (layers: ConvLayer[n], the float is the log
 # floor), the dilated stack of the time-domain critic (ConvLayerD[n]) and the strided stack of the MelGAN critic (ConvLayerS[n]; for

@@ -1708,4 +1708,75 @@ int ntm_multi_ema(float *const *dst, const float *const *src, const int64_t *n, 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_multi_ema");
 }
 
+// ---- the batch feeder of the diffusion trainers (segment_feed.hip) ----
+extern "C++" {
+
+// every row is checked before anything is launched
+static int segment_check(const std::string &w, const float *bank, int64_t bank_len, const int64_t *start, int64_t B, int64_t L)
+{
+    if (B < 0) return fail(NTM_EINVAL, w + ": negative B");
+    if (L < 1) return fail(NTM_EINVAL, w + ": L must be positive");
+    if (!bank || !start) return fail(NTM_EINVAL, w + ": null pointer");
+    for (int64_t b = 0; b < B; ++b)
+        if (start[b] < 0 || bank_len < L || start[b] > bank_len - L)
+            return fail(NTM_EINVAL, w + ": row " + std::to_string(b) + " lies outside the bank");
+    return NTM_OK;
+}
+
+// the rows in launches of at most NTM_SEGMENT_MAX_ROWS; go(starts, first row, rows)
+template <class F>
+static hipError_t segment_walk(const int64_t *start, int64_t B, F &&go)
+{
+    for (int64_t b0 = 0; b0 < B; b0 += NTM_SEGMENT_MAX_ROWS) {
+        const int rows = (int)(B - b0 < NTM_SEGMENT_MAX_ROWS ? B - b0 : NTM_SEGMENT_MAX_ROWS);
+        ntm::SegStarts st{};
+        for (int r = 0; r < rows; ++r) st.s[r] = start[b0 + r];
+        hipError_t e = go(st, b0, rows);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // extern "C++"
+
+int ntm_segment_mean(const float *bank, int64_t bank_len, const int64_t *start, int64_t B, int64_t L, float *mean, void *stream)
+{
+    const std::string w("ntm_segment_mean");
+    if (!mean) return fail(NTM_EINVAL, w + ": null pointer");
+    if (int rc = segment_check(w, bank, bank_len, start, B, L)) return rc;
+    hipError_t e = segment_walk(start, B, [&](const ntm::SegStarts &st, int64_t b0, int rows) {
+        return ntm::launch_segment_mean(bank, st, rows, L, mean + b0, (hipStream_t)stream);
+    });
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_segment_mean");
+}
+
+int ntm_segment_crop(const float *bank, int64_t bank_len, const int64_t *start, const float *mean, int64_t B, int64_t L, float *out,
+                     void *stream)
+{
+    const std::string w("ntm_segment_crop");
+    if (!mean || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    if (int rc = segment_check(w, bank, bank_len, start, B, L)) return rc;
+    hipError_t e = segment_walk(start, B, [&](const ntm::SegStarts &st, int64_t b0, int rows) {
+        return ntm::launch_segment_crop(bank, st, mean + b0, rows, L, out + b0 * L, (hipStream_t)stream);
+    });
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_segment_crop");
+}
+
+int ntm_segment_decimate(const float *bank, int64_t bank_len, const int64_t *start, const float *mean, int64_t B, int64_t L,
+                         const float *ker, int orig, int width, int taps, float *out, void *stream)
+{
+    const std::string w("ntm_segment_decimate");
+    if (!mean || !ker || !out) return fail(NTM_EINVAL, w + ": null pointer");
+    if (orig < 1) return fail(NTM_EINVAL, w + ": orig must be positive");
+    if (width < 0 || (int64_t)taps != 2 * (int64_t)width + orig) return fail(NTM_EINVAL, w + ": taps must be 2 width + orig, width >= 0");
+    if (int rc = segment_check(w, bank, bank_len, start, B, L)) return rc;
+    const int64_t n_out = (L + orig - 1) / orig;
+    if (n_out > 0x7fffffff) return fail(NTM_EINVAL, w + ": ceil(L / orig) must be below 2^31");
+    hipError_t e = segment_walk(start, B, [&](const ntm::SegStarts &st, int64_t b0, int rows) {
+        return ntm::launch_segment_decimate(bank, st, mean + b0, rows, L, ker, orig, width, taps, n_out, out + b0 * n_out,
+                                            (hipStream_t)stream);
+    });
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_segment_decimate");
+}
+
 }  // extern "C"

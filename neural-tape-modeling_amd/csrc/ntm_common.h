@@ -174,6 +174,15 @@ hipError_t launch_multi_sqnorm(const MultiTable<1> &t, double *partials, int64_t
 hipError_t launch_multi_norm_finalize(const double *partials, int64_t n, float max_norm, float *norm_coef, hipStream_t stream);
 hipError_t launch_multi_adam(const MultiTable<4> &t, const float *norm_coef, const MultiAdamScalars &s, hipStream_t stream);
 hipError_t launch_multi_ema(const MultiTable<2> &t, float s, float one_minus_s, hipStream_t stream);
+// the batch feeder of the diffusion trainers (segment_feed.hip): the first bank sample of each row of one launch, passed by value
+struct SegStarts {
+    int64_t s[NTM_SEGMENT_MAX_ROWS];
+};
+hipError_t launch_segment_mean(const float *bank, const SegStarts &st, int rows, int64_t L, float *mean, hipStream_t stream);
+hipError_t launch_segment_crop(const float *bank, const SegStarts &st, const float *mean, int rows, int64_t L, float *out,
+                               hipStream_t stream);
+hipError_t launch_segment_decimate(const float *bank, const SegStarts &st, const float *mean, int rows, int64_t L, const float *ker,
+                                   int orig, int width, int taps, int64_t n_out, float *out, hipStream_t stream);
 // the diffusion generators' network and sampler step (unet_kernels.hip); the sizes are checked by ntm_api.hip
 int unet_block_launches(const ntm_unet_block &k);
 int64_t unet_block_workspace(int64_t B, const ntm_unet_block &k);

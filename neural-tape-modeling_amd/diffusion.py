@@ -24,6 +24,7 @@ The sampler and `forward` are inference only.  Two additions to the reference's 
            given per stream every stream equals its own sample() bit for bit.
 """
 import copy
+import glob
 import math
 import os
 import pickle
@@ -934,14 +935,22 @@ class EDMTrainer:
     draws = (a, noise) stands in for the step's torch.rand(B) and torch.randn(B, T), so that a recorded run can be replayed.
     With an optim.FusedAdam the gradient clip, the Adam step and the EMA run as launches over lists of tensors (optim.py);
     with any other optimizer they are torch's, as in the reference.
-    The reference's prints, its dataset, hydra and logging code and a command-line driver are not here: the caller hands
-    train_step its batch (B, T) and counts with `iteration`."""
+    Either the caller hands train_step its batch (B, T) and counts with `iteration`, or dset= supplies the batches and
+    training_loop runs the reference's loop (:431-443) with its checkpoints (:277-364).  dset is what the reference's Trainer
+    takes -- an iterator of (B, seg_len) segments at the dataset's rate, which get_batch moves to the device and resamples (:366-375)
+    -- or an object with next_batch() (datasets_diffusion.DeviceSegmentFeeder) that returns the finished batch.
+    load_state_dict builds attempts 1 and 2 of utilities/training_utils.load_state_dict (strict; then strict=False without the
+    optimizer); its attempts 3 to 7 and the last resort, which serve the checkpoint layouts of other projects, are not built: a
+    checkpoint that both attempts refuse raises.
+    The reference's prints and its hydra and logging code are not here; the command line is tools/train_diffusion.py."""
 
-    def __init__(self, args, network, optimizer, device, backend="hip", scheduler=None):
+    def __init__(self, args, network, optimizer, device, backend="hip", scheduler=None, dset=None):
         if backend not in ("hip", "torch"):
             raise ValueError(f"EDMTrainer: backend {backend!r}; built: 'hip' and 'torch'")
         self.args, self.network, self.optimizer, self.device, self.backend = args, network, optimizer, device, backend
-        self.scheduler = scheduler
+        self.scheduler, self.dset = scheduler, dset
+        self.latest_checkpoint = None
+        self._resample = None
         dp = args.diff_params
         self.sigma_min, self.sigma_max, self.ro, self.sigma_data = dp.sigma_min, dp.sigma_max, dp.ro, dp.sigma_data
         network._packed, network._plans = None, {}        # caches of bound launches: not state, and not copyable
@@ -1030,3 +1039,89 @@ class EDMTrainer:
         """The reference's checkpoint: DiffusionGenerator loads its "ema"."""
         return {"it": self.it, "network": self.network.state_dict(), "optimizer": self.optimizer.state_dict(),
                 "ema": self.ema.state_dict(), "args": self.args}
+
+    # -- the loop, its batches and its checkpoints --
+    def get_batch(self):
+        """The next batch (B, T) float32 on the device: next(dset), moved and resampled from args.dset.fs to args.exp.sample_rate
+        by torchaudio's rule (the filter is built once here; torchaudio rebuilds it per call), or dset.next_batch()."""
+        if self.dset is None:
+            raise RuntimeError("EDMTrainer.get_batch: no dset= was given")
+        if hasattr(self.dset, "next_batch"):
+            return self.dset.next_batch()
+        audio = torch.as_tensor(next(self.dset)).to(self.device).to(torch.float32)
+        o, n = int(self.args.dset.fs), int(self.args.exp.sample_rate)
+        if o == n:
+            return audio
+        if self._resample is None:
+            k, w = sinc_resample_kernel(o, n)
+            g = math.gcd(o, n)
+            self._resample = (k.to(self.device), w, o // g, n // g)
+        k, w, o, n = self._resample
+        return apply_resample_kernel(audio, k, o, n, w)
+
+    def training_loop(self, max_it=None, log=None):
+        """The reference's loop: train_step, update_ema, the checkpoint condition, it += 1.  The reference never returns; here
+        max_it is the last iteration number that runs (None: for ever), so that a checkpoint due at max_it is still written.
+        log(it, loss), if given, is called after every step with the detached loss (reading it synchronises)."""
+        train = self.args.train
+        while max_it is None or self.it <= max_it:
+            loss = self.train_step(self.get_batch())
+            self.update_ema()
+            if log is not None:
+                log(self.it, loss)
+            if self.it > 0 and self.it % train.save_interval == 0 and train.save_model:
+                self.save_checkpoint()
+            self.it += 1
+
+    def save_checkpoint(self):
+        """{model_dir}/{exp_name}-{it}.pt; with args.logging.remove_last_checkpoint the file this trainer wrote before goes.
+        (The reference's configurations have no `logging` section, and its save_checkpoint fails on them after the file is
+        written; here a missing section reads as "keep".)"""
+        save_name = f"{self.args.model_dir}/{self.args.exp.exp_name}-{self.it}.pt"
+        torch.save(self.state_dict(), save_name)
+        if (self.args.get("logging") or {}).get("remove_last_checkpoint"):
+            try:
+                os.remove(self.latest_checkpoint)
+            except (OSError, TypeError):          # nothing written yet (None), or already gone: as the reference, go on
+                pass
+        self.latest_checkpoint = save_name
+        return save_name
+
+    def load_state_dict(self, sd):
+        """Attempts 1 and 2 of the reference's training_utils.load_state_dict -> True; raises what attempt 2 raised otherwise."""
+        try:
+            self.network.load_state_dict(sd["network"])
+            self.optimizer.load_state_dict(sd["optimizer"])
+            self.ema.load_state_dict(sd["ema"])
+            return True
+        except Exception:                         # noqa: BLE001 -- the reference's rule: whatever fails, try the next way
+            pass
+        self.network.load_state_dict(sd["network"], strict=False)
+        self.ema.load_state_dict(sd["ema"], strict=False)
+        return True
+
+    def resume_from_checkpoint(self, checkpoint_path=None, checkpoint_id=None):
+        """The reference's: a path, or {model_dir}/{exp_name}-{checkpoint_id}.pt with the largest id on disk by default.  Sets
+        `it` from the checkpoint (157007 / 159000 where it holds none, as there) -> True; on any failure False, and with a path
+        given `it` = 0."""
+        try:
+            if checkpoint_path is None:
+                if checkpoint_id is None:
+                    name = self.args.exp.exp_name
+                    id_regex = re.compile(f"{name}-(\\d*)\\.pt")
+                    checkpoint_id = max(int(id_regex.search(p).groups()[0]) for p in glob.glob(f"{self.args.model_dir}/{name}-*.pt"))
+                path = f"{self.args.model_dir}/{self.args.exp.exp_name}-{checkpoint_id}.pt"
+            else:
+                path = checkpoint_path
+            checkpoint = torch.load(path, map_location=self.device, pickle_module=_tolerant_pickle, weights_only=False)
+            try:
+                self.it = checkpoint["it"]
+            except KeyError:
+                self.it = 157007 if checkpoint_path is not None else 159000
+            self.load_state_dict(checkpoint)
+            return True
+        except Exception as e:                    # noqa: BLE001 -- the reference's rule: report and train from scratch
+            print(f"Could not resume from checkpoint: {e}")
+            if checkpoint_path is not None:
+                self.it = 0
+            return False
