@@ -806,6 +806,64 @@ int ntm_edm_pre(const float *z, const float *eps, float eps_scale, float snoise,
 int ntm_edm_post(const float *z, const float *F, float cskip, float cout, float b2, float k, int64_t N, float *out, void *stream);
 
 /*
+ * The whole sampler of a network whose every level fits the whole form, in ONE launch (csrc/unet_sampler.hip).  Additions
+ * within ABI version 9.
+ *
+ * ntm_unet_sample_one_launch: n_steps times { ntm_edm_pre, the network's n_stages calls, ntm_edm_post } on B streams of T
+ *   frames, one workgroup per stream (grid (1, B), 1024 threads) walking the steps and the stages with a workgroup barrier
+ *   between them.  Every output is computed by the code of the step-by-step entry points above (one definition per output,
+ *   csrc/unet_steps.h and csrc/unet_block.h), in their order of operations: z is bit-identical to running those entry points
+ *   with the same operands.  Workgroups do not communicate and a workgroup touches only its own stream's rows.
+ *   stages [n_stages] in HOST memory: the network's calls in launch order, read and checked by this entry point on every call;
+ *   stages_dev: the same n_stages records in DEVICE memory, which the kernel walks (the caller copies them once).  A record:
+ *     kind NTM_USTAGE_BLOCK  ntm_unet_resblock_forward(a = src0, b = src1, w3 = init_w, film, 0, w0 = w_first, w1 = w_gated,
+ *                            w2 = w_res, B, &blk, NULL, o0 = out), blk of the whole form (form AUTO or WHOLE, T <= 1024), with
+ *                            film = films + step film_len + film_off: c0 + c1 floats of the step's FiLM row, one vector for all
+ *                            streams.  a == NULL: the network's input [B][1][T] (needs blk.init, blk.T0 == T)
+ *          NTM_USTAGE_DOWN   ntm_unet_down_combine(a = x, b = pyr, w0 = ker, w1 = wc, B, C, F, S, width, taps, o0 = x_out,
+ *                            o1 = pyr_out), F <= 1024.  b == NULL: the network's input (needs F == T)
+ *          NTM_USTAGE_UP     ntm_unet_up_combine(a = x, b = pyr or NULL, pyr_T, w0 = ker, w1 = wc, B, C, F, S, width, taps,
+ *                            o0 = x_out, o1 = pyr_out), S >= 2, F <= 1024, S F <= 2048
+ *          NTM_USTAGE_FINAL  ntm_unet_up_combine with S == 1 (w0 == o0 == NULL, width == taps == 0): the last combiner.
+ *                            o1 == NULL: the network's output [B][T] (needs F == T)
+ *     Fields a kind does not name are ignored.  Every other pointer is a device pointer to a buffer of that entry point's
+ *     layout for B streams; an intermediate is written by one stage and read by later ones, through vector loads.
+ *   scal [n_steps][NTM_UNET_SAMPLE_SCALARS] fp32, per step: eps_scale, snoise, sigma0, cin (ntm_edm_pre's), cskip, cout, b2, k
+ *     (ntm_edm_post's).  films [n_steps][film_len] fp32.  eps_steps: bit i set when step i has the eps draw.
+ *   z0 [B][T]: the first latent.  draws [n_draws][B][T]: per step its eps draw (where eps_steps says so), then its outpainting
+ *     noise n (with a mask, every step): n_draws == popcount(eps_steps below n_steps) + (mask ? n_steps : 0); NULL when 0.
+ *   x_outpaint [B][T], mask [1 or B][T] with mask_stride 0 or T: ntm_edm_pre's, the same for every step; both NULL: no outpainting.
+ *   ws: ntm_unet_sample_workspace_floats(B, T) = 3 B T floats (z after pre, the network's input, the network's output).
+ *   z [B][T]: the sample; also the carry between steps, so it must not alias z0, the draws, x_outpaint, mask or ws.
+ *   Refused (NTM_EINVAL) before anything touches a device, z untouched: null pointers, B outside [0, 65535], T outside [1, 1024],
+ *   n_stages outside [1, NTM_UNET_SAMPLE_MAX_STAGES], n_steps outside [1, NTM_UNET_SAMPLE_MAX_STEPS], an unknown kind, a stage that
+ *   its own entry point refuses or that breaks a bound stated above, film_off < 0 or film_off + c0 + c1 > film_len, n_draws not
+ *   as stated, a mask without x_outpaint, mask_stride neither 0 nor T, z aliasing an input.  B == 0 returns NTM_OK.
+ *   Dynamic LDS: the largest stage's (a block of 16 channels at 1024 frames: 143 360 bytes).  No scratch, no atomics.
+ */
+#define NTM_USTAGE_BLOCK 0
+#define NTM_USTAGE_DOWN 1
+#define NTM_USTAGE_UP 2
+#define NTM_USTAGE_FINAL 3
+#define NTM_UNET_SAMPLE_MAX_STAGES 64
+#define NTM_UNET_SAMPLE_MAX_STEPS 64
+#define NTM_UNET_SAMPLE_SCALARS 8
+typedef struct {
+    int32_t kind;                   /* NTM_USTAGE_* */
+    int32_t C, S, width, taps;      /* the resample stages */
+    int32_t film_off;               /* BLOCK: floats into the step's FiLM row */
+    int64_t F, pyr_T;               /* the resample stages: input frames; UP / FINAL: the pyramid's row length */
+    ntm_unet_block blk;             /* BLOCK */
+    const float *a, *b, *w0, *w1, *w2, *w3;
+    float *o0, *o1;
+} ntm_unet_stage;                   /* 168 bytes */
+int64_t ntm_unet_sample_workspace_floats(int64_t B, int64_t T);
+int ntm_unet_sample_one_launch(const ntm_unet_stage *stages, const ntm_unet_stage *stages_dev, int n_stages, const float *scal,
+                               const float *films, int64_t film_len, int n_steps, uint64_t eps_steps, const float *z0,
+                               const float *draws, int n_draws, const float *x_outpaint, const float *mask, int64_t mask_stride,
+                               int64_t B, int64_t T, float *ws, float *z, void *stream);
+
+/*
  * Training of that network (code/train-diffusion.py): the ResnetBlock in its whole form (T <= NTM_UNET_WHOLE_MAX_T, form AUTO or
  * WHOLE) with its adjoint (csrc/unet_train.hip).  Additions within ABI version 9.  Operands and layouts are
  * ntm_unet_resblock_forward's; with y_0 = W_first gelu(x) and y_{l+1} = (y_l + conv_l(gelu(y_l))) / sqrt 2:

@@ -106,6 +106,10 @@ _SIGNATURES = {
     "ntm_unet_upsample": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "ntm_edm_pre": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64, _vp, _vp, _vp]),
     "ntm_edm_post": (_int, [_vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _i64, _vp, _vp]),
+    # the whole sampler in one launch: stages is a host UnetStage array (unet_stages), stages_dev its copy on the device
+    "ntm_unet_sample_workspace_floats": (_i64, [_i64, _i64]),
+    "ntm_unet_sample_one_launch": (_int, [_vp, _vp, _int, _vp, _vp, _i64, _int, ctypes.c_uint64, _vp, _vp, _int, _vp, _vp, _i64,
+                                          _i64, _i64, _vp, _vp, _vp]),
     # the optimiser step over a list of tensors (additions within ABI version 9): p / g / m / v / dst / src are host arrays of
     # device pointers (ptr_array), n a host int64 array (i64_array)
     "ntm_multi_partials": (_i64, [_vp, _i64]),
@@ -162,6 +166,30 @@ class ConvLayerS(ctypes.Structure):
 def conv_layers_s(spec):
     """((c_in, c_out, k, groups, stride, pad, pad_mode), ...) -> a ConvLayerS array for the ntm_sconvstack entry points."""
     return (ConvLayerS * len(spec))(*[ConvLayerS(*map(int, s)) for s in spec])
+
+
+class UnetBlock(ctypes.Structure):
+    """include/ntm.h ntm_unet_block (64 bytes)."""
+    _fields_ = [("c0", ctypes.c_int32), ("c1", ctypes.c_int32), ("c_out", ctypes.c_int32), ("n_layers", ctypes.c_int32),
+                ("T", ctypes.c_int64), ("T0", ctypes.c_int64), ("off0", ctypes.c_int64), ("T1", ctypes.c_int64),
+                ("off1", ctypes.c_int64), ("init", ctypes.c_int32), ("form", ctypes.c_int32)]
+
+
+USTAGE_KINDS = {"block": 0, "down": 1, "up": 2, "final": 3}     # include/ntm.h NTM_USTAGE_*
+UNET_SAMPLE_MAX_STAGES, UNET_SAMPLE_MAX_STEPS, UNET_SAMPLE_SCALARS = 64, 64, 8     # include/ntm.h NTM_UNET_SAMPLE_*
+UNET_STAGE_BYTES = 168
+
+
+class UnetStage(ctypes.Structure):
+    """include/ntm.h ntm_unet_stage (UNET_STAGE_BYTES): one call of the network in the one-launch sampler's table."""
+    _fields_ = [("kind", ctypes.c_int32), ("C", ctypes.c_int32), ("S", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("taps", ctypes.c_int32), ("film_off", ctypes.c_int32), ("F", ctypes.c_int64), ("pyr_T", ctypes.c_int64),
+                ("blk", UnetBlock)] + [(n, ctypes.c_void_p) for n in ("a", "b", "w0", "w1", "w2", "w3", "o0", "o1")]
+
+
+def unet_stages(stages):
+    """A list of UnetStage -> the host array ntm_unet_sample_one_launch checks."""
+    return (UnetStage * len(stages))(*stages)
 
 
 def ptr_array(tensors):

@@ -574,6 +574,88 @@ int ntm_edm_post(const float *z, const float *F, float cskip, float cout, float 
     return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_edm_post");
 }
 
+// the size checks ntm_unet_sample_workspace_floats and _one_launch share
+static int unet_sample_sizes(const std::string &w, int64_t B, int64_t T)
+{
+    if (B < 0 || B > 65535) return fail(NTM_EINVAL, w + ": B must lie in [0, 65535]");
+    if (T < 1 || T > NTM_UNET_WHOLE_MAX_T) return fail(NTM_EINVAL, w + ": T must lie in [1, 1024]");
+    return NTM_OK;
+}
+
+int64_t ntm_unet_sample_workspace_floats(int64_t B, int64_t T)
+{
+    if (unet_sample_sizes("ntm_unet_sample_workspace_floats", B, T) != NTM_OK) return -1;
+    return 3 * B * T;
+}
+
+// one record of the stage table against the caps the kernel's loops rely on: what the stage's own entry point checks, the whole
+// form, and the null pointers that stand for the network's input and output
+static int unet_stage_check(const std::string &w, const ntm_unet_stage &st, int64_t B, int64_t T, int64_t film_len)
+{
+    if (st.kind == NTM_USTAGE_BLOCK) {
+        const ntm_unet_block &k = st.blk;
+        if (int rc = unet_block_check(w, B, &k)) return rc;
+        if (k.form == NTM_UNET_TILED || k.T > NTM_UNET_WHOLE_MAX_T)
+            return fail(NTM_EINVAL, w + ": a block of " + std::to_string(k.T) + " frames: the whole form only, T <= 1024");
+        const int cin = k.c0 + k.c1;
+        if (st.film_off < 0 || st.film_off + cin > film_len) return fail(NTM_EINVAL, w + ": film_off + c0 + c1 must lie within film_len");
+        if (!st.w2 && cin != k.c_out) return fail(NTM_EINVAL, w + ": an identity residual (w2 == NULL) needs c0 + c1 == c_out");
+        if (!st.a && !(k.init && k.T0 == T)) return fail(NTM_EINVAL, w + ": a == NULL (the network's input) needs blk.init and blk.T0 == T");
+        if (!st.w0 || !st.w1 || !st.o0 || (k.c1 > 0 && !st.b) || (k.init && !st.w3)) return fail(NTM_EINVAL, w + ": null pointer (block stage)");
+        if (st.o0 == st.a || st.o0 == st.b) return fail(NTM_EINVAL, w + ": a block's out must not alias a source");
+        return NTM_OK;
+    }
+    if (st.kind == NTM_USTAGE_DOWN) {
+        if (int rc = unet_resample_check(w, B, st.C, st.F, st.S, st.width, st.taps, st.F)) return rc;
+        if (st.taps != 2 * st.width + st.S) return fail(NTM_EINVAL, w + ": taps must be 2 * width + S (down stage)");
+        if (st.F > NTM_UNET_WHOLE_MAX_T) return fail(NTM_EINVAL, w + ": a down stage takes F <= 1024");
+        if (!st.b && st.F != T) return fail(NTM_EINVAL, w + ": b == NULL (the network's input) needs F == T");
+        if (!st.a || !st.w0 || !st.w1 || !st.o0 || !st.o1) return fail(NTM_EINVAL, w + ": null pointer (down stage)");
+        return NTM_OK;
+    }
+    if (st.kind == NTM_USTAGE_UP || st.kind == NTM_USTAGE_FINAL) {
+        const bool fin = st.kind == NTM_USTAGE_FINAL;
+        if (int rc = unet_resample_check(w, B, st.C, st.F, st.S, st.width, st.taps, (int64_t)st.S * st.F)) return rc;
+        if (fin ? (st.S != 1 || st.taps != 0 || st.width != 0) : (st.S < 2 || st.taps != 2 * st.width + 1))
+            return fail(NTM_EINVAL, w + ": an up stage has S >= 2 and taps == 2 * width + 1, the final one S == 1 and no filter");
+        if (st.F > NTM_UNET_WHOLE_MAX_T || (int64_t)st.S * st.F > 2 * NTM_UNET_WHOLE_MAX_T)
+            return fail(NTM_EINVAL, w + ": an up stage takes F <= 1024 and S F <= 2048");
+        if (st.b && st.pyr_T < st.F) return fail(NTM_EINVAL, w + ": the pyramid is shorter than F");
+        if (st.b && st.pyr_T > 0x7fffffff) return fail(NTM_EINVAL, w + ": pyr_T must be below 2^31");
+        if (!st.a || !st.w1 || (!fin && (!st.w0 || !st.o0 || !st.o1))) return fail(NTM_EINVAL, w + ": null pointer (up stage)");
+        if (fin && !st.o1 && st.F != T) return fail(NTM_EINVAL, w + ": o1 == NULL (the network's output) needs F == T");
+        return NTM_OK;
+    }
+    return fail(NTM_EINVAL, w + ": unknown stage kind " + std::to_string(st.kind));
+}
+
+int ntm_unet_sample_one_launch(const ntm_unet_stage *stages, const ntm_unet_stage *stages_dev, int n_stages, const float *scal,
+                               const float *films, int64_t film_len, int n_steps, uint64_t eps_steps, const float *z0,
+                               const float *draws, int n_draws, const float *x_outpaint, const float *mask, int64_t mask_stride,
+                               int64_t B, int64_t T, float *ws, float *z, void *stream)
+{
+    const std::string w("ntm_unet_sample_one_launch");
+    if (int rc = unet_sample_sizes(w, B, T)) return rc;
+    if (n_stages < 1 || n_stages > NTM_UNET_SAMPLE_MAX_STAGES) return fail(NTM_EINVAL, w + ": n_stages must lie in [1, 64]");
+    if (n_steps < 1 || n_steps > NTM_UNET_SAMPLE_MAX_STEPS) return fail(NTM_EINVAL, w + ": n_steps must lie in [1, 64]");
+    if (film_len < 1 || film_len > 0x7fffffff / NTM_UNET_SAMPLE_MAX_STEPS) return fail(NTM_EINVAL, w + ": film_len must lie in [1, 2^25)");
+    if (!stages) return fail(NTM_EINVAL, w + ": null pointer (stages)");
+    for (int q = 0; q < n_stages; ++q)
+        if (int rc = unet_stage_check(w + ", stage " + std::to_string(q), stages[q], B, T, film_len)) return rc;
+    if (mask && mask_stride != 0 && mask_stride != T) return fail(NTM_EINVAL, w + ": mask_stride must be 0 or T");
+    if (mask ? !x_outpaint : x_outpaint != nullptr) return fail(NTM_EINVAL, w + ": mask and x_outpaint come together");
+    int want = mask ? n_steps : 0;
+    for (int i = 0; i < n_steps; ++i) want += (int)((eps_steps >> i) & 1);
+    if (n_draws != want) return fail(NTM_EINVAL, w + ": n_draws must be " + std::to_string(want) + " (an eps draw per step of eps_steps, "
+                                                     "an outpainting draw per step with a mask)");
+    if (B == 0) return NTM_OK;
+    if (!stages_dev || !scal || !films || !z0 || !ws || !z || (n_draws > 0 && !draws)) return fail(NTM_EINVAL, w + ": null pointer");
+    if (z == z0 || z == draws || z == x_outpaint || z == mask || z == ws) return fail(NTM_EINVAL, w + ": z must not alias an input or ws");
+    hipError_t e = ntm::launch_unet_sampler(stages, stages_dev, n_stages, scal, films, film_len, n_steps, eps_steps, z0, draws,
+                                            x_outpaint, mask, mask_stride, B, T, ws, z, (hipStream_t)stream);
+    return e == hipSuccess ? NTM_OK : hip_fail(e, "ntm_unet_sample_one_launch");
+}
+
 // ntm_diffdel_gru_forward[_ex] (ls == NULL) and ntm_diffdel_gru_forward_esr / _losses share this body
 static int diffdel_impl(const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w_o, int H,
                         const float *x, const float *d, float *y, float *pre_d, int64_t B, int64_t T, float *h_state,

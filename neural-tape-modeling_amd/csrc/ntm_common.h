@@ -198,6 +198,11 @@ hipError_t launch_edm_pre(const float *z, const float *eps, float eps_scale, flo
                           float *net_in, hipStream_t stream);
 hipError_t launch_edm_post(const float *z, const float *F, float cskip, float cout, float b2, float k, int64_t N, float *out,
                            hipStream_t stream);
+// that sampler in one launch (unet_sampler.hip): stages is the host copy ntm_api.hip has checked, stages_dev what the kernel walks
+hipError_t launch_unet_sampler(const ntm_unet_stage *stages, const ntm_unet_stage *stages_dev, int n_stages, const float *scal,
+                               const float *films, int64_t film_len, int n_steps, uint64_t eps_steps, const float *z0,
+                               const float *draws, const float *x_outpaint, const float *mask, int64_t mask_stride, int64_t B,
+                               int64_t T, float *ws, float *z, hipStream_t stream);
 // the training of that network (unet_train.hip): the whole-form block with y_0 .. y_{n-1} saved, its adjoint, the reduction
 int64_t unet_block_wgrad_floats(const ntm_unet_block &k);
 int unet_block_partials(const ntm_unet_block &k);

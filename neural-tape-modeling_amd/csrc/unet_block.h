@@ -226,10 +226,29 @@ __device__ __forceinline__ void unet_block_body(UBlockArgs a, float *ysave)
     }
 }
 
-// unet_kernels.hip: the description of a launch, filled from a block description the API has checked
-UBlockArgs unet_block_args(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
-                           const float *w_first, const float *w_gated, const float *w_res, const ntm_unet_block &k, float *out);
-size_t unet_block_lds_bytes(const UBlockArgs &a);
+__host__ __device__ inline bool ublock_whole(const ntm_unet_block &k) { return k.form == 1 || (k.form == 0 && k.T <= kUW); }
+
+// the description of a launch, filled from a block description the API has checked (on the device too: the one-launch sampler,
+// unet_sampler.hip, fills it per stage from its table)
+__host__ __device__ inline UBlockArgs unet_block_args(const float *src0, const float *src1, const float *init_w, const float *film,
+                                                      int64_t film_stride, const float *w_first, const float *w_gated,
+                                                      const float *w_res, const ntm_unet_block &k, float *out)
+{
+    UBlockArgs a{};
+    a.src0 = src0, a.src1 = src1, a.init_w = k.init ? init_w : nullptr, a.film = film, a.film_stride = film_stride;
+    a.w_first = w_first, a.w_gated = w_gated, a.w_res = w_res, a.out = out;
+    a.c0 = k.c0, a.c1 = k.c1, a.cout = k.c_out, a.nl = k.n_layers;
+    a.T = (int)k.T, a.T0 = (int)k.T0, a.off0 = (int)k.off0, a.T1 = (int)k.T1, a.off1 = (int)k.off1;
+    a.CP = (k.c_out + 3) & ~3;
+    if (ublock_whole(k)) {
+        a.W = ((int)k.T + 15) & ~15, a.tile = a.W, a.halo = 0;
+    } else {
+        a.W = kUW, a.tile = kUTile, a.halo = kUHalo;
+    }
+    a.P = a.W + 16;     // 16 mod 64 floats: the four channel rows of an MFMA operand read fall on 64 different banks
+    return a;
+}
+size_t unet_block_lds_bytes(const UBlockArgs &a);       // unet_kernels.hip
 int ublock_run_end(int l0, int nl);     // layers [l0, l1) of a tiled run
 
 }  // namespace ntm

@@ -22,8 +22,9 @@
 // unet_up_kernel      CombinerUp + Upsample(S) of x and pyr (S phases of 2 width + 1 taps); S = 1: the combiner alone; without
 //                     weights: a plain upsampler (the sampler's 100 Hz -> 44.1 kHz resampler, 441 phases).
 // edm_pre / edm_post  the sampler's step around the network, in the reference's order of operations.
-// The block's arguments and the forward's body are in unet_block.h, which the training kernels (unet_train.hip) share.
-#include "unet_block.h"
+// The block's arguments and the forward's body are in unet_block.h, which the training kernels (unet_train.hip) share; what
+// the other kernels compute per output is in unet_steps.h, which the one-launch sampler (unet_sampler.hip) shares.
+#include "unet_steps.h"
 
 namespace ntm {
 
@@ -36,8 +37,6 @@ int ublock_run_end(int l0, int nl)
     while (l1 < nl && reach + (2 << l1) <= kUHalo) reach += 2 << l1, ++l1;    // a layer of dilation d reaches 2 d a side
     return l1 > l0 ? l1 : l0 + 1;
 }
-
-static bool ublock_whole(const ntm_unet_block &k) { return k.form == 1 || (k.form == 0 && k.T <= kUW); }
 
 int unet_block_launches(const ntm_unet_block &k)
 {
@@ -52,24 +51,6 @@ int64_t unet_block_workspace(int64_t B, const ntm_unet_block &k)
 {
     const int n = unet_block_launches(k);
     return n <= 1 ? 0 : (n == 2 ? 1 : 2) * B * k.c_out * k.T;
-}
-
-UBlockArgs unet_block_args(const float *src0, const float *src1, const float *init_w, const float *film, int64_t film_stride,
-                           const float *w_first, const float *w_gated, const float *w_res, const ntm_unet_block &k, float *out)
-{
-    UBlockArgs a{};
-    a.src0 = src0, a.src1 = src1, a.init_w = k.init ? init_w : nullptr, a.film = film, a.film_stride = film_stride;
-    a.w_first = w_first, a.w_gated = w_gated, a.w_res = w_res, a.out = out;
-    a.c0 = k.c0, a.c1 = k.c1, a.cout = k.c_out, a.nl = k.n_layers;
-    a.T = (int)k.T, a.T0 = (int)k.T0, a.off0 = (int)k.off0, a.T1 = (int)k.T1, a.off1 = (int)k.off1;
-    a.CP = (k.c_out + 3) & ~3;
-    if (ublock_whole(k)) {
-        a.W = ((int)k.T + 15) & ~15, a.tile = a.W, a.halo = 0;
-    } else {
-        a.W = kUW, a.tile = kUTile, a.halo = kUHalo;
-    }
-    a.P = a.W + 16;     // 16 mod 64 floats: the four channel rows of an MFMA operand read fall on 64 different banks
-    return a;
 }
 
 size_t unet_block_lds_bytes(const UBlockArgs &a) { return ((size_t)2 * a.CP * a.P + 2 * kUWn) * sizeof(float); }
@@ -98,39 +79,13 @@ hipError_t launch_unet_block(const float *src0, const float *src1, const float *
     return hipSuccess;
 }
 
-// ---- resample + combine ----------------------------------------------------------------------------------------------------------
-struct UDownArgs {
-    const float *x, *pyr, *ker, *wc;
-    float *x_out, *pyr_out;
-    int C, F, Fo, S, width, taps;
-};
-
+// ---- resample + combine: a thread per output, the output itself in unet_steps.h ---------------------------------------------------
 __global__ __launch_bounds__(256) void unet_down_kernel(UDownArgs a)
 {
     const int j = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
-    const int64_t b = blockIdx.z;
     if (j >= a.Fo) return;
-    const float *xr = a.x + (b * a.C + c) * a.F, *pr = a.pyr + b * a.F;
-    const int base = j * a.S - a.width;      // j S < F + S <= 2^31 is checked by the caller
-    float xd = 0.0f, pd = 0.0f;
-    for (int i = 0; i < a.taps; ++i) {
-        const int g = base + i;
-        if (g >= 0 && g < a.F) {
-            const float k = a.ker[i];
-            xd = fmaf(k, xr[g], xd);
-            pd = fmaf(k, pr[g], pd);
-        }
-    }
-    a.x_out[(b * a.C + c) * a.Fo + j] = (a.wc[c] * pd + xd) * kRsqrt2;
-    if (c == 0) a.pyr_out[b * a.Fo + j] = pd;
+    udown_one(a, blockIdx.z, c, j);
 }
-
-struct UUpArgs {
-    const float *x, *pyr, *ker, *wc;
-    float *x_out, *pyr_out;
-    int C, F, S, width, taps, pyr_T;
-    int64_t Fo;
-};
 
 constexpr int kUpStage = 256 + 64;   // input frames under 256 outputs: 256 / S + 1 + taps - 1, taps <= 64
 
@@ -143,42 +98,16 @@ __global__ __launch_bounds__(256) void unet_up_kernel(UUpArgs a)
     const int j = (int)(n / a.S), ph = (int)(n - (int64_t)j * a.S);
     if (!pyramid) {                              // a channel of x (block-uniform)
         if (n >= a.Fo) return;
-        const float *xr = a.x + (b * a.C + c) * a.F, *kr = a.ker + ph * a.taps;
-        float v = 0.0f;
-        for (int i = 0; i < a.taps; ++i) {
-            const int g = j + i - a.width;
-            if (g >= 0 && g < a.F) v = fmaf(kr[i], xr[g], v);
-        }
-        a.x_out[(b * a.C + c) * a.Fo + n] = v;
+        uup_x_one(a, b, c, n, j, ph);
         return;
     }
     // the pyramid: the combined frames under this workgroup's outputs once, then the filter
     const int64_t nl = (n0 + 255 < a.Fo ? n0 + 255 : a.Fo - 1);
     const int jlo = (int)(n0 / a.S) - a.width, cnt = (int)(nl / a.S) - (int)(n0 / a.S) + 1 + (a.taps > 0 ? a.taps - 1 : 0);
-    for (int t = threadIdx.x; t < cnt; t += 256) {
-        const int g = jlo + t;
-        float v = 0.0f;
-        if (g >= 0 && g < a.F) {
-            if (a.wc) {
-                for (int ch = 0; ch < a.C; ++ch) v = fmaf(a.wc[ch], a.x[(b * a.C + ch) * a.F + g], v);
-                if (a.pyr) v = (a.pyr[b * a.pyr_T + g] + v) * kRsqrt2;
-            } else {
-                v = a.x[b * a.F + g];
-            }
-        }
-        pn[t] = v;
-    }
+    for (int t = threadIdx.x; t < cnt; t += 256) pn[t] = uup_combined(a, b, jlo + t);
     __syncthreads();
     if (n >= a.Fo) return;
-    float v;
-    if (a.S == 1 && a.taps == 0) {
-        v = pn[threadIdx.x];
-    } else {
-        const float *kr = a.ker + ph * a.taps;
-        v = 0.0f;
-        for (int i = 0; i < a.taps; ++i) v = fmaf(kr[i], pn[j + i - a.width - jlo], v);
-    }
-    a.pyr_out[b * a.Fo + n] = v;
+    uup_pyr_one(a, b, n, ph, pn + (j - a.width - jlo));
 }
 
 hipError_t launch_unet_down(const float *x, const float *pyr, const float *ker, const float *wc, int64_t B, int C, int64_t F, int S,
@@ -199,40 +128,19 @@ hipError_t launch_unet_up(const float *x, const float *pyr, int64_t pyr_T, const
 }
 
 // ---- the EDM step around the network ----------------------------------------------------------------------------------------------
-struct EdmPreArgs {
-    const float *z, *eps, *mask, *x_out, *n;
-    float *z_out, *net_in;
-    float eps_scale, snoise, sigma0, cin;
-    int64_t mask_stride, T, N;
-};
-
-// z' = z + eps_scale (eps snoise);  z' = mask (x_out + n sigma0) + (1 - mask) z';  net_in = cin z'   -- each product and sum
-// rounded on its own, as the reference's tensor expressions are
 __global__ __launch_bounds__(256) void edm_pre_kernel(EdmPreArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.N) return;
-    float z = a.z[i];
-    if (a.eps) z = __fadd_rn(z, __fmul_rn(a.eps_scale, __fmul_rn(a.eps[i], a.snoise)));
-    if (a.mask) {
-        const float m = a.mask[(i / a.T) * a.mask_stride + i % a.T];
-        const float xn = __fadd_rn(a.x_out[i], __fmul_rn(a.n[i], a.sigma0));
-        z = __fadd_rn(__fmul_rn(m, xn), __fmul_rn(__fsub_rn(1.0f, m), z));
-    }
-    a.z_out[i] = z;
-    a.net_in[i] = __fmul_rn(a.cin, z);
+    edm_pre_one(a, i);
 }
 
-// x0 = cskip z + cout F;  score = (x0 - z) / b2;  z <- z - k score
 __global__ __launch_bounds__(256) void edm_post_kernel(const float *z, const float *F, float cskip, float cout, float b2, float k,
                                                        int64_t N, float *out)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const float zi = z[i];
-    const float x0 = __fadd_rn(__fmul_rn(cskip, zi), __fmul_rn(cout, F[i]));
-    const float score = __fdiv_rn(__fsub_rn(x0, zi), b2);
-    out[i] = __fsub_rn(zi, __fmul_rn(k, score));
+    edm_post_one(z, F, cskip, cout, b2, k, i, out);
 }
 
 hipError_t launch_edm_pre(const float *z, const float *eps, float eps_scale, float snoise, const float *mask, int64_t mask_stride,

@@ -13,7 +13,9 @@ code/networks/unet_1d.py): the wow-and-flutter delay trajectories that drive Dif
                                FiLM and the embedding are torch ops under autograd
   down_combine / up_combine    one resample + combine step on the device; differentiable (the same nodes) when an operand
                                requires a gradient
-  DiffusionGenerator(args, device)   the EDM sampler with the reference's attributes and methods
+  DiffusionGenerator(args, device)   the EDM sampler with the reference's attributes and methods; sampler="one_launch" (opt-in)
+                               runs a whole sampler whose levels all fit one workgroup as ONE launch (csrc/unet_sampler.hip), bit
+                               for bit what the default step-by-step path gives
   EDMTrainer(args, network, optimizer, device, backend)   the EDM training step and EMA of code/train-diffusion.py
 
 The sampler and `forward` are inference only.  Two additions to the reference's protocol, both keyword arguments:
@@ -269,12 +271,8 @@ class CombinerDown(nn.Module):
         return (self.conv1x1(pyr) + x) / (2 ** 0.5)
 
 
-class BlockSpec(_lib.ctypes.Structure):
-    """include/ntm.h ntm_unet_block."""
-    _fields_ = [("c0", _lib.ctypes.c_int32), ("c1", _lib.ctypes.c_int32), ("c_out", _lib.ctypes.c_int32),
-                ("n_layers", _lib.ctypes.c_int32), ("T", _lib.ctypes.c_int64), ("T0", _lib.ctypes.c_int64),
-                ("off0", _lib.ctypes.c_int64), ("T1", _lib.ctypes.c_int64), ("off1", _lib.ctypes.c_int64),
-                ("init", _lib.ctypes.c_int32), ("form", _lib.ctypes.c_int32)]
+BlockSpec = _lib.UnetBlock       # include/ntm.h ntm_unet_block
+SAMPLERS = ("steps", "one_launch")
 
 
 def _require_hip(what, *tensors):
@@ -287,9 +285,9 @@ class _Call:
     """One C call with its arguments bound: `args` in the entry point's order with the stream last, `slot` the positions by name
     of the pointers a plan patches, `out` what the call writes, `ws` its workspace, `launches` the kernels it starts."""
 
-    def __init__(self, name, args, slot, out, ws=None, launches=1):
+    def __init__(self, name, args, slot, out, ws=None, launches=1, spec=None):
         self.name, self.fn, self.args, self.slot = name, getattr(_lib.lib(), name), args, slot
-        self.out, self.ws, self.launches = out, ws, launches
+        self.out, self.ws, self.launches, self.spec = out, ws, launches, spec
 
     def __call__(self, stream):
         self.args[-1] = stream
@@ -319,7 +317,7 @@ def _bind_resblock(dev, src0, film, w_first, w_gated, w_res=None, src1=None, off
     args = [_addr(src0), _addr(src1), _addr(init_w), _addr(film), 0 if film.shape[0] == 1 else film.stride(0), _addr(w_first),
             _addr(w_gated), _addr(w_res), B, _lib.ctypes.byref(spec), _addr(ws), _addr(out), None]
     # above NTM_UNET_WHOLE_MAX_T the tiled form runs the eight dilations in two launches
-    return _Call("ntm_unet_resblock_forward", args, {"src0": 0, "film": 3}, out, ws, launches=2 if T > WHOLE_MAX_T else 1)
+    return _Call("ntm_unet_resblock_forward", args, {"src0": 0, "film": 3}, out, ws, launches=2 if T > WHOLE_MAX_T else 1, spec=spec)
 
 
 def _bind_down(dev, x, pyr, kernel, wc, S, width):
@@ -485,6 +483,28 @@ class _Plan:
             call.args[-1] = stream
             _lib.check(call.fn(*call.args), call.name)
 
+    def stages(self):
+        """The evaluation as records of the one-launch sampler's table (_lib.UnetStage, include/ntm.h ntm_unet_stage), in launch
+        order.  They are read off `calls`, the list run() launches, so the two sampler modes cannot list different calls.  What
+        run() patches per evaluation -- the input, the FiLM rows, the output -- is null in a record: the kernel puts the
+        network's input, the step's FiLM row (from film_off) and the network's output there."""
+        patched = {(id(a), pos) for a, pos in self.inputs} | {(id(self.output[0]), self.output[1])}
+        kinds, out = _lib.USTAGE_KINDS, []
+        for c in self.calls:
+            a = [None if (id(c.args), i) in patched else v for i, v in enumerate(c.args)]
+            if c.name == "ntm_unet_resblock_forward":
+                st = _lib.UnetStage(kind=kinds["block"], film_off=c.film_off, blk=c.spec, a=a[0], b=a[1], w3=a[2], w0=a[5],
+                                    w1=a[6], w2=a[7], o0=a[11])
+            elif c.name == "ntm_unet_down_combine":
+                st = _lib.UnetStage(kind=kinds["down"], a=a[0], b=a[1], w0=a[2], w1=a[3], C=a[5], F=a[6], S=a[7], width=a[8],
+                                    taps=a[9], o0=a[10], o1=a[11])
+            else:
+                assert c.name == "ntm_unet_up_combine", c.name
+                st = _lib.UnetStage(kind=kinds["final" if c is self.calls[-1] else "up"], a=a[0], b=a[1], pyr_T=a[2], w0=a[3],
+                                    w1=a[4], C=a[6], F=a[7], S=a[8], width=a[9], taps=a[10], o0=a[11], o1=a[12])
+            out.append(st)
+        return out
+
     def add(self, name, call, buf):
         self.calls.append(call)
         self.buffers[name] = buf
@@ -496,6 +516,7 @@ class _Plan:
         call = _bind_resblock(self.dev, x, self.film[:, o:o + blk.dim], blk.first_conv[1].weight, self.gated[k], res, skip, off,
                               init_w=self.init_w if first else None)
         self.films.append((call.args, call.slot["film"], 4 * o))
+        call.film_off = o
         if x is self.x:
             self.inputs.append((call.args, call.slot["src0"]))
         return self.add(name, call, call.out)
@@ -603,6 +624,13 @@ class UNet1D(nn.Module):
         if self.depth < 2:
             raise ValueError("UNet1D: depth >= 2 (the last level reuses the combiner of the level before, as the reference does)")
         return self.ups[self.depth - 2][2]
+
+    def level_lengths(self, T):
+        """Frames of the network's levels for an input of T frames, top first: the lengths of its ResnetBlocks."""
+        out = [int(T)]
+        for S in self.Ss[:self.depth - 1]:
+            out.append(-(-out[-1] // S))
+        return out
 
     # -- the torch path --
     def forward_torch(self, inputs, sigma, record=None):
@@ -720,9 +748,17 @@ def load_checkpoint(path, device="cpu"):
 
 class DiffusionGenerator:
     """The reference's DiffusionGenerator.  On a HIP device every method runs the HIP path (network and EDM step kernels); with
-    hip=False, or on the CPU, the torch path -- the reference's expressions on forward_torch."""
+    hip=False, or on the CPU, the torch path -- the reference's expressions on forward_torch.
+    sampler (also a plain attribute, read by every call): "steps", one sampler step as ntm_edm_pre, the network's launches and
+    ntm_edm_post; "one_launch", the whole sampler as ONE launch (ntm_unet_sample_one_launch, csrc/unet_sampler.hip) -- the same
+    bits, for a network whose every level is at most 1024 frames at seg_len (the trajectory nets), HIP path only; anything it
+    cannot run raises, it never falls back to "steps".  last_launches: this project's launches in the last sampler run (torch's
+    own -- the draws, their stacking, the first latent's scaling -- not counted)."""
 
-    def __init__(self, args, device, hip=None):
+    def __init__(self, args, device, hip=None, sampler="steps"):
+        if sampler not in SAMPLERS:
+            raise ValueError(f"DiffusionGenerator: sampler {sampler!r}; built: {SAMPLERS}")
+        self.sampler, self.last_launches, self._consts = sampler, 0, None
         self.args, self.device = args, torch.device(device)
         self.hip = self.device.type == "cuda" if hip is None else bool(hip)
         self.network = UNet1D(args, self.device)
@@ -819,6 +855,10 @@ class DiffusionGenerator:
         return d
 
     def _sample(self, B, x_outpaint=None, mask=None, draws=None):
+        if self.sampler not in SAMPLERS:
+            raise ValueError(f"DiffusionGenerator: sampler {self.sampler!r}; built: {SAMPLERS}")
+        if self.sampler == "one_launch":
+            return self._sample_one_launch(B, x_outpaint, mask, draws)
         steps = self._plan()
         z = self._draw(draws, B) * self.schedule[0]
         if self.hip and mask is not None:                  # once per sample: every step reads the same two
@@ -835,6 +875,64 @@ class DiffusionGenerator:
             if mask is not None:
                 z = mask * (x_outpaint + n.to(z) * s0) + (1 - mask) * z
             z = self.ode_update(z, s1, s0)
+        self.last_launches = len(steps) * (self.network._plan_for(B, self.seg_len, False, z.device).launches + 2) if self.hip else 0
+        return z
+
+    def _one_launch_consts(self):
+        """The per-step operands of the one-launch sampler, made once per _plan() and Snoise: scal (steps, 8) -- the float32
+        values _hip_step hands ntm_edm_pre and ntm_edm_post --, the steps' FiLM rows stacked, and the bit set of the steps
+        that draw eps."""
+        steps, sn = self._plan(), float(self.Snoise)
+        if self._consts is None or self._consts[0] is not steps or self._consts[1] != sn:
+            rows = [[st["f"]["eps"], sn] + [st["f"][n] for n in ("s0", "cin", "cskip", "cout", "b2", "k")] for st in steps]
+            scal = torch.tensor(rows, dtype=torch.float32).to(self.device)
+            films = torch.cat([st["films"] for st in steps], 0).contiguous()
+            bits = sum(1 << i for i, st in enumerate(steps) if st["eps"] is not None)
+            self._consts = (steps, sn, scal, films, bits)
+        return self._consts[2:]
+
+    def _sample_one_launch(self, B, x_outpaint, mask, draws):
+        """_sample as one launch: the same draws taken in the same order first, then ntm_unet_sample_one_launch on the stage
+        table of the step path's own plan (cached with it: per B, seg_len and state of the parameters)."""
+        what, T = "DiffusionGenerator(sampler='one_launch')", self.seg_len
+        if not self.hip or self.device.type != "cuda":
+            raise RuntimeError(f"{what}: HIP device only (no CPU fallback, no torch path); supported: {SUPPORTED}")
+        lengths = self.network.level_lengths(T)
+        if max(lengths) > WHOLE_MAX_T:
+            raise RuntimeError(f"{what}: every level must fit one workgroup, at most {WHOLE_MAX_T} frames; at seg_len {T} the "
+                               f"levels have {lengths} frames, too long: {[n for n in lengths if n > WHOLE_MAX_T]}.  "
+                               "Use sampler='steps'")
+        steps = self._plan()
+        if len(steps) > _lib.UNET_SAMPLE_MAX_STEPS:
+            raise RuntimeError(f"{what}: {len(steps)} steps, at most {_lib.UNET_SAMPLE_MAX_STEPS}")
+        z0 = (self._draw(draws, B) * self.schedule[0]).float().contiguous()
+        if mask is not None:
+            x_outpaint, mask = self._outpaint_operands(B, T, x_outpaint, mask)
+        taken = []
+        for st in steps:
+            if st["eps"] is not None:
+                taken.append(self._draw(draws, B))
+            if mask is not None:
+                taken.append(self._draw(draws, B))
+        stacked = torch.stack([d.float() for d in taken]) if taken else None
+        scal, films, bits = self._one_launch_consts()
+        L, plan = _lib.lib(), self.network._plan_for(B, T, False, self.device)
+        if getattr(plan, "one_launch", None) is None:
+            host = _lib.unet_stages(plan.stages())
+            if len(host) > _lib.UNET_SAMPLE_MAX_STAGES:
+                raise RuntimeError(f"{what}: {len(host)} calls per evaluation, at most {_lib.UNET_SAMPLE_MAX_STAGES}")
+            table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.device)
+            n = L.ntm_unet_sample_workspace_floats(B, T)
+            if n < 0:
+                raise _lib.NtmError(f"ntm_unet_sample_workspace_floats refused: {L.ntm_last_error().decode()}")
+            plan.one_launch = (host, table, torch.empty(max(n, 1), dtype=torch.float32, device=self.device))
+        host, table, ws = plan.one_launch
+        z = torch.empty_like(z0)
+        _lib.check(L.ntm_unet_sample_one_launch(host, _lib.ptr(table), len(host), _lib.ptr(scal), _lib.ptr(films), films.shape[1],
+                                                len(steps), bits, _lib.ptr(z0), _lib.ptr(stacked), len(taken), _lib.ptr(x_outpaint),
+                                                _lib.ptr(mask), 0 if mask is None or mask.shape[0] == 1 else T, B, T, _lib.ptr(ws),
+                                                _lib.ptr(z), _lib.current_stream()), "ntm_unet_sample_one_launch")
+        self.last_launches = 1
         return z
 
     @staticmethod
